@@ -1,18 +1,25 @@
 """Headline benchmark: object-pairs/sec of the relation-query + LMM-decode path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic image per rank: BASELINE.json config C3
 (1024x1024, 50 masks = 2450 ordered pairs, relation Q-Former + existence head + top-20 selection +
 batched greedy Llama-2-7B-shaped decode of 16 tokens), random-init weights, inputs already resident in HBM;
 one `head(inputs)` call per step, its result awaited (wall time of ONE head call).
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = milliseconds of
+one timed step, `dtype`, `config`); every other figure described below is measured only with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (the caller's relation triples and scores as one
+[objects, objects, relation classes] array, the existence logits and probabilities of every pair, the selected pairs,
+their token ids and first-step logits) as DIR/<name>.npy; the inputs and weights are seeded, so two builds run with the
+same arguments can be compared output for output.
+
 PRECISION OF THE HEADLINE: the reference runs this path in fp32 (V4:99-100 loads the LLM without a dtype) and the
 north star's tolerance (logits 1e-3, argmax-exact) is an fp32 statement, so `value` is measured in the `fp32s` mode:
 fp32 weights, activations, KV cache, norms, softmaxes and decode-step projections (26.4 GB of fp32 weights streamed
 per decode step); the prompt pass's and the Q-Former's projections are split-fp16 products (x.w = xh.wh + xh.wl +
 xl.wh on the 16-bit matrix cores, fp32 accumulation: 3e-7 relative, the library SGEMM's own error class).  The line's
-`parity` block re-checks that mode against the CPU oracle in the same run.  The 16-bit figures of earlier rounds
+`parity` block (`--full`) re-checks that mode against the CPU oracle in the same run.  The 16-bit figures of earlier rounds
 (`mixed`: fp16 operands, outside the tolerance) and the exact-fp32 figures are sub-objects, as is BASELINE config C2
 (`c2`).  `--workload rq` times config C2 alone.
 
@@ -21,19 +28,19 @@ when `--gpus N` is given without a rendezvous in the environment): WEAK scaling.
 EVERY image's pairs are sharded over all N ranks, existence probabilities are all-gathered, every rank runs the
 same deterministic top-K, the selected pair features are reduce-scattered to the image's decoding rank
 (openpsg_amd/dist.py).  Per-rank work is that of one image, so `value` grows with N by construction; what the
-multi-GPU line measures is the cost of the four collectives per step.  The line therefore also carries
+multi-GPU line measures is the cost of the four collectives per step.  With `--full` the line therefore also carries
 `strong_scaling`: ONE BASELINE-C4 image (100 masks, 9900 pairs) for all N ranks, pairs sharded, the K decodes
 dealt round-robin - its latency is bounded below by the 16 weight passes of the decode (no tensor parallelism in
 scope), which is stated next to the number.
 
-Round 6 additions to the line: `frozen_fp16_checkpoint` is timed exactly like the headline (same steps / warm-up, its
+Round 6 additions to the `--full` line: `frozen_fp16_checkpoint` is timed exactly like the headline (same steps / warm-up, its
 own roofline.image terms): the same mode over LLM matrices that hold fp16 VALUES, as the reference's frozen checkpoint does;
 `c4_single_gpu` = BASELINE C4 (100 masks) on this one GPU; `batched_decode` = head.forward_batch at 4 / 8 images per step in
 the headline mode (BASELINE C5's batch at the reference's precision); `parity.modes.*.decode_7b_32_layers` = the oracle's
 UN-TRUNCATED 32-layer fp32 decode of a pair (the one cpu_baseline times) against the fp32s head on the same weights, both
 weight kinds; multi-GPU lines add `strong_scaling_rq` (C4's sharded part alone) beside `strong_scaling`.
 
-The JSON line also carries
+With `--full` the JSON line also carries
   roofline     - the dominant kernel (skinny_gemm_f32_kernel: HBM stream of the fp32 LLM weights in the decode
                  steps), timed with HIP events on the launch stream right after the timed region with the
                  same weights and shapes (inside the region the decode is ONE graph replay, which has no
@@ -111,6 +118,14 @@ def parse():
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the one-image strong-scaling figures")
     ap.add_argument("--no-c4", action="store_true", help="N = 1: skip the C4 (100 masks) single-GPU point")
     ap.add_argument("--pair-chunk", type=int, default=0, help="pairs per Q-Former pass (0: the head's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: roofline, two_in_flight, stages, "
+                         "c4_single_gpu, batched_decode, exact_fp32, frozen_fp16_checkpoint, mixed, c2, strong scaling, "
+                         "cpu_baseline and parity (the --no-* switches above select among them).  Off: the line holds "
+                         "the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32 / "
+                         "float64; integer results as float64), rank 0")
     a = ap.parse_args()
     if a.dtype is None:
         a.dtype = "fp32s" if a.workload == "full" else "bf16"
@@ -769,6 +784,99 @@ def time_steps(step, warmup, steps):
     return time.perf_counter() - t0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20          # elements kept of an array too large to write whole (fixed seeded positions)
+
+
+def output_arrays(obj, name="", out=None):
+    """Flattens a step's results (dicts / lists / tensors / arrays / numbers) into {name: float32 or float64 array}:
+    floating results as float32 (float64 kept), integer and boolean results as float64 (exact).  Strings, None and
+    private keys (leading '_') are left out."""
+    import numpy as np
+    out = {} if out is None else out
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            if not str(k).startswith("_"):
+                output_arrays(v, f"{name}.{k}" if name else str(k), out)
+        return out
+    if isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        obj = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t).cpu().numpy()
+    elif isinstance(obj, (list, tuple)) and any(isinstance(v, (dict, list, tuple, torch.Tensor, np.ndarray)) for v in obj):
+        try:                                                           # rows of numbers: one array
+            arr = np.asarray(obj)
+            if arr.dtype.kind in "biuf":
+                obj = arr
+        except (ValueError, TypeError):                               # ragged, or device tensors inside
+            pass
+        if not isinstance(obj, np.ndarray):
+            for i, v in enumerate(obj):
+                output_arrays(v, f"{name}.{i}", out)
+            return out
+    if obj is None or isinstance(obj, str):
+        return out
+    arr = np.asarray(obj)
+    if arr.dtype.kind not in "biuf":
+        return out
+    out[name] = arr.astype(np.float64 if arr.dtype.kind in "biu" or arr.dtype == np.float64 else np.float32)
+    return out
+
+
+def dense_relations(obj, n_obj):
+    """A caller's result dict(rel_pred = [[subject, object, relation], ...], rel_score = [...]) as ONE array of fixed
+    shape, `relation_scores` [objects, objects, relation classes] holding each predicted triple's score (0 elsewhere):
+    the same information as the two lists, and a result without relations is an array of zeros, not an empty one."""
+    if isinstance(obj, (list, tuple)):
+        return [dense_relations(v, n_obj) for v in obj]
+    if not (isinstance(obj, dict) and "rel_pred" in obj):
+        return obj
+    import numpy as np
+    from openpsg_amd.categories import relation_categories
+    rel = np.zeros((n_obj, n_obj, len(relation_categories)), dtype=np.float32)
+    for (s_, o_, r_), sc in zip(obj["rel_pred"], obj.get("rel_score") or [1] * len(obj["rel_pred"])):
+        rel[int(s_), int(o_), int(r_)] = float(sc)
+    rest = {k: v for k, v in obj.items() if k not in ("rel_pred", "rel_score")}
+    return dict(rest, relation_scores=rel)
+
+
+def last_step_outputs(a, single, res, head, extra=None):
+    """What a caller of the timed path received from its last timed step (its relation triples and scores as
+    `dense_relations`), plus the path's own per-image results of that step (existence logits and probabilities of every
+    pair, the selected pairs, the decoded token ids and the first decode step's logits of the full path; the selected
+    pairs' features of `--workload rq`)."""
+    arrays = output_arrays(dense_relations(res, a.objects), "result")
+    last = head.last if (single and a.workload == "full" and a.images_per_step == 1 and a.in_flight <= 1) else None
+    if last is not None:
+        for k in ("exist_logit", "exist_prob", "selected", "tokens", "first_logits"):
+            if k in last:
+                output_arrays(last[k], k, arrays)
+    if extra:
+        output_arrays(extra, "", arrays)
+    return arrays
+
+
+def dump_outputs(arrays, out_dir):
+    """DIR/<name>.npy per non-empty array, DUMP_LIMIT_BYTES in all: an array larger than an eighth of that is replaced by
+    DUMP_SAMPLE of its elements at fixed (seed 0) flat positions, written as <name>.sample.npy next to the positions
+    (<name>.sample_index.npy)."""
+    import numpy as np
+    files = {}
+    for name, arr in sorted(arrays.items()):
+        if arr.size == 0:                                              # nothing to compare
+            continue
+        if arr.nbytes > DUMP_LIMIT_BYTES // 8:
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, DUMP_SAMPLE, replace=False))
+            files[f"{name}.sample_index"] = idx.astype(np.float64)
+            name, arr = f"{name}.sample", arr.reshape(-1)[idx]
+        files[name] = arr
+    total = sum(arr.nbytes for arr in files.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total >> 20} MB of outputs, more than {DUMP_LIMIT_BYTES >> 20} MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -799,6 +907,7 @@ def main():
 
     drain = lambda: None  # noqa: E731  (a pipelined step replaces it)
     per_rank = 1
+    rq_last = {}                                                       # --workload rq: the last step's stage results
     if single:
         scene = make_scene((a.size, a.size), N, seed=0, device=str(dev), num_categories=a.categories)
         inputs = scene_inputs(scene)
@@ -820,8 +929,10 @@ def main():
                 return pending.popleft().result() if len(pending) >= a.in_flight else None
 
             def drain():
+                res = None
                 while pending:
-                    pending.popleft().result()
+                    res = pending.popleft().result()
+                return res
         elif a.workload == "full":
             def step():                                                # ONE head call, its result awaited
                 return head(inputs)
@@ -833,7 +944,8 @@ def main():
             def step():
                 rq = head.run_relation_query(scene["mask_features"], scene["img_meta"], obj_ids, names,
                                              scene["pan_results"])
-                head.selected_pair_features(rq)                 # pair_feature of the selected pairs is part of the stage
+                pf = head.selected_pair_features(rq)            # pair_feature of the selected pairs is part of the stage
+                rq_last.update(exist_logit=rq["exist_logit"], exist_prob=rq["exist_prob"], pair_feature=pf)
                 return rq["selected"].cpu()
         barrier = lambda: None  # noqa: E731
     else:
@@ -855,9 +967,10 @@ def main():
     torch.cuda.synchronize()
     barrier()
     t0 = time.perf_counter()
+    res = None
     for _ in range(a.steps):
-        step()
-    drain()                                                            # every submitted image's result is taken
+        res = step()
+    tail = drain()                                                     # every submitted image's result is taken
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -867,9 +980,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     plain = single and a.workload == "full" and a.images_per_step == 1
+    if a.dump_outputs and rank == 0:                                   # before anything else runs the head again
+        dump_outputs(last_step_outputs(a, single, res if tail is None else tail, head, rq_last), a.dump_outputs)
 
     strong = None
-    if not single and not a.no_strong:
+    if a.full and not single and not a.no_strong:
         # STRONG scaling: one BASELINE-C4 image (100 masks) for all ranks; max over ranks like the headline
         import torch.distributed as dist
         from openpsg_amd.dist import PairShardedPipeline
@@ -908,7 +1023,7 @@ def main():
                            "relation query and the compute-bound prompt pass shrink with N"}
 
     strong_rq = None
-    if not single and not a.no_strong:
+    if a.full and not single and not a.no_strong:
         # the part of C4 that actually shards: relation query + existence head + all-gather + top-20 + the
         # selected pairs' features, no decode - the curve north_star asks for at 1/2/4/8 GPUs
         import torch.distributed as dist
@@ -974,7 +1089,7 @@ def main():
                   "LDS-DMA rings; fp32 weights)") if f32 else \
                  "skinny_gemm_dma_kernel (psg_skinny_gemm; 8-wave slabs, 11-wave for gate/up, 12-wave for q/k/v)"
         pmc_file = "pmc_skinny_gemm_f32.json" if f32 else "pmc_skinny_gemm.json"
-        if not a.no_roofline and a.workload == "full":
+        if a.full and not a.no_roofline and a.workload == "full":
             line["roofline"] = decode_roofline(head, N, pmc_file, k_name)
             if plain and a.in_flight <= 1:
                 line["roofline"]["image"] = image_floor(head, a, a.dtype, line["roofline"]["bytes_per_decode_step"], ms_step)
@@ -987,7 +1102,7 @@ def main():
                                 "qformer_cls_attn_input_kernel)", "achieved": round(ach, 1), "peak": peak / mult / 1e12,
                                 "unit": "TFLOP/s", "frac": round(ach * 1e12 * mult / peak, 4), "traffic": None,
                                 "flops_per_step": int(fl)}
-        if plain:
+        if plain and a.full:
             # the same mode with two images in flight (fixed form, no best-of selection): head.submit on two slot streams
             try:
                 k2 = max(6, a.steps // 2)
@@ -1060,7 +1175,7 @@ def main():
                 bd["decode_projections"] = "library SGEMM over the fp32 weights (exact), 33..160 rows"
                 line["batched_decode"] = bd
         # ---- sub-objects measured with their own heads: the headline head is released first -------------------------
-        if plain:
+        if plain and a.full:
             import copy
             del head
             torch.cuda.empty_cache()
@@ -1185,7 +1300,7 @@ def main():
         if strong_rq is not None:
             line["strong_scaling_rq"] = strong_rq
         oracle_part = None
-        if not a.no_cpu_baseline and single:
+        if a.full and not a.no_cpu_baseline and single:
             scene_cpu = make_scene((a.size, a.size), N, seed=0)
             line["cpu_baseline"], oracle_part = cpu_baseline(a, scene_cpu)
         if not a.no_parity and single and a.images_per_step == 1 and oracle_part is not None:

@@ -12,7 +12,7 @@ db() { ls "$1"/*/*_results.db 2>/dev/null | head -1; }
 run() { local d=$1; shift; rm -rf "$d"; rocprofv3 "$@" > "$d.log" 2>&1; }
 
 # 1. headline benchmark, per-kernel durations
-run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-batched
+run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-batched
 python tools/prof_summary.py "$(db /tmp/p_full)" "$OUT/${TAG}_bench_full_kernel_stats.csv" > /dev/null
 grep '^{"metric"' /tmp/p_full.log | tail -1 > "$OUT/${TAG}_bench_full_line.json"
 # 2. relation-query-only workload (BASELINE C2)

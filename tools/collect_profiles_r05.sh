@@ -9,9 +9,9 @@ export TMPDIR=/tmp
 db() { ls "$1"/*/*_results.db 2>/dev/null | head -1; }
 run() { local d=$1; shift; rm -rf "$d"; rocprofv3 "$@" > "$d.log" 2>&1; }
 # 1. the default command, as the driver runs it
-python bench.py --steps 20 --warmup 5 2> "$OUT/bench_default.err" | grep '^{"metric"' | tail -1 > "$OUT/${TAG}_bench_default_line.json"
+python bench.py --full --steps 20 --warmup 5 2> "$OUT/bench_default.err" | grep '^{"metric"' | tail -1 > "$OUT/${TAG}_bench_default_line.json"
 # 2. per-kernel durations of the headline path (kernel trace + stats; no counters in this pass)
-run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-mixed --no-exact --no-frozen16
+run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-mixed --no-exact --no-frozen16
 python tools/prof_summary.py "$(db /tmp/p_full)" "$OUT/${TAG}_bench_full_kernel_stats.csv" > /dev/null
 grep '^{"metric"' /tmp/p_full.log | tail -1 > "$OUT/${TAG}_bench_full_line.json"
 # 3. dominant kernel (fp32 decode GEMM): HBM traffic, two PMC passes
@@ -22,7 +22,7 @@ python tools/pmc_summary.py "$(db /tmp/p_fetch32)" "$(db /tmp/p_write32)" "$OUT/
 run /tmp/p_fetchw --pmc FETCH_SIZE --kernel-trace -d /tmp/p_fetchw -- env PSG_BENCH_NOLIB=1 python tools/bench_kernels.py skinnysplit
 run /tmp/p_writew --pmc WRITE_SIZE --kernel-trace -d /tmp/p_writew -- env PSG_BENCH_NOLIB=1 python tools/bench_kernels.py skinnysplit
 python tools/pmc_summary.py "$(db /tmp/p_fetchw)" "$(db /tmp/p_writew)" "$OUT/pmc_split_gemm_w16.json" 2 batch_gemm > /dev/null
-run /tmp/p_fullw --kernel-trace --stats -d /tmp/p_fullw -- python bench.py --steps 5 --warmup 2 --llm-values fp16 --no-cpu-baseline --no-parity --no-mixed --no-exact --no-frozen16
+run /tmp/p_fullw --kernel-trace --stats -d /tmp/p_fullw -- python bench.py --full --steps 5 --warmup 2 --llm-values fp16 --no-cpu-baseline --no-parity --no-mixed --no-exact --no-frozen16
 python tools/prof_summary.py "$(db /tmp/p_fullw)" "$OUT/${TAG}_bench_w16_kernel_stats.csv" > /dev/null
 grep '^{"metric"' /tmp/p_fullw.log | tail -1 > "$OUT/${TAG}_bench_w16_line.json"
 # 4. BASELINE C2 (bf16 relation query) per step, and the 16-bit cross-attention counters at C2

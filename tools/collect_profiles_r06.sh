@@ -10,13 +10,13 @@ export TMPDIR=/tmp
 QUIET="--no-cpu-baseline --no-parity --no-mixed --no-exact --no-frozen16 --no-batched --no-c4"
 db() { ls "$1"/*/*_results.db 2>/dev/null | head -1; }
 run() { local d=$1; shift; rm -rf "$d"; rocprofv3 "$@" > "$d.log" 2>&1; }
-# 1. the default command, as the driver runs it
-python bench.py --steps 20 --warmup 5 2> "$OUT/bench_default.err" | grep '^{"metric"' | tail -1 > "$OUT/${TAG}_bench_default_line.json"
+# 1. the whole line (--full), every figure it can carry
+python bench.py --full --steps 20 --warmup 5 2> "$OUT/bench_default.err" | grep '^{"metric"' | tail -1 > "$OUT/${TAG}_bench_default_line.json"
 # 2. per-kernel durations of the headline path (kernel trace + stats; no counters in this pass), both weight kinds
-run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --steps 5 --warmup 2 $QUIET
+run /tmp/p_full --kernel-trace --stats -d /tmp/p_full -- python bench.py --full --steps 5 --warmup 2 $QUIET
 python tools/prof_summary.py "$(db /tmp/p_full)" "$OUT/${TAG}_bench_full_kernel_stats.csv" > /dev/null
 grep '^{"metric"' /tmp/p_full.log | tail -1 > "$OUT/${TAG}_bench_full_line.json"
-run /tmp/p_fullw --kernel-trace --stats -d /tmp/p_fullw -- python bench.py --steps 5 --warmup 2 --llm-values fp16 $QUIET
+run /tmp/p_fullw --kernel-trace --stats -d /tmp/p_fullw -- python bench.py --full --steps 5 --warmup 2 --llm-values fp16 $QUIET
 python tools/prof_summary.py "$(db /tmp/p_fullw)" "$OUT/${TAG}_bench_w16_kernel_stats.csv" > /dev/null
 grep '^{"metric"' /tmp/p_fullw.log | tail -1 > "$OUT/${TAG}_bench_w16_line.json"
 # 3. what ONE image costs per kernel (difference of two traces), both weight kinds
