@@ -444,10 +444,11 @@ __global__ void exist_head_kernel(const T* __restrict__ x, const float* __restri
 
 extern "C" int psg_exist_head(psg_ctx* ctx, const void* x, const float* w, const float* b, int P, int nq, int hidden,
                               float* logit, float* prob, int dtype, void* stream) {
-  PSG_REQUIRE(ctx && x && w && b && logit, PSG_ERR_INVALID, "psg_exist_head: NULL argument");
   PSG_REQUIRE(hidden % 4 == 0 && P >= 0 && nq > 0, PSG_ERR_INVALID, "psg_exist_head: P=%d nq=%d hidden=%d", P, nq,
               hidden);
-  if (P == 0) return PSG_OK;
+  PSG_REQUIRE(ctx && w && b, PSG_ERR_INVALID, "psg_exist_head: NULL argument");
+  if (P == 0) return PSG_OK;                        // no pairs: x / logit / prob may be empty (NULL) tensors
+  PSG_REQUIRE(x && logit, PSG_ERR_INVALID, "psg_exist_head: NULL argument");
   PSG_DISPATCH_DTYPE(dtype, "psg_exist_head",
                      (exist_head_kernel<T><<<(P + 3) / 4, 256, 0, (hipStream_t)stream>>>((const T*)x, w, b, P, nq,
                                                                                        hidden, logit, prob)));
