@@ -66,8 +66,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   501  round 5 (psg_batch_gemm*, psg_qformer_cross_attn_indexed, psg_skinny_gemm_w16, psg_split_f16x2, psg_split_gemm_w16,
  *        psg_rmsnorm_split2, psg_rmsnorm_split / psg_rope_kvwrite_scaled /
  *        psg_silu_mul_split added)
- *   600  round 6 (psg_dense_gemm_split added; psg_split_f16x3 order 2) */
-#define PSG_ABI_VERSION 600
+ *   600  round 6 (psg_dense_gemm_split added; psg_split_f16x3 order 2)
+ *   601  psg_multiclass_head, psg_topk_large(_workspace), psg_train_mlcce_fwd / _bwd added */
+#define PSG_ABI_VERSION 601
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -200,6 +201,19 @@ int psg_exist_head(psg_ctx*, const void* x, const float* w, const float* b, int 
 
 /* ---- K9: selector, V4:235-237: indices of the k largest scores, descending, ties -> lower index. */
 int psg_topk(psg_ctx*, const float* score, int n, int k, int32_t* out_idx, float* out_val, void* stream);
+
+/* ---- K8b: multiclass relation head, V4:93-95, 213-214: logit[p][r] = W[r] . x[p*nq] + b[r] (row stride nq*hidden; fp32,
+ * bf16 or fp16 input, fp32 accumulation), prob = sigmoid(logit) except prob[p][:] = 0 for a diagonal pair (g = i*N + i
+ * with g = pair_index[p], or p itself when pair_index is NULL; N = 0: no diagonal).  W [R][hidden] fp32, b [R];
+ * 1 <= R <= 128 (PSG_ERR_UNSUPPORTED above), hidden a multiple of 64.  prob may be NULL. */
+int psg_multiclass_head(psg_ctx*, const void* x, const float* w, const float* b, int P, int nq, int hidden, int R,
+                        const int32_t* pair_index, int N, float* logit, float* prob, int dtype, void* stream);
+
+/* ---- K9b: psg_topk for large n (k <= 256): the same order and output, several workgroups.  The caller passes a device
+ * workspace of at least psg_topk_large_workspace() bytes; no allocation, no host synchronisation. */
+int psg_topk_large_workspace(psg_ctx*, int n, int k, int64_t* bytes);
+int psg_topk_large(psg_ctx*, const float* score, int n, int k, void* workspace, int64_t ws_bytes, int32_t* out_idx,
+                   float* out_val, void* stream);
 
 /* ---- row gather (pair_feature[selected], embed_tokens[ids]; V4:294-297): dst[r] = src[idx[r]];
  * idx < 0 writes zeros.  src_dtype/dst_dtype allow fp32 tables -> bf16 activations. */
@@ -541,6 +555,12 @@ int psg_train_ce_bwd(psg_ctx*, const float* logits, int64_t rows, int vocab, con
                      float* dlogits, void* stream);
 int psg_train_bce_bwd(psg_ctx*, const float* logit, const float* label, int n, float weight, const float* dloss,
                       float* dlogit, void* stream);
+/* multilabel categorical cross entropy of the multiclass head (V4:484-495), rows of R fp32 logits with 0/1 fp32 labels:
+ * loss[row] = lse([z - 9999 y, 0]) + lse([z - 9999 (1 - y), 0]), z = (1 - 2y) x; the backward writes
+ * dlogits = dloss[row] (1 - 2y) (softmax_neg + softmax_pos) over the R real classes. */
+int psg_train_mlcce_fwd(psg_ctx*, const float* logits, const float* labels, int rows, int R, float* loss, void* stream);
+int psg_train_mlcce_bwd(psg_ctx*, const float* logits, const float* labels, int rows, int R, const float* dloss,
+                        float* dlogits, void* stream);
 
 /* ---- 8f: bilinear relation scorer of the closed-set heads (relation_transformer_head_v2.py:204-209):
  * pred[b][r][s][o] = sum_c sub[b][s][r*C + c] * obj[b][o][r*C + c], i.e. einsum('nrsc,nroc->nrso') on the

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpsg_hip.so")
 
-PSG_ABI_VERSION = 600            # include/psg_hip.h; checked against psg_version() of the loaded library
+PSG_ABI_VERSION = 601            # include/psg_hip.h; checked against psg_version() of the loaded library
 PSG_F32, PSG_BF16, PSG_F16 = 0, 1, 2
 PSG_EMPTY_UNIFORM, PSG_EMPTY_UNMASKED = 0, 1
 PSG_XATTN_MFMA, PSG_XATTN_SIMPLE, PSG_XATTN_MFMA_V1 = 0, 1, 2
@@ -60,6 +60,9 @@ SIGNATURES = {
     "psg_qformer_cross_attn": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "psg_exist_head": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp],
     "psg_topk": [_vp, _vp, _i, _i, _vp, _vp, _vp],
+    "psg_multiclass_head": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp],
+    "psg_topk_large_workspace": [_vp, _i, _i, C.POINTER(_i64)],
+    "psg_topk_large": [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp],
     "psg_gather_rows": [_vp, _vp, _i, _vp, _i64, _i, _i64, _vp, _i, _i64, _vp],
     "psg_gather_pair_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "psg_rmsnorm": [_vp, _vp, _vp, _i, _vp, _f, _i64, _i, _vp, _i, _i, _vp],
@@ -116,6 +119,8 @@ SIGNATURES = {
     "psg_train_rope": [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _f, _vp, _vp],
     "psg_train_ce_bwd": [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp],
     "psg_train_bce_bwd": [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
+    "psg_train_mlcce_fwd": [_vp, _vp, _vp, _i, _i, _vp, _vp],
+    "psg_train_mlcce_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "psg_greedy_step": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
 }
 

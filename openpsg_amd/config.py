@@ -62,9 +62,16 @@ class PSGConfig:
     # 'uniform': an empty pair mask gives a uniform softmax over all L patches (additive finfo.min,
     # legacy/eager semantics).  'unmasked': additive -10000 variant.
     empty_row_policy: str = "uniform"
+    # relation classifier(s) on the cls row (V4:31, 91-95): 'binary' (pair existence, the default),
+    # 'binary+multiclass' (+ one sigmoid score per relation class) or 'multiclass' (the class scores only)
+    rel_cls_type: str = "binary"
+    num_relation_classes: int = 56     # len(relation_classes) (V4:43)
 
     def to_dict(self):
         return asdict(self)
+
+
+REL_CLS_TYPES = ("binary", "binary+multiclass", "multiclass")
 
 
 def tiny_llm(hidden=256, layers=2, inter=512, vocab=512) -> LlamaConfig:

@@ -343,6 +343,159 @@ extern "C" int psg_topk(psg_ctx* ctx, const float* score, int n, int k, int32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
+// K9b: top-k of a LARGE score vector (the multiclass decode: N^2 x R scores, up to 12 288 x 128), same order and output
+// as psg_topk (topk_key: larger score first, ties -> lower index, NaN last, -0 == +0; -1 / -inf tail when n < k).
+// Two launches, no host round trip: workgroup g radix-selects the k best keys of its segment of TKL_SEG scores (held in
+// LDS) and writes them, unordered, to workspace row g (0 = empty slot, below every real key); one workgroup then
+// radix-selects the k best of the G x k candidates and ranks those k among themselves.
+// Radix select: the keys are unique, so walking the 64-bit key 8 bits at a time from the top - histogram of the digit
+// over the keys that share the prefix found so far, pick the bin where the count from the top reaches the number still
+// wanted - ends with a prefix t such that exactly min(k, keys) keys are >= t.  Per-wave histograms: scores of one
+// image share their top bits, and one histogram would put every LDS atomic of the workgroup on the same address.
+// ---------------------------------------------------------------------------------------------
+constexpr int TKL_SEG = 4096, TKL_KMAX = 256;
+struct TklShared {
+  int hist[16][256];
+  int cnt[256];
+  int wtot[4];
+  unsigned long long prefix;
+  int rem, done, n_sel;
+};
+
+// src: m keys (generic pointer: LDS or global).  Returns the threshold (every thread).
+__device__ unsigned long long tkl_threshold(const unsigned long long* src, int m, int k, TklShared& sh) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (tid == 0) {
+    sh.prefix = 0ull;
+    sh.rem = k;
+    sh.done = 0;
+  }
+  unsigned long long mask = 0ull;
+  for (int shift = 56; shift >= 0; shift -= 8) {
+    for (int i = tid; i < 16 * 256; i += 1024) (&sh.hist[0][0])[i] = 0;
+    __syncthreads();
+    const unsigned long long prefix = sh.prefix;                 // (written again only after the next barrier)
+    const int rem = sh.rem;
+    for (int i = tid; i < m; i += 1024) {
+      const unsigned long long key = src[i];
+      if (key != 0ull && (key & mask) == prefix) atomicAdd(&sh.hist[wid][(int)((key >> shift) & 255ull)], 1);
+    }
+    __syncthreads();
+    int c = 0, s = 0;
+    if (tid < 256) {
+      for (int w = 0; w < 16; ++w) c += sh.hist[w][tid];
+      sh.cnt[tid] = c;
+      s = c;                                                    // suffix sum over the bins of this wave
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_down(s, o, 64);
+        if (lane + o < 64) s += t;
+      }
+      if (lane == 0) sh.wtot[wid] = s;
+    }
+    __syncthreads();
+    if (tid < 256) {
+      for (int w = wid + 1; w < 4; ++w) s += sh.wtot[w];       // keys in bins >= tid
+      const int total = sh.wtot[0] + sh.wtot[1] + sh.wtot[2] + sh.wtot[3];
+      if (shift == 56 && total <= k) {                          // no more keys than wanted: all of them
+        if (tid == 0) {
+          sh.prefix = 1ull;
+          sh.done = 1;
+        }
+      } else if (s >= rem && s - c < rem) {                     // the bin where the count from the top reaches rem
+        const int r2 = rem - (s - c);
+        sh.prefix = prefix | ((unsigned long long)tid << shift);
+        sh.rem = r2;
+        sh.done = c == r2;
+      }
+    }
+    __syncthreads();
+    if (sh.done) break;
+    mask |= 255ull << shift;
+  }
+  return sh.prefix;
+}
+
+__global__ void __launch_bounds__(1024) topk_large_seg_kernel(const float* __restrict__ score, int n, int k,
+                                                              unsigned long long* __restrict__ ws) {
+  __shared__ unsigned long long keys[TKL_SEG];
+  __shared__ TklShared sh;
+  const int tid = threadIdx.x;
+  const int s0 = blockIdx.x * TKL_SEG, m = min(TKL_SEG, n - s0);
+  for (int i = tid; i < m; i += 1024) keys[i] = topk_key(score[s0 + i], s0 + i);
+  if (tid == 0) sh.n_sel = 0;
+  __syncthreads();
+  const unsigned long long t = tkl_threshold(keys, m, k, sh);
+  unsigned long long* row = ws + (int64_t)blockIdx.x * k;
+  for (int i = tid; i < m; i += 1024) {
+    const unsigned long long key = keys[i];
+    if (key >= t) {                                             // exactly min(k, m) keys pass
+      const int slot = atomicAdd(&sh.n_sel, 1);
+      if (slot < k) row[slot] = key;
+    }
+  }
+  __syncthreads();
+  for (int j = sh.n_sel + tid; j < k; j += 1024) row[j] = 0ull;
+}
+
+__global__ void __launch_bounds__(1024) topk_large_merge_kernel(const float* __restrict__ score, int m, int k,
+                                                                const unsigned long long* __restrict__ ws,
+                                                                int32_t* __restrict__ out_idx, float* __restrict__ out_val) {
+  __shared__ unsigned long long sel[TKL_KMAX];
+  __shared__ TklShared sh;
+  const int tid = threadIdx.x;
+  if (tid == 0) sh.n_sel = 0;
+  __syncthreads();
+  const unsigned long long t = tkl_threshold(ws, m, k, sh);
+  for (int i = tid; i < m; i += 1024) {
+    const unsigned long long key = ws[i];
+    if (key != 0ull && key >= t) {
+      const int slot = atomicAdd(&sh.n_sel, 1);
+      if (slot < k) sel[slot] = key;
+    }
+  }
+  __syncthreads();
+  const int c = min(sh.n_sel, k);
+  if (tid < c) {
+    const unsigned long long mine = sel[tid];
+    int r = 0;
+    for (int j = 0; j < c; ++j) r += sel[j] > mine ? 1 : 0;
+    const int i = (int)(0xffffffffu - (uint32_t)mine);
+    out_idx[r] = i;
+    if (out_val) {
+      const float v = score[i];
+      out_val[r] = v != v ? -INFINITY : v;
+    }
+  } else if (tid < k) {                                         // fewer than k elements: the tail is "none"
+    out_idx[tid] = -1;
+    if (out_val) out_val[tid] = -INFINITY;
+  }
+}
+
+extern "C" int psg_topk_large_workspace(psg_ctx* ctx, int n, int k, int64_t* bytes) {
+  PSG_REQUIRE(ctx && bytes, PSG_ERR_INVALID, "psg_topk_large_workspace: NULL argument");
+  PSG_REQUIRE(n > 0 && k > 0 && k <= TKL_KMAX, PSG_ERR_INVALID, "psg_topk_large_workspace: n=%d k=%d (k <= %d)", n, k,
+              TKL_KMAX);
+  *bytes = (int64_t)((n + TKL_SEG - 1) / TKL_SEG) * k * (int64_t)sizeof(unsigned long long);
+  return PSG_OK;
+}
+
+extern "C" int psg_topk_large(psg_ctx* ctx, const float* score, int n, int k, void* workspace, int64_t ws_bytes,
+                              int32_t* out_idx, float* out_val, void* stream) {
+  PSG_REQUIRE(ctx && score && workspace && out_idx, PSG_ERR_INVALID, "psg_topk_large: NULL argument");
+  PSG_REQUIRE(n > 0 && k > 0 && k <= TKL_KMAX, PSG_ERR_INVALID, "psg_topk_large: n=%d k=%d (k <= %d)", n, k, TKL_KMAX);
+  const int G = (n + TKL_SEG - 1) / TKL_SEG;
+  PSG_REQUIRE(ws_bytes >= (int64_t)G * k * (int64_t)sizeof(unsigned long long), PSG_ERR_INVALID,
+              "psg_topk_large: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+              (long long)G * k * (long long)sizeof(unsigned long long));
+  hipStream_t st = (hipStream_t)stream;
+  topk_large_seg_kernel<<<G, 1024, 0, st>>>(score, n, k, (unsigned long long*)workspace);
+  topk_large_merge_kernel<<<1, 1024, 0, st>>>(score, G * k, k, (const unsigned long long*)workspace, out_idx, out_val);
+  PSG_CHECK_LAUNCH("psg_topk_large");
+  return PSG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Rows of the SELECTED pairs for the second phase of the last Q-Former layer (V4:215, 235-237: pair_feature of the chosen
 // pairs only): one launch instead of the index arithmetic (arange / mul / add / where / clamp / cat / index_select: ~20
 // library launches of 5 us) that depended on the selection.  sel[s] is a global pair id; a pair this chunk owns

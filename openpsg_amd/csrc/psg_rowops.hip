@@ -456,6 +456,110 @@ extern "C" int psg_exist_head(psg_ctx* ctx, const void* x, const float* w, const
   return PSG_OK;
 }
 
+// ---- K8b multiclass relation head (V4:93-95, 213-214): logits = W x[p*nq] + b over R <= 128 classes ------------------
+// A workgroup owns MC_TP pairs and walks the hidden dimension in MC_KC-column chunks: the chunk of every pair's cls row
+// (read once from HBM, converted to fp32) and the matching W columns (L2-resident, 172 KB at R = 56 - more than LDS,
+// hence the chunks) are staged in LDS, then thread (ty, tx) accumulates pairs 4 ty .. 4 ty + 3 x classes tx + 16 c in
+// fp32.  CG = ceil(R / 16) class groups are computed; the padded classes of the last group read zero weights.
+// The probability of a diagonal pair (i == j of p = i N + j) is written as 0 (the intent of V4:239-241); its logit is not
+// touched.  A separate launch from exist_head_kernel: the existence logits stay exactly what they were.
+constexpr int MC_TP = 64, MC_KC = 64, MC_RMAX = 128;
+template <typename T, int CG>
+__global__ void __launch_bounds__(256) multiclass_head_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ b, int P, int nq, int hidden,
+                                                              int R, const int32_t* __restrict__ pair_index, int N,
+                                                              float* __restrict__ logit, float* __restrict__ prob) {
+  __shared__ float xs[MC_KC][MC_TP + 4];            // [column][pair]: 4 consecutive pairs = one float4
+  __shared__ float ws[MC_KC][CG * 16 + 1];          // [column][class]
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int p0 = blockIdx.x * MC_TP;
+  float acc[4][CG];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < CG; ++c) acc[a][c] = 0.f;
+  for (int k0 = 0; k0 < hidden; k0 += MC_KC) {
+    // x chunk: MC_TP pairs x MC_KC columns, 4 columns per load (16 loads per row chunk, 4 per thread)
+    for (int e = tid; e < MC_TP * (MC_KC / 4); e += 256) {
+      const int pp = e / (MC_KC / 4), cc = (e % (MC_KC / 4)) * 4;
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (p0 + pp < P) Act<T>::ld4(x, (int64_t)(p0 + pp) * nq * hidden + k0 + cc, v);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) xs[cc + u][pp] = v[u];
+    }
+    for (int e = tid; e < CG * 16 * (MC_KC / 4); e += 256) {
+      const int r = e / (MC_KC / 4), cc = (e % (MC_KC / 4)) * 4;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (r < R) v = *reinterpret_cast<const float4*>(w + (int64_t)r * hidden + k0 + cc);
+      ws[cc][r] = v.x;
+      ws[cc + 1][r] = v.y;
+      ws[cc + 2][r] = v.z;
+      ws[cc + 3][r] = v.w;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int kk = 0; kk < MC_KC; ++kk) {
+      const float4 xv = *reinterpret_cast<const float4*>(&xs[kk][ty * 4]);
+#pragma unroll
+      for (int c = 0; c < CG; ++c) {
+        const float wv = ws[kk][tx + 16 * c];
+        acc[0][c] = fmaf(xv.x, wv, acc[0][c]);
+        acc[1][c] = fmaf(xv.y, wv, acc[1][c]);
+        acc[2][c] = fmaf(xv.z, wv, acc[2][c]);
+        acc[3][c] = fmaf(xv.w, wv, acc[3][c]);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int p = p0 + ty * 4 + a;
+    if (p >= P) continue;
+    const int g = pair_index ? pair_index[p] : p;
+    const bool diag = N > 0 && g / N == g % N;
+#pragma unroll
+    for (int c = 0; c < CG; ++c) {
+      const int r = tx + 16 * c;
+      if (r >= R) continue;
+      const float l = acc[a][c] + b[r];
+      logit[(int64_t)p * R + r] = l;
+      if (prob) prob[(int64_t)p * R + r] = diag ? 0.f : 1.0f / (1.0f + expf(-l));
+    }
+  }
+}
+
+extern "C" int psg_multiclass_head(psg_ctx* ctx, const void* x, const float* w, const float* b, int P, int nq,
+                                   int hidden, int R, const int32_t* pair_index, int N, float* logit, float* prob,
+                                   int dtype, void* stream) {
+  PSG_REQUIRE(ctx && w && b, PSG_ERR_INVALID, "psg_multiclass_head: NULL argument");
+  PSG_REQUIRE(P >= 0 && nq > 0 && hidden > 0 && hidden % MC_KC == 0 && N >= 0, PSG_ERR_INVALID,
+              "psg_multiclass_head: P=%d nq=%d hidden=%d N=%d (hidden must be a multiple of %d)", P, nq, hidden, N, MC_KC);
+  PSG_REQUIRE(R >= 1 && R <= MC_RMAX, PSG_ERR_UNSUPPORTED, "psg_multiclass_head: R=%d classes (1..%d supported)", R,
+              MC_RMAX);
+  if (P == 0) return PSG_OK;
+  PSG_REQUIRE(x && logit, PSG_ERR_INVALID, "psg_multiclass_head: NULL argument");
+  const unsigned grid = (unsigned)((P + MC_TP - 1) / MC_TP);
+  const int cg = (R + 15) / 16;
+  hipStream_t st = (hipStream_t)stream;
+#define MC_LAUNCH(CGV)                                                                                               \
+  PSG_DISPATCH_DTYPE(dtype, "psg_multiclass_head",                                                                   \
+                     (multiclass_head_kernel<T, CGV><<<grid, 256, 0, st>>>((const T*)x, w, b, P, nq, hidden, R,        \
+                                                                         pair_index, N, logit, prob)))
+  switch (cg) {
+    case 1: MC_LAUNCH(1); break;
+    case 2: MC_LAUNCH(2); break;
+    case 3: MC_LAUNCH(3); break;
+    case 4: MC_LAUNCH(4); break;
+    case 5: MC_LAUNCH(5); break;
+    case 6: MC_LAUNCH(6); break;
+    case 7: MC_LAUNCH(7); break;
+    default: MC_LAUNCH(8); break;
+  }
+#undef MC_LAUNCH
+  PSG_CHECK_LAUNCH("psg_multiclass_head");
+  return PSG_OK;
+}
+
 // ---- K12 RMSNorm (+ residual add) -------------------------------------------------------------
 // One 256-thread workgroup per row (decode has only K ~ 20 rows of 4096: a single wave walking a
 // row serialises ~16 dependent HBM round trips).  Thread t owns the 4-element chunks t, t+256, ...;

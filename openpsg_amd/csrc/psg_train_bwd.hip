@@ -19,6 +19,7 @@
 //   psg_train_silu_mul_fwd / _bwd      SwiGLU gate (HF-LL:163-177)
 //   psg_train_rope                     half-split rotary (HF-LL:130-160); sign = -1 is its adjoint
 //   psg_train_ce_bwd / psg_train_bce_bwd   gradients of psg_cross_entropy_rows / psg_bce_with_logits
+//   psg_train_mlcce_fwd / _bwd         multilabel categorical cross entropy of the multiclass head (V4:484-495)
 #include "psg_common.h"
 
 #define TR_FMIN (-3.4028234663852886e38f)
@@ -448,5 +449,78 @@ extern "C" int psg_train_bce_bwd(psg_ctx* ctx, const float* logit, const float* 
   PSG_REQUIRE(ctx && logit && label && dloss && dlogit && n > 0, PSG_ERR_INVALID, "psg_train_bce_bwd: bad argument");
   tr_bce_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(logit, label, n, weight, dloss, dlogit);
   PSG_CHECK_LAUNCH("psg_train_bce_bwd");
+  return PSG_OK;
+}
+
+// ---- multilabel categorical cross entropy (V4:484-495, the multiclass head's row loss) ------------------------------
+// Per row of R logits x with 0/1 labels y, exactly the reference's arithmetic in fp32:
+//   z = (1 - 2y) x,  neg = z - 9999 y,  pos = z - 9999 (1 - y),  loss = lse([neg, 0]) + lse([pos, 0])
+// (the concatenated zero is the extra class of both log-sum-exps).  Backward over the R real classes only:
+//   dx = dloss (1 - 2y) (softmax([neg, 0])[:R] + softmax([pos, 0])[:R]).
+// One wave per row; the self-weighting of the rows (loss / loss.max(), V4:473-476) is left to autograd on the caller side.
+__device__ __forceinline__ void tr_mlcce_stats(const float* __restrict__ x, const float* __restrict__ y, int R, int lane,
+                                               float& mn, float& ln, float& mp, float& lp) {
+  float a = 0.f, b = 0.f;                              // the zero column takes part in both maxima
+  for (int r = lane; r < R; r += 64) {
+    const float yr = y[r], z = (1.0f - 2.0f * yr) * x[r];
+    a = fmaxf(a, z - yr * 9999.0f);
+    b = fmaxf(b, z - (1.0f - yr) * 9999.0f);
+  }
+  mn = wave_max(a);
+  mp = wave_max(b);
+  float sa = 0.f, sb = 0.f;
+  for (int r = lane; r < R; r += 64) {
+    const float yr = y[r], z = (1.0f - 2.0f * yr) * x[r];
+    sa += expf(z - yr * 9999.0f - mn);
+    sb += expf(z - (1.0f - yr) * 9999.0f - mp);
+  }
+  ln = wave_sum(sa) + expf(-mn);                       // sum of exp over [neg, 0] relative to its max
+  lp = wave_sum(sb) + expf(-mp);
+}
+
+__global__ void __launch_bounds__(256) tr_mlcce_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
+                                                           int rows, int R, float* __restrict__ loss) {
+  const int row = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  float mn, ln, mp, lp;
+  tr_mlcce_stats(logits + (int64_t)row * R, labels + (int64_t)row * R, R, lane, mn, ln, mp, lp);
+  if (lane == 0) loss[row] = (mn + logf(ln)) + (mp + logf(lp));
+}
+
+__global__ void __launch_bounds__(256) tr_mlcce_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
+                                                           int rows, int R, const float* __restrict__ dloss,
+                                                           float* __restrict__ dlogits) {
+  const int row = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* x = logits + (int64_t)row * R;
+  const float* y = labels + (int64_t)row * R;
+  float mn, ln, mp, lp;
+  tr_mlcce_stats(x, y, R, lane, mn, ln, mp, lp);
+  const float g = dloss[row], in = 1.0f / ln, ip = 1.0f / lp;
+  for (int r = lane; r < R; r += 64) {
+    const float yr = y[r], s = 1.0f - 2.0f * yr, z = s * x[r];
+    const float pn = expf(z - yr * 9999.0f - mn) * in, pp = expf(z - (1.0f - yr) * 9999.0f - mp) * ip;
+    dlogits[(int64_t)row * R + r] = g * s * (pn + pp);
+  }
+}
+
+extern "C" int psg_train_mlcce_fwd(psg_ctx* ctx, const float* logits, const float* labels, int rows, int R, float* loss,
+                                   void* stream) {
+  PSG_REQUIRE(ctx && rows >= 0 && R > 0, PSG_ERR_INVALID, "psg_train_mlcce_fwd: rows=%d R=%d", rows, R);
+  if (rows == 0) return PSG_OK;
+  PSG_REQUIRE(logits && labels && loss, PSG_ERR_INVALID, "psg_train_mlcce_fwd: NULL argument");
+  tr_mlcce_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(logits, labels, rows, R, loss);
+  PSG_CHECK_LAUNCH("psg_train_mlcce_fwd");
+  return PSG_OK;
+}
+
+extern "C" int psg_train_mlcce_bwd(psg_ctx* ctx, const float* logits, const float* labels, int rows, int R,
+                                   const float* dloss, float* dlogits, void* stream) {
+  PSG_REQUIRE(ctx && rows >= 0 && R > 0, PSG_ERR_INVALID, "psg_train_mlcce_bwd: rows=%d R=%d", rows, R);
+  if (rows == 0) return PSG_OK;
+  PSG_REQUIRE(logits && labels && dloss && dlogits, PSG_ERR_INVALID, "psg_train_mlcce_bwd: NULL argument");
+  tr_mlcce_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(logits, labels, rows, R, dloss,
+                                                                                   dlogits);
+  PSG_CHECK_LAUNCH("psg_train_mlcce_bwd");
   return PSG_OK;
 }

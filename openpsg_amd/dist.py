@@ -34,6 +34,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ._lib import PsgHipError
+
 
 def shard_range(num_pairs: int, world: int, rank: int):
     """Contiguous pair range of `rank` and the (uniform, padded) shard length."""
@@ -80,6 +82,10 @@ class HipBackend:
 
     def __init__(self, head):
         from .categories import INSTANCE_OFFSET, object_categories
+        if getattr(head, "rel_cls_type", "binary") != "binary":
+            # the multiclass scores of all pairs would need an all-gather of [pairs, R] and a global top-k merge
+            raise PsgHipError(f"pair-sharded pipelines run rel_cls_type='binary' heads only, not {head.rel_cls_type!r} "
+                              "(the multiclass head runs on one GPU: head.forward / submit / forward_batch)")
         self.head = head
         # the same object truncation (V4:136) and selector options as head.forward, so sharded == single GPU
         self._ids = lambda scene: [int(i) for i in scene["object_id_list"][:head.max_object_num]]

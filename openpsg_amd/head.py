@@ -12,6 +12,9 @@ Differences that are deliberate and documented:
     implements the intended contract: rel_pred = LLM triples, rel_score = 1 each (SURVEY 0.3);
   * the training branch computes the reference's two losses (`forward_train`: values through the inference kernels;
     `forward_train_grad`: fp32, with the gradient graph - openpsg_amd/train_graph.py; SURVEY 8f rank 3);
+  * rel_cls_type 'binary+multiclass' / 'multiclass' (V4:31, 91-95): the multiclass triples follow the LLM triples with
+    the diagonal zeroed and the flat index decoded as p*R + r (V4:239-250 as intended), and 'multiclass' alone runs no
+    pair selector or decode (DESIGN 9);
   * all arithmetic runs in libpsg_hip.so / hipBLASLt on the GPU; there is no CPU path.
 """
 from __future__ import annotations
@@ -26,7 +29,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import PsgHipError
 from .categories import INSTANCE_OFFSET, object_categories, relation_categories
-from .config import LlamaConfig, PSGConfig, QFormerConfig
+from .config import REL_CLS_TYPES, LlamaConfig, PSGConfig, QFormerConfig
 from .llm import LlamaDecodeEngine
 from .qformer import RelationQueryEngine
 from .registry import HEADS
@@ -59,6 +62,8 @@ class _Pending:
         h, out = self.head, self.out
         with torch.cuda.stream(self.stream):
             sel = self.rq["selected"]
+            if out.get("tokens") is None and "_finish" not in out:         # 'multiclass' alone: no decode
+                out["tokens_host"] = out["selected_host"] = None
             if "_finish" in out:                                           # natural EOS: the chunks behind the first
                 out.pop("_finish")()
                 # the deferred chunks were enqueued only now: `_decode_done` of this image (recorded at submit, behind the
@@ -66,13 +71,18 @@ class _Pending:
                 if h._decode_done_slot == self.slot:
                     h._decode_done = torch.cuda.Event()
                     h._decode_done.record(self.stream)
-            out["tokens_host"] = out["tokens"].cpu().numpy()               # waits for this stream's work only
-            out["selected_host"] = sel.cpu().numpy()
+            if out["tokens"] is not None:
+                out["tokens_host"] = out["tokens"].cpu().numpy()           # waits for this stream's work only
+                out["selected_host"] = sel.cpu().numpy()
+            if h.has_multiclass:
+                out["mc_host"] = self.rq["mc_topk"].cpu().numpy()
         self.rq.update(out)
         h.last = self.rq
-        rel_pred, rel_score = h.parse(out["tokens_host"], out["selected_host"], self.N)
+        rel_pred, rel_score = ([], []) if out["tokens_host"] is None else h.parse(out["tokens_host"], out["selected_host"],
+                                                                                 self.N)
+        mc_pred, mc_score = h.parse_multiclass(out.get("mc_host"), self.N)
         self.rq = self.out = self.inputs = None
-        self._result = dict(rel_pred=rel_pred, rel_score=rel_score)
+        self._result = dict(rel_pred=rel_pred + mc_pred, rel_score=rel_score + mc_score)
         return self._result
 
     @property
@@ -83,16 +93,18 @@ class _Pending:
 class _PendingBatch:
     """A batch submitted with `head.submit_batch`; `result()` is the only host wait (on the batch's stream)."""
 
-    def __init__(self, head, stream, items, results, tokens):
+    def __init__(self, head, stream, items, results, tokens, mcs=None):
         self.head, self.stream, self.items, self.results, self.tokens = head, stream, items, results, tokens
+        self.mcs = mcs or {}                                    # image -> (multiclass top-k [2, k] on the device, N)
 
     def result(self):
         h, results = self.head, self.results
-        if not self.items:
+        if not self.items and not self.mcs:
             return results
         with torch.cuda.stream(self.stream):
-            tokens_host = self.tokens.cpu().numpy()
+            tokens_host = self.tokens.cpu().numpy() if self.items else None
             sels = [sel.cpu().numpy() for _, _, sel, _, _ in self.items]
+            mc_host = {i: t.cpu().numpy() for i, (t, _) in self.mcs.items()}
         k0 = 0
         h.last_batch = []
         for (i, N, _, X, _), sel_host in zip(self.items, sels):
@@ -101,7 +113,12 @@ class _PendingBatch:
             results[i] = dict(rel_pred=rel_pred, rel_score=rel_score)
             h.last_batch.append(dict(tokens_host=tokens_host[k0:k1], selected_host=sel_host))
             k0 = k1
+        for i, (_, N) in self.mcs.items():                      # V4:355-356: LLM triples, then the multiclass ones
+            mc_pred, mc_score = h.parse_multiclass(mc_host[i], N)
+            r = results[i] if results[i] is not None else dict(rel_pred=[], rel_score=[])
+            results[i] = dict(rel_pred=r["rel_pred"] + mc_pred, rel_score=r["rel_score"] + mc_score)
         self.items = self.tokens = None
+        self.mcs = {}
         return results
 
 
@@ -202,14 +219,24 @@ class RelationTransformerHeadV4(nn.Module):
                                                # config.json (unless llm_config is given) and its weights, as the reference's
                                                # from_pretrained does at V4:99-103 (llm_truncate_num layers only).  A hub name
                                                # cannot be resolved here (no network): load_llm_weights() then
+                 num_multiclass_triples=100,   # multiclass triples per image (V4:249: k=100), at most 256
                  train_losses_without_grad=False,   # forward() in training mode returns the two losses WITHOUT a graph
                                                # (forward_train); off: it raises, so that an mmdet-style loop cannot sum
                                                # them and silently train nothing in this head
                  **kwargs):
         super().__init__()
-        if rel_cls_type != 'binary':
-            raise NotImplementedError("only rel_cls_type='binary' (the reference default, V4:31) is built; the "
-                                      "'multiclass' branch of the reference is broken as committed (SURVEY 0.3)")
+        if rel_cls_type not in REL_CLS_TYPES:
+            raise ValueError(f"rel_cls_type must be one of {REL_CLS_TYPES} (V4:31, 91-95), got {rel_cls_type!r}")
+        # 'binary': existence head -> top-20 pairs -> LLM decode (V4:206-209, 235-237).  'multiclass' in the type: one
+        # sigmoid score per (pair, relation class) from multiclass_rel_cls_pred, the diagonal zeroed, the top
+        # `num_multiclass_triples` (pair, class) scores returned behind the LLM triples (V4:238-257, 355-356)
+        self.has_binary = "binary" in rel_cls_type
+        self.has_multiclass = "multiclass" in rel_cls_type
+        self.num_multiclass_triples = int(num_multiclass_triples)
+        if not 1 <= self.num_multiclass_triples <= 256:
+            raise PsgHipError(f"num_multiclass_triples must be in 1..256, got {num_multiclass_triples}")
+        if self.has_multiclass and not 1 <= len(relation_classes) <= 128:
+            raise PsgHipError(f"the multiclass head runs up to 128 relation classes, got {len(relation_classes)}")
         self.qformer_instruction = qformer_instruction
         self.sampled_qformer_batch_size = int(sampled_qformer_batch_size)
         self.qformer_neg_over_pos = int(qformer_neg_over_pos)
@@ -269,7 +296,8 @@ class RelationTransformerHeadV4(nn.Module):
             qformer=QFormerConfig(hidden=qformer_feature_size, layers=qformer_layer_num, vocab=qformer_vocab_size,
                                   enc_hidden=object_feature_size),
             llm=llm, patch_size=patch_size, feat_channels=object_feature_size, max_object_num=max_object_num,
-            max_new_tokens=max_new_tokens, num_selected=num_selected, empty_row_policy=empty_row_policy)
+            max_new_tokens=max_new_tokens, num_selected=num_selected, empty_row_policy=empty_row_policy,
+            rel_cls_type=rel_cls_type, num_relation_classes=self.num_relation_classes)
         # parameters under the reference's names (fp32 masters; the engines keep packed copies)
         for key, shape in head_shapes(self.cfg).items():
             _set_nested(self, key, torch.zeros(shape, dtype=torch.float32, device=self.device))
@@ -505,11 +533,15 @@ class RelationTransformerHeadV4(nn.Module):
         rq = self.run_relation_query(feat, meta, obj_ids, names, info["pan_results"])
         if is_generation is None:
             is_generation = True
+        is_generation = is_generation and self.has_binary        # 'multiclass' alone: no pair selector, no decode
         out = self.decode_selected(rq, names) if is_generation else dict(tokens=None)
+        if self.has_multiclass:                               # behind the tokens' copy: the stream has drained
+            out["mc_host"] = rq["mc_topk"].cpu().numpy()
         rq.update(out)                                        # keeps a lazy rq lazy (`hidden` on demand)
         self.last = rq
         rel_pred, rel_score = self.parse(out["tokens_host"], out["selected_host"], N) if is_generation else ([], [])
-        return dict(rel_pred=rel_pred, rel_score=rel_score)
+        mc_pred, mc_score = self.parse_multiclass(out.get("mc_host"), N)
+        return dict(rel_pred=rel_pred + mc_pred, rel_score=rel_score + mc_score)   # V4:355-356
 
     # ---- two images in flight -------------------------------------------------------------------------------------------
     def submit(self, inputs, slot=0):
@@ -554,7 +586,7 @@ class RelationTransformerHeadV4(nn.Module):
             # image k+1's front half and decode.
             self._wait_front(st)
             rq = self.run_relation_query(feat, meta, obj_ids, names, info["pan_results"])
-            out = self._enqueue_decode(st, rq, names, slot, defer=True)
+            out = self._enqueue_decode(st, rq, names, slot, defer=True) if self.has_binary else dict(tokens=None)
         pend = _Pending(self, st, rq, out, N, inputs=inputs, slot=slot)
         self._slot_pending[slot] = weakref.ref(pend)                   # (a dropped handle frees its slot)
         return pend
@@ -720,6 +752,7 @@ class RelationTransformerHeadV4(nn.Module):
             cids[i, :len(seqs[i])] = seqs[i]
             rpos[i, :len(rope[i])] = rope[i]
         return dict(feat=feat, N=N, names=names, binary=binary, bits=bits, sampled=sampled, selected=selected, where=where,
+                    mc_label=target.reshape(-1, self.num_relation_classes)[sampled].contiguous(),   # V4:128-129, 198-201
                     ids=torch.from_numpy(ids).to(dev), msk=torch.from_numpy(msk).to(dev), K=K, S=S,
                     cids=torch.from_numpy(cids).to(dev), rpos=torch.from_numpy(rpos).to(dev),
                     seq_len=torch.tensor([nv + len(s_) for s_ in seqs], dtype=torch.int32, device=dev),
@@ -748,8 +781,18 @@ class RelationTransformerHeadV4(nn.Module):
         N, K, S = t["N"], t["K"], t["S"]
         patches = eng.patch_embed(t["feat"].to(torch.float32))
         kv = eng.cross_kv(patches)
-        hidden, logit, _ = eng.forward_pairs(kv, t["bits"], N, t["sampled"].to(dev, torch.int32), t["ids"], t["msk"])
-        bce = ops.bce_with_logits(logit, t["binary"][t["sampled"]].to(dev), self.rel_cls_loss_weight)  # V4:186-196, 463-482
+        mc = None
+        if self.has_multiclass:
+            Sn, R = len(t["sampled"]), self.num_relation_classes
+            mc = (torch.empty((Sn, R), device=dev, dtype=torch.float32), torch.empty((Sn, R), device=dev, dtype=torch.float32))
+        hidden, logit, _ = eng.forward_pairs(kv, t["bits"], N, t["sampled"].to(dev, torch.int32), t["ids"], t["msk"], mc=mc)
+        losses = {}
+        if self.has_binary:
+            losses["binary_rel_cls_loss"] = ops.bce_with_logits(logit, t["binary"][t["sampled"]].to(dev),
+                                                                self.rel_cls_loss_weight)   # V4:186-196, 463-482
+        if self.has_multiclass:                                   # V4:196-204, 473-477: self-weighted MLCCE rows
+            rows = ops.mlcce_rows(mc[0], t["mc_label"].to(dev))
+            losses["multiclass_rel_cls_loss"] = torch.mean(rows * (rows / rows.max())) * self.rel_cls_loss_weight
         # pair features of the selected pairs; pairs the sampler skipped stay zero (V4:177, 186)
         nv = q.num_query
         where = t["where"]
@@ -764,8 +807,8 @@ class RelationTransformerHeadV4(nn.Module):
         per_pair = self._mean_per_pair(rl, t["counts"])
         llm_loss = torch.stack(per_pair).mean()                                              # V4:350-351
         self.last = dict(sampled=t["sampled"], selected=t["selected"], bits=t["bits"], bce_logit=logit, llm_logits=logits,
-                         llm_row_loss=rl, llm_pair_loss=per_pair)
-        return dict(binary_rel_cls_loss=bce, rel_llm_loss=llm_loss)
+                         llm_row_loss=rl, llm_pair_loss=per_pair, mc_logit=None if mc is None else mc[0])
+        return dict(**losses, rel_llm_loss=llm_loss)                                        # V4:345-351
 
     def forward_train_grad(self, inputs, sampled=None, selected=None, dropout=None):
         """The training branch WITH its gradient graph (V4:327-351, 463-482; tools/train.py:239-246 back-propagates the
@@ -800,8 +843,15 @@ class RelationTransformerHeadV4(nn.Module):
                 dropout = G.Dropout(q.hidden_dropout, q.attn_dropout)
             h = G.qformer_pairs(P, self.cfg, patches, t["ids"].to(torch.int64), t["msk"], keep, dropout or None)
             out_s = h[:, :q.q_rows]                                                          # V4:185
-            logit = F.linear(out_s[:, 0], P["binary_rel_cls_pred.weight"], P["binary_rel_cls_pred.bias"]).squeeze(1)
-            bce = G.BceFn.apply(logit, t["binary"][t["sampled"]].to(dev), self.rel_cls_loss_weight)
+            losses, logit, mc_logit = {}, None, None
+            if self.has_binary:
+                logit = F.linear(out_s[:, 0], P["binary_rel_cls_pred.weight"], P["binary_rel_cls_pred.bias"]).squeeze(1)
+                losses["binary_rel_cls_loss"] = G.BceFn.apply(logit, t["binary"][t["sampled"]].to(dev),
+                                                              self.rel_cls_loss_weight)
+            if self.has_multiclass:                                                          # V4:196-204, 473-477
+                mc_logit = F.linear(out_s[:, 0], P["multiclass_rel_cls_pred.weight"], P["multiclass_rel_cls_pred.bias"])
+                losses["multiclass_rel_cls_loss"] = G.multiclass_loss(mc_logit, t["mc_label"].to(dev),
+                                                                      self.rel_cls_loss_weight)
             # pair features of the selected pairs as the reference builds them (V4:177, 186): a zero table of all N*N pairs,
             # `table[sampled] = out`.  The sampler draws WITH replacement (V4:437-461), and index_put's backward hands
             # every duplicate row the gradient of its table entry - so a selected pair that was drawn d times sends the
@@ -819,9 +869,11 @@ class RelationTransformerHeadV4(nn.Module):
             rl = G.CrossEntropyRowsFn.apply(logits, t["want_lab"])
             per_pair = self._mean_per_pair(rl, t["counts"])
             llm_loss = torch.stack(per_pair).mean()                                          # V4:350-351
-        self.last = dict(sampled=t["sampled"], selected=t["selected"], bits=t["bits"], bce_logit=logit.detach(),
-                         llm_logits=logits.detach(), llm_row_loss=rl.detach(), llm_pair_loss=[x.detach() for x in per_pair])
-        return dict(binary_rel_cls_loss=bce, rel_llm_loss=llm_loss)
+        self.last = dict(sampled=t["sampled"], selected=t["selected"], bits=t["bits"],
+                         bce_logit=None if logit is None else logit.detach(), llm_logits=logits.detach(),
+                         llm_row_loss=rl.detach(), llm_pair_loss=[x.detach() for x in per_pair],
+                         mc_logit=None if mc_logit is None else mc_logit.detach())
+        return dict(**losses, rel_llm_loss=llm_loss)                                        # V4:345-351
 
     def train(self, mode: bool = True):
         """The training flag only; `requires_grad` is NOT tied to it (set once at construction: fp32 masters are
@@ -845,7 +897,7 @@ class RelationTransformerHeadV4(nn.Module):
         if self.training:
             raise NotImplementedError("training branch (V4:114-133, 360-406) is out of scope of this build")
         st, gslot = torch.cuda.current_stream(self.device), 0
-        items, results, tokens = [], [None] * len(batch), None
+        items, results, tokens, mcs = [], [None] * len(batch), None, {}
         with torch.cuda.stream(st):
             for i, inputs in enumerate(batch):
                 feat, meta, info, obj_ids, names = self._unpack(inputs)
@@ -853,6 +905,10 @@ class RelationTransformerHeadV4(nn.Module):
                     results[i] = dict(rel_pred=[], rel_score=[])
                     continue
                 rq = self.run_relation_query(feat, meta, obj_ids, names, info["pan_results"])
+                if self.has_multiclass:
+                    mcs[i] = (rq["mc_topk"], len(obj_ids))
+                if not self.has_binary:
+                    continue
                 X, plen = self.llm_inputs(rq, names)
                 items.append((i, len(obj_ids), rq["selected"], X, plen))
             if items:
@@ -868,7 +924,7 @@ class RelationTransformerHeadV4(nn.Module):
                     Xall = torch.cat([Xall, Xall[-1:].expand(extra, -1, -1)])
                     pall = torch.cat([pall, pall[-1:].expand(extra)])
                 tokens = self.llm_engine.generate(Xall, pall, suppress_eos=self.suppress_eos, slot=gslot)
-        return _PendingBatch(self, st, items, results, tokens).result()
+        return _PendingBatch(self, st, items, results, tokens, mcs).result()
 
     def image_constants(self, feat, meta, obj_ids, pan):
         """What the rank that holds an image's segmenter outputs hands to the other ranks: the patch
@@ -949,43 +1005,88 @@ class RelationTransformerHeadV4(nn.Module):
         p0, p1 = (0, B) if pair_range is None else pair_range
         q = self.cfg.qformer
         single = 0 < p1 - p0 <= self.pair_chunk                  # one chunk: take the engine's outputs as they are
+        mc = None
+        if self.has_multiclass:
+            if pair_range is not None:
+                raise PsgHipError("the multiclass head runs over all pairs of an image (no pair_range)")
+            # every chunk writes its rows of ONE [N^2, R] buffer (probabilities of the diagonal pairs already 0)
+            R = self.num_relation_classes
+            mc = (torch.empty((B, R), device=dev, dtype=torch.float32), torch.empty((B, R), device=dev, dtype=torch.float32))
+        mcs = lambda c0, c1: None if mc is None else (mc[0][c0:c1], mc[1][c0:c1])  # noqa: E731
         if self.cls_first and p1 > p0:
             # selection phase first (per chunk of pairs), the selected pairs' rows 1..32 on demand
             pending, lgs, prs = [], [], []
             for c0 in range(p0, p1, self.pair_chunk):
                 c1 = min(p1, c0 + self.pair_chunk)
                 ent = self._chunk_prompts(ck, N, c0, c1)
-                state, lg, pr = eng.forward_pairs_cls(kv, bits, N, ent[0], ent[1], ent[2], prompts=ent[3])
+                state, lg, pr = eng.forward_pairs_cls(kv, bits, N, ent[0], ent[1], ent[2], prompts=ent[3], mc=mcs(c0, c1))
                 pending.append((c0, c1, state, 0))
                 lgs.append(lg)
                 prs.append(pr)
-            logit, prob = (lgs[0], prs[0]) if len(lgs) == 1 else (torch.cat(lgs), torch.cat(prs))
+            if self.has_binary:
+                logit, prob = (lgs[0], prs[0]) if len(lgs) == 1 else (torch.cat(lgs), torch.cat(prs))
+            else:
+                logit = prob = None
             out = _LazyRQ(patches=patches, bits=bits, exist_logit=logit, exist_prob=prob, num_objects=N,
                           pair_range=(p0, p1), uidx=uidx, pending=pending)
             out.engine = eng
             if pair_range is None:
-                out["selected"] = self.select_pairs(prob, N)
+                out["selected"] = self.select_pairs(prob, N) if self.has_binary else None
+            self._multiclass_topk(out, mc)
             return out
         if not single:
             np_ = max(0, p1 - p0)                                 # an empty shard (more ranks than pairs) is legal
             hidden = torch.empty((np_ * q.q_rows, q.hidden), device=dev, dtype=self.act_dtype)
-            logit = torch.empty(np_, device=dev, dtype=torch.float32)
-            prob = torch.empty(np_, device=dev, dtype=torch.float32)
+            logit = torch.empty(np_, device=dev, dtype=torch.float32) if self.has_binary else None
+            prob = torch.empty(np_, device=dev, dtype=torch.float32) if self.has_binary else None
         for c0 in range(p0, p1, self.pair_chunk):
             c1 = min(p1, c0 + self.pair_chunk)
             ent = self._chunk_prompts(ck, N, c0, c1)
             if single:
-                hidden, logit, prob = eng.forward_pairs(kv, bits, N, ent[0], ent[1], ent[2])
+                hidden, logit, prob = eng.forward_pairs(kv, bits, N, ent[0], ent[1], ent[2], mc=mcs(c0, c1))
             else:                                                 # the last layer writes straight into its slice
                 _, lg, pr = eng.forward_pairs(kv, bits, N, ent[0], ent[1], ent[2],
-                                              hidden_out=hidden[(c0 - p0) * q.q_rows:(c1 - p0) * q.q_rows])
-                logit[c0 - p0:c1 - p0] = lg
-                prob[c0 - p0:c1 - p0] = pr
+                                              hidden_out=hidden[(c0 - p0) * q.q_rows:(c1 - p0) * q.q_rows],
+                                              mc=mcs(c0, c1))
+                if self.has_binary:
+                    logit[c0 - p0:c1 - p0] = lg
+                    prob[c0 - p0:c1 - p0] = pr
         out = dict(patches=patches, bits=bits, hidden=hidden, exist_logit=logit, exist_prob=prob,
                    num_objects=N, pair_range=(p0, p1), uidx=uidx)
         if pair_range is None:
-            out["selected"] = self.select_pairs(prob, N)
+            out["selected"] = self.select_pairs(prob, N) if self.has_binary else None
+        self._multiclass_topk(out, mc)
         return out
+
+    def _multiclass_topk(self, out, mc):
+        """V4:238-257 with the SURVEY 0.3 corrections, on the device: the k = min(num_multiclass_triples, N^2 R) best
+        flat indices f = p R + r of the [N^2, R] probabilities (diagonal already 0; psg_topk's order) as ONE int32 [2, k]
+        tensor - row 0 the indices, row 1 the fp32 scores' bits - so that the host fetches both with a single copy."""
+        if mc is None:
+            return
+        n = mc[1].numel()
+        k = min(self.num_multiclass_triples, n)
+        res = torch.empty((2, k), device=mc[1].device, dtype=torch.int32)
+        ws = torch.empty(ops.topk_large_workspace_bytes(mc[1].device, n, k), device=mc[1].device, dtype=torch.uint8)
+        ops.topk_large(mc[1].view(-1), k, ws, idx=res[0], val=res[1].view(torch.float32))
+        out.update(mc_logit=mc[0], mc_prob=mc[1], mc_topk=res)
+
+    def parse_multiclass(self, mc_host, object_num):
+        """Host side of `_multiclass_topk`: the kept flat indices f -> triples [p // N, p % N, r] (p = f // R, r = f % R)
+        with their scores as Python floats.  The indices are distinct, so are the triples (V4:255-257 keeps the first
+        occurrence of a triple)."""
+        if mc_host is None:
+            return [], []
+        R = self.num_relation_classes
+        idx, val = mc_host[0], mc_host[1].view(np.float32)
+        rel_pred, rel_score = [], []
+        for f, v in zip(idx.tolist(), val.tolist()):
+            if f < 0:
+                break
+            p = f // R
+            rel_pred.append([p // object_num, p % object_num, f % R])
+            rel_score.append(float(v))
+        return rel_pred, rel_score
 
     def run_relation_query_shards(self, items, pair_range, patches_list):
         """Pair sharding over R images: a shard of EVERY image in one Q-Former pass - the dense projections

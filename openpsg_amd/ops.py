@@ -287,6 +287,74 @@ def topk(score, k):
     return idx, val
 
 
+def multiclass_head(x, w, b, P, nq, pair_index=None, N=0, logit=None, prob=None):
+    """Multiclass relation head (K8b): logits / probabilities [P, R] fp32 of the cls rows x[p*nq] (row stride nq*hidden).
+    pair_index int32 [P] (global pair ids, None = p) and N mark the diagonal pairs, whose probabilities are 0.  logit /
+    prob: caller-owned [P, R] fp32 outputs (e.g. slices of one [N^2, R] buffer); allocated when None."""
+    lib, ctx, st = _env(x)
+    hidden, R = x.shape[1], w.shape[0]
+    if logit is None:
+        logit = torch.empty((P, R), device=x.device, dtype=torch.float32)
+    if prob is None:
+        prob = torch.empty((P, R), device=x.device, dtype=torch.float32)
+    if logit.shape != (P, R) or prob.shape != (P, R):
+        raise PsgHipError(f"multiclass_head: outputs must be [{P}, {R}], got {tuple(logit.shape)} / {tuple(prob.shape)}")
+    check(lib.psg_multiclass_head(ctx, _p(x), _p(w, torch.float32, "w"), _p(b, torch.float32, "b"), P, nq, hidden, R,
+                                  _p(pair_index, torch.int32, "pair_index"), int(N), _p(logit, torch.float32, "logit"),
+                                  _p(prob, torch.float32, "prob"), _dt(x), st), "psg_multiclass_head")
+    return logit, prob
+
+
+def topk_large_workspace_bytes(device, n, k):
+    import ctypes
+    out = ctypes.c_int64(0)
+    check(_lib.load().psg_topk_large_workspace(_lib.ctx(torch.device(device).index or 0), int(n), int(k),
+                                               ctypes.byref(out)),
+          "psg_topk_large_workspace")
+    return out.value
+
+
+def topk_large(score, k, workspace=None, idx=None, val=None):
+    """`topk` for large n (k <= 256; K9b): the same order and output.  workspace: uint8 device tensor of at least
+    `topk_large_workspace_bytes(...)` bytes (allocated when None); idx int32 [k] / val fp32 [k]: caller-owned outputs."""
+    lib, ctx, st = _env(score)
+    n = score.numel()
+    need = topk_large_workspace_bytes(score.device, n, k)
+    if workspace is None:
+        workspace = torch.empty(need, device=score.device, dtype=torch.uint8)
+    if workspace.numel() * workspace.element_size() < need:
+        raise PsgHipError(f"topk_large: workspace of {workspace.numel() * workspace.element_size()} bytes, {need} needed")
+    if idx is None:
+        idx = torch.empty(k, device=score.device, dtype=torch.int32)
+    if val is None:
+        val = torch.empty(k, device=score.device, dtype=torch.float32)
+    if idx.numel() != k or val.numel() != k:
+        raise PsgHipError(f"topk_large: outputs of {idx.numel()} / {val.numel()} elements for k={k}")
+    check(lib.psg_topk_large(ctx, _p(score, torch.float32, "score"), n, k, _p(workspace, name="workspace"),
+                             workspace.numel() * workspace.element_size(), _p(idx, torch.int32, "idx"),
+                             _p(val, torch.float32, "val"), st), "psg_topk_large")
+    return idx, val
+
+
+def mlcce_rows(logits, labels):
+    """Per-row multilabel categorical cross entropy (V4:484-495) of fp32 [S, R] logits with 0/1 fp32 labels."""
+    lib, ctx, st = _env(logits)
+    rows, R = logits.shape
+    loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    check(lib.psg_train_mlcce_fwd(ctx, _p(logits, torch.float32, "logits"), _p(labels, torch.float32, "labels"), rows, R,
+                                  _p(loss), st), "psg_train_mlcce_fwd")
+    return loss
+
+
+def mlcce_rows_bwd(logits, labels, dloss):
+    lib, ctx, st = _env(logits)
+    rows, R = logits.shape
+    d = torch.empty_like(logits)
+    check(lib.psg_train_mlcce_bwd(ctx, _p(logits, torch.float32, "logits"), _p(labels, torch.float32, "labels"), rows, R,
+                                  _p(dloss, torch.float32, "dloss"), _p(d), st), "psg_train_mlcce_bwd")
+    return d
+
+
 def gather_rows(src, idx, dst):
     """dst[r] = src[idx[r]] (rows; idx < 0 -> zeros).  src/dst may be row-strided 2-D views."""
     lib, ctx, st = _env(src)

@@ -55,8 +55,15 @@ class RelationQueryEngine:
         # patch embedding stays fp32 (exact f32 MFMA kernel): one 8.6 GFLOP GEMM per image over fp32 mask_features
         self.patch_w = f32("patch_embed.proj.weight")
         self.patch_b = f32("patch_embed.proj.bias")
-        self.exist_w = f32("binary_rel_cls_pred.weight").reshape(-1).contiguous()
-        self.exist_b = f32("binary_rel_cls_pred.bias")
+        # relation classifiers on the cls row (V4:91-95): the existence head ('binary' in rel_cls_type) and / or the
+        # multiclass head ('multiclass'); an engine without one of them launches nothing for it
+        self.exist_w = self.exist_b = self.mc_w = self.mc_b = None
+        if "binary_rel_cls_pred.weight" in weights:
+            self.exist_w = f32("binary_rel_cls_pred.weight").reshape(-1).contiguous()
+            self.exist_b = f32("binary_rel_cls_pred.bias")
+        if "multiclass_rel_cls_pred.weight" in weights:
+            self.mc_w = f32("multiclass_rel_cls_pred.weight")
+            self.mc_b = f32("multiclass_rel_cls_pred.bias")
         self.layers = []
         for l in range(q.layers):
             p = f"relation_qformer.encoder.layer.{l}."
@@ -239,21 +246,38 @@ class RelationQueryEngine:
             return o16, out32
         return self._ln(x, r16, None, bias, ln, out16=out16, period=period, index=index)
 
-    def forward_pairs(self, kv, bits, num_objects, pair_index, ids, text_mask, hidden_out=None, segments=None):
+    def _cls_heads(self, x, P, nq, pair_index, num_objects, segments, mc):
+        """The classifiers on the cls rows x[p*nq] (fp32 twin where one exists): existence logits / probabilities [P]
+        (None, None without a binary head) and, when `mc` = (logit [P, R], prob [P, R]) fp32 buffers are given, the
+        multiclass head into them (a separate launch behind the existence head's: that one is unchanged)."""
+        logit = prob = None
+        if self.exist_w is not None:
+            logit, prob = ops.exist_head(x, self.exist_w, self.exist_b, P, nq)
+        if mc is not None:
+            if self.mc_w is None:
+                raise PsgHipError("multiclass outputs requested from an engine without multiclass_rel_cls_pred")
+            if segments is not None:
+                raise PsgHipError("the multiclass head does not run over pair-sharded segments of several images")
+            ops.multiclass_head(x, self.mc_w, self.mc_b, P, nq, pair_index, num_objects, logit=mc[0], prob=mc[1])
+        return logit, prob
+
+    def forward_pairs(self, kv, bits, num_objects, pair_index, ids, text_mask, hidden_out=None, segments=None, mc=None):
         """pair_index int32 [P] (p = i*N + j), ids int32 [P,T], text_mask uint8 [P,T].
         Returns (hidden [P*33, 768] in the activation dtype, exist_logit [P] fp32, exist_prob [P] fp32).
         hidden_out: caller-owned [P*33, 768] buffer the last layer writes into (no copy when pairs are chunked).
         segments: [(first pair, pair count, kv, bits, num_objects)] - the pairs come from several images (pair
-        sharding); everything but the cross-attention runs over all of them at once."""
+        sharding); everything but the cross-attention runs over all of them at once.
+        mc: (logit [P, R], prob [P, R]) fp32 buffers for the multiclass head (see `_cls_heads`)."""
         P, T = ids.shape
         X, X32, shared0 = self._embed(ids)
         for li in range(len(self.layers)):
             X, X32 = self._layer(li, X, X32, P, T, text_mask, pair_index, kv, bits, num_objects, segments, shared0,
                                  hidden_out if li == len(self.layers) - 1 else None)
-        logit, prob = ops.exist_head(X32 if X32 is not None else X, self.exist_w, self.exist_b, P, self.cfg.qformer.q_rows)
+        logit, prob = self._cls_heads(X32 if X32 is not None else X, P, self.cfg.qformer.q_rows, pair_index, num_objects,
+                                      segments, mc)
         return X, logit, prob
 
-    def forward_pairs_cls(self, kv, bits, num_objects, pair_index, ids, text_mask, segments=None, prompts=None):
+    def forward_pairs_cls(self, kv, bits, num_objects, pair_index, ids, text_mask, segments=None, prompts=None, mc=None):
         """Selection phase: everything the existence logits depend on, and nothing else.
 
         The existence head reads row 0 (the cls row) of the last layer's output (V4:206-209), and rows 1..32
@@ -265,6 +289,7 @@ class RelationQueryEngine:
         prompts = (ids_u int32 [U, T], mask_u uint8 [U, T], inv int32 [P][, rows int32 [P*33]]): the distinct prompts of
         these pairs and each pair's row in that table (ids == ids_u[inv]); lets the prompt-only work run on U rows instead
         of P.  rows (optional, cached by the caller) = inv[p] * 33 + r, the query rows of each pair's prompt block.
+        mc: (logit [P, R], prob [P, R]) fp32 buffers for the multiclass head (see `_cls_heads`).
         Returns (state, exist_logit [P], exist_prob [P]); state feeds `pair_hidden`."""
         q = self.cfg.qformer
         nq, H = q.q_rows, q.hidden
@@ -276,17 +301,18 @@ class RelationQueryEngine:
                         4 if self.dtype == torch.float32 else 2) + q.heads * 256 <= 160 * 1024)
         if (prompts is not None and segments is None and nl == 2 and T > 0 and in_space and self.dedup_prompts
                 and prompts[0].shape[0] <= 0.9 * P):
-            return self._forward_pairs_cls_dedup(kv, bits, num_objects, pair_index, text_mask, prompts)
+            return self._forward_pairs_cls_dedup(kv, bits, num_objects, pair_index, text_mask, prompts, mc)
         X, X32, shared0 = self._embed(ids)
         for li in range(nl - 1):
             X, X32 = self._layer(li, X, X32, P, T, text_mask, pair_index, kv, bits, num_objects, segments, shared0)
         logit, prob = self._cls_phase(X[:RQ], self._s(X32, 0, RQ), X[RQ:], None, text_mask, P, T, kv, bits, num_objects,
-                                      pair_index, segments, in_space, X)
+                                      pair_index, segments, in_space, X, mc)
         state = dict(X=X, X32=X32, P=P, T=T, text_mask=text_mask, pair_index=pair_index, kv=kv, bits=bits,
                      num_objects=num_objects, segments=segments)
         return state, logit, prob
 
-    def _cls_phase(self, Xq, Xq32, Xt, text_index, mask, P, T, kv, bits, num_objects, pair_index, segments, in_space, X=None):
+    def _cls_phase(self, Xq, Xq32, Xt, text_index, mask, P, T, kv, bits, num_objects, pair_index, segments, in_space, X=None,
+                   mc=None):
         """Last layer for the cls row of every pair.  Xq [P*33, H] query rows entering the layer (Xq32: fp32 twin); Xt:
         text rows, block text_index[p] (None: block p) per pair, `mask` indexed the same way.  X: the two as one tensor
         (K | V form)."""
@@ -327,9 +353,9 @@ class RelationQueryEngine:
         iq = self._ffn1(Cq, L["w1q"], L["b1q"])
         hq = self._lin(iq, L["w2q"])
         Xc, Xc32 = self._ln(hq, Cq, Cq32, L["b2q"], L["ln_q"])
-        return ops.exist_head(Xc32 if Xc32 is not None else Xc, self.exist_w, self.exist_b, P, 1)
+        return self._cls_heads(Xc32 if Xc32 is not None else Xc, P, 1, pair_index, num_objects, segments, mc)
 
-    def _forward_pairs_cls_dedup(self, kv, bits, num_objects, pair_index, text_mask, prompts):
+    def _forward_pairs_cls_dedup(self, kv, bits, num_objects, pair_index, text_mask, prompts, mc=None):
         """forward_pairs_cls with the prompt-only work done per DISTINCT prompt (two layers).  Layer 0's input is the
         learned query block plus the prompt's embeddings, so its whole self-attention block (HF-IB:471-530) is a
         function of the prompt; a pair enters at the cross-attention (its object masks).  The text rows never see the
@@ -401,7 +427,8 @@ class RelationQueryEngine:
         hq = self._lin(iq, L["w2q"])
         Xq, Xq32 = self._ln(hq, Cq, Cq32, L["b2q"], L["ln_q"])
         del iq, hq, Cq
-        logit, prob = self._cls_phase(Xq, Xq32, Xt_u, inv, mask_u, P, T, kv, bits, num_objects, pair_index, None, True)
+        logit, prob = self._cls_phase(Xq, Xq32, Xt_u, inv, mask_u, P, T, kv, bits, num_objects, pair_index, None, True,
+                                      mc=mc)
         state = dict(Xq=Xq, Xq32=Xq32, Xt_u=Xt_u, Xt_u32=Xt_u32, inv=inv, P=P, T=T, text_mask=text_mask,
                      pair_index=pair_index, kv=kv, bits=bits, num_objects=num_objects, segments=None)
         return state, logit, prob

@@ -243,6 +243,30 @@ class BceFn(torch.autograd.Function):
         return d, None, None
 
 
+class MlcceRowsFn(torch.autograd.Function):
+    """Per-row multilabel categorical cross entropy (V4:484-495) of the multiclass head: forward / backward are
+    psg_train_mlcce_fwd / _bwd.  The labels take no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits, labels = _f32(logits, "logits"), _f32(labels, "labels")
+        ctx.save_for_backward(logits, labels)
+        return ops.mlcce_rows(logits, labels)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, labels = ctx.saved_tensors
+        return ops.mlcce_rows_bwd(logits, labels, _f32(dloss)), None
+
+
+def multiclass_loss(logits, labels, weight):
+    """V4:473-477: the row losses weighted by themselves - w = loss / loss.max(), NOT detached, so autograd takes the
+    gradient through max() (split evenly among tied rows) as in the reference - then mean x rel_cls_loss_weight."""
+    loss = MlcceRowsFn.apply(logits, labels)
+    w = loss / loss.max()
+    return torch.mean(loss * w) * weight
+
+
 class PatchEmbedFn(torch.autograd.Function):
     """timm PatchEmbed (V4:410): forward = the exact-fp32 matrix-core kernel of the inference path; backward = the weight
     gradient as one GEMM over the unfolded feature map (the features themselves come from the frozen segmenter)."""

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .config import PSGConfig
+from .config import REL_CLS_TYPES, PSGConfig
 
 
 def head_shapes(cfg: PSGConfig) -> dict:
@@ -33,11 +33,17 @@ def head_shapes(cfg: PSGConfig) -> dict:
         "relation_qformer.embeddings.layernorm.bias": (q.hidden,),
         "relation_query": (1, q.num_query, q.hidden),
         "rel_cls_query": (1, 1, q.hidden),
-        "binary_rel_cls_pred.weight": (1, q.hidden),
-        "binary_rel_cls_pred.bias": (1,),
-        "language_projection.weight": (cfg.llm.hidden, q.hidden),
-        "language_projection.bias": (cfg.llm.hidden,),
     }
+    if cfg.rel_cls_type not in REL_CLS_TYPES:
+        raise ValueError(f"rel_cls_type must be one of {REL_CLS_TYPES}, got {cfg.rel_cls_type!r}")
+    if "binary" in cfg.rel_cls_type:                                    # V4:91-92
+        s["binary_rel_cls_pred.weight"] = (1, q.hidden)
+        s["binary_rel_cls_pred.bias"] = (1,)
+    if "multiclass" in cfg.rel_cls_type:                                # V4:93-95
+        s["multiclass_rel_cls_pred.weight"] = (cfg.num_relation_classes, q.hidden)
+        s["multiclass_rel_cls_pred.bias"] = (cfg.num_relation_classes,)
+    s["language_projection.weight"] = (cfg.llm.hidden, q.hidden)
+    s["language_projection.bias"] = (cfg.llm.hidden,)
     for l in range(q.layers):
         p = f"relation_qformer.encoder.layer.{l}."
         for att, kin in (("attention", q.hidden), ("crossattention", q.enc_hidden)):
@@ -107,6 +113,8 @@ def _std_for(key: str, shape) -> tuple[float, float]:
     if key.endswith("lm_head.weight"):
         return 0.0, 3.0 / np.sqrt(fan_in)     # logit std ~3 -> argmax margins >> fp32 noise
     if key.startswith("binary_rel_cls_pred"):
+        return 0.0, 2.0 / np.sqrt(fan_in)
+    if key.startswith("multiclass_rel_cls_pred"):
         return 0.0, 2.0 / np.sqrt(fan_in)
     return 0.0, 1.0 / np.sqrt(fan_in)
 
