@@ -67,8 +67,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *        psg_rmsnorm_split2, psg_rmsnorm_split / psg_rope_kvwrite_scaled /
  *        psg_silu_mul_split added)
  *   600  round 6 (psg_dense_gemm_split added; psg_split_f16x3 order 2)
- *   601  psg_multiclass_head, psg_topk_large(_workspace), psg_train_mlcce_fwd / _bwd added */
-#define PSG_ABI_VERSION 601
+ *   601  psg_multiclass_head, psg_topk_large(_workspace), psg_train_mlcce_fwd / _bwd added
+ *   602  grouped-query attention: psg_rope_kvwrite_gqa, psg_rope_kvwrite_scaled_gqa, psg_llm_attn_gqa, psg_prefill_attn_gqa,
+ *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added */
+#define PSG_ABI_VERSION 602
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -279,6 +281,34 @@ int psg_prefill_attn_rope(psg_ctx*, const void* qkv, const int32_t* tok_pos, con
 int psg_decode_attn(psg_ctx*, const void* qkv, int qkv_splits, const int32_t* tok_pair, const int32_t* tok_pos,
                     const float* rope_cos, const float* rope_sin, int rows, int heads, int head_dim, int ctx, void* k_cache,
                     void* v_cache, void* out, int dtype, void* stream);
+
+/* ---- grouped-query attention (GQA): kv_heads key / value heads, each shared by G = heads / kv_heads query heads
+ * (1 <= G <= 8; query head h reads key / value head h / G).  The projection row is [q | k | v] of width
+ * (heads + 2 kv_heads) * 128; KV caches are [pairs][kv_heads][ctx][128].  Otherwise each entry is the multi-head entry of
+ * the same name; with kv_heads == heads they compute what it computes.  The *_rope / *_kvwrite forms write a key / value
+ * head's cache rows once (from the group's first query head).
+ * psg_decode_attn_gqa: one workgroup serves G / parts query heads of a (row, KV head) unit, streaming that head's cache
+ * once for all of them; G must be a power of two. */
+int psg_rope_kvwrite_gqa(psg_ctx*, const void* qkv, int qkv_splits, const int32_t* tok_pair, const int32_t* tok_pos,
+                         const int32_t* rope_pos, const float* rope_cos, const float* rope_sin, int64_t rows, int heads,
+                         int kv_heads, int head_dim, int ctx, void* q_out, void* k_cache, void* v_cache, int dtype,
+                         void* stream);
+int psg_rope_kvwrite_scaled_gqa(psg_ctx*, const float* qkv, const float* row_scale, const float* col_scale,
+                                const int32_t* tok_pair, const int32_t* tok_pos, const float* rope_cos,
+                                const float* rope_sin, int slices, int64_t rows, int heads, int kv_heads, int head_dim,
+                                int ctx, float* q_out, float* k_cache, float* v_cache, void* stream);
+int psg_llm_attn_gqa(psg_ctx*, const void* q, const void* k_cache, const void* v_cache, const int32_t* tok_pair,
+                     const int32_t* tok_pos, int64_t rows, int heads, int kv_heads, int head_dim, int ctx, void* out,
+                     int dtype, void* stream);
+int psg_prefill_attn_gqa(psg_ctx*, const void* q, const void* k_cache, const void* v_cache, const int32_t* tok_pos,
+                         int pairs, int rows_per_pair, int heads, int kv_heads, int head_dim, int ctx, void* out, int dtype,
+                         void* stream);
+int psg_prefill_attn_rope_gqa(psg_ctx*, const void* qkv, const int32_t* tok_pos, const float* rope_cos,
+                              const float* rope_sin, int pairs, int rows_per_pair, int heads, int kv_heads, int head_dim,
+                              int ctx, void* k_cache, void* v_cache, void* out, int dtype, void* stream);
+int psg_decode_attn_gqa(psg_ctx*, const void* qkv, int qkv_splits, const int32_t* tok_pair, const int32_t* tok_pos,
+                        const float* rope_cos, const float* rope_sin, int rows, int heads, int kv_heads, int head_dim,
+                        int ctx, void* k_cache, void* v_cache, void* out, int dtype, void* stream);
 
 /* ---- SwiGLU gate, HF-LL:163-177: out = silu(gate_up[:, :inter]) * gate_up[:, inter:].
  * splits > 0: gate_up is fp32 split-K partials [splits][rows][2*inter]. */

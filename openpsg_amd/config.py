@@ -6,6 +6,8 @@ configs it instantiates (InstructBlipQFormerConfig at :78-82, Llama-2-7b at :99-
 the reference's; tests shrink vocabularies / LLM width, never the Q-Former geometry the kernels are
 specialised for (hidden 768 = 12 heads x 64, 33 query rows).
 """
+from __future__ import annotations
+
 from dataclasses import dataclass, field, asdict
 
 
@@ -44,10 +46,40 @@ class LlamaConfig:
     bos: int = 1
     eos: int = 2
     pad: int = 0               # pad_token = unk_token (V4:105) -> id 0 for Llama-2
+    # key / value heads (HF num_key_value_heads): None = heads (multi-head, Llama-2-7B); fewer = grouped-query attention,
+    # each of the n_kv_heads key / value heads shared by heads / n_kv_heads query heads (Mistral-7B: 32 / 8)
+    kv_heads: int | None = None
 
     @property
     def head_dim(self) -> int:
         return self.hidden // self.heads
+
+    @property
+    def n_kv_heads(self) -> int:
+        """Effective key / value head count (`kv_heads`, or `heads` when unset)."""
+        return self.heads if self.kv_heads is None else int(self.kv_heads)
+
+    @property
+    def kv_group(self) -> int:
+        """Query heads per key / value head (1: multi-head)."""
+        return self.heads // self.n_kv_heads
+
+    @property
+    def kv_dim(self) -> int:
+        """Width of the k_proj / v_proj outputs: n_kv_heads * head_dim."""
+        return self.n_kv_heads * self.head_dim
+
+    def check_kv_heads(self):
+        """Raises ValueError unless the key / value head count is one the kernels are built for: a divisor of `heads`,
+        groups of at most 8 query heads, head_dim 128."""
+        kv = self.n_kv_heads
+        if kv <= 0 or self.heads % kv:
+            raise ValueError(f"kv_heads={kv} must divide heads={self.heads}")
+        if self.heads // kv > 8:
+            raise ValueError(f"grouped-query attention with {self.heads // kv} query heads per key / value head is not "
+                             "built (at most 8)")
+        if kv != self.heads and (self.heads // kv) & (self.heads // kv - 1):
+            raise ValueError(f"grouped-query attention needs a power-of-two group, got {self.heads // kv}")
 
 
 @dataclass(frozen=True)
@@ -74,7 +106,7 @@ class PSGConfig:
 REL_CLS_TYPES = ("binary", "binary+multiclass", "multiclass")
 
 
-def tiny_llm(hidden=256, layers=2, inter=512, vocab=512) -> LlamaConfig:
-    """A small full-arithmetic Llama for parity tests (head_dim stays 128)."""
+def tiny_llm(hidden=256, layers=2, inter=512, vocab=512, kv_heads=None) -> LlamaConfig:
+    """A small full-arithmetic Llama for parity tests (head_dim stays 128); kv_heads < hidden / 128: grouped-query."""
     assert hidden % 128 == 0
-    return LlamaConfig(hidden=hidden, heads=hidden // 128, layers=layers, inter=inter, vocab=vocab)
+    return LlamaConfig(hidden=hidden, heads=hidden // 128, layers=layers, inter=inter, vocab=vocab, kv_heads=kv_heads)

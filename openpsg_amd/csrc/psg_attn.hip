@@ -608,7 +608,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) llm_attn_kernel(const T* __restrict__ q, const T* __restrict__ kc,
                                                        const T* __restrict__ vc, const int32_t* __restrict__ tok_pair,
                                                        const int32_t* __restrict__ tok_pos, int64_t rows, int heads,
-                                                       int ctx, T* __restrict__ out) {
+                                                       int kvh, int ctx, T* __restrict__ out) {
   __shared__ float s_q[4][128];
   __shared__ float s_p[4][64];
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -626,7 +626,8 @@ __global__ void __launch_bounds__(256) llm_attn_kernel(const T* __restrict__ q, 
   s_q[wid][lane] = Act<T>::ld(q, row * hidden + h * 128 + lane);
   s_q[wid][lane + 64] = Act<T>::ld(q, row * hidden + h * 128 + lane + 64);
   __builtin_amdgcn_wave_barrier();
-  const int64_t cbase = ((int64_t)tok_pair[row] * heads + h) * ctx * 128;
+  // caches [pair][kvh][ctx][128]: query head h reads key / value head h / (heads / kvh) (kvh == heads: multi-head)
+  const int64_t cbase = ((int64_t)tok_pair[row] * kvh + h / (heads / kvh)) * ctx * 128;
   const float scale = 0.08838834764831845f;  // 1/sqrt(128)
   float m_run = -INFINITY, l_run = 0.f, o1 = 0.f, o2 = 0.f;
   for (int base = 0; base <= pos; base += 64) {
@@ -679,9 +680,27 @@ extern "C" int psg_llm_attn(psg_ctx* ctx_, const void* q, const void* k_cache, c
   int64_t waves = rows * heads;
   PSG_DISPATCH_DTYPE(dtype, "psg_llm_attn",
                      (llm_attn_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, ctx,
-                         (T*)out)));
+                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, heads,
+                         ctx, (T*)out)));
   PSG_CHECK_LAUNCH("psg_llm_attn");
+  return PSG_OK;
+}
+
+extern "C" int psg_llm_attn_gqa(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
+                                const int32_t* tok_pair, const int32_t* tok_pos, int64_t rows, int heads, int kv_heads,
+                                int head_dim, int ctx, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && q && k_cache && v_cache && tok_pair && tok_pos && out, PSG_ERR_INVALID,
+              "psg_llm_attn_gqa: NULL argument");
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_llm_attn_gqa: head_dim=%d (kernel is built for 128)", head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "psg_llm_attn_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  int64_t waves = rows * heads;
+  PSG_DISPATCH_DTYPE(dtype, "psg_llm_attn_gqa",
+                     (llm_attn_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, kv_heads,
+                         ctx, (T*)out)));
+  PSG_CHECK_LAUNCH("psg_llm_attn_gqa");
   return PSG_OK;
 }
 
@@ -875,5 +894,264 @@ extern "C" int psg_decode_attn(psg_ctx* ctx_, const void* qkv, int qkv_splits, c
                          qkv, qkv_splits, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, ctx, (T*)k_cache,
                          (T*)v_cache, (T*)out)));
   PSG_CHECK_LAUNCH("psg_decode_attn");
+  return PSG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The fused decode step (rotary + KV append + attention) for grouped-query attention: G = heads / kvh query heads share
+// one key / value head.  Unit = (row, KV head, part): a workgroup of four waves serves GQ = G / parts query heads of
+// the group, so that the KV head's cache rows [0, pos) leave HBM once per part and every K / V tile in registers is used
+// for all GQ score rows and all GQ P.V accumulations.  The arithmetic per query head is psg_decode_attn4_unit's, in the
+// same order: the same key layout (wave w owns keys {64 b + 16 w .. + 15}, a load instruction covers two whole rows),
+// the same transposing swizzle tree per key, the same per-wave online softmax in fp32 and the same LDS merge with the
+// new token's own term - a query head gets the bits the multi-head kernel gives it on the cache expanded to MHA.
+// The new token: wave w rotates the queries of local heads w and w + 4 (psg_rope_pair) and the group's key; the first
+// part's wave 0 appends the key / value row at slot `pos`.
+// ---------------------------------------------------------------------------------------------
+struct PsgDecodeGqaScratch {
+  float q[PSG_GQA_MAX_GROUP][128];
+  float p[4][PSG_GQA_MAX_GROUP][16];
+  float o[4][2][PSG_GQA_MAX_GROUP][128];      // [wave][half-wave][head][dim]
+  float ml[4][PSG_GQA_MAX_GROUP][2];
+  float snew[PSG_GQA_MAX_GROUP];
+};
+
+template <typename T, int GQ>
+__global__ void __launch_bounds__(256) decode_attn_gqa_kernel(const void* __restrict__ qkv, int qs,
+                                                              const int32_t* __restrict__ tok_pair,
+                                                              const int32_t* __restrict__ tok_pos,
+                                                              const float* __restrict__ cos_tab,
+                                                              const float* __restrict__ sin_tab, int rows, int heads,
+                                                              int kvh, int ctx, T* __restrict__ kc, T* __restrict__ vc,
+                                                              T* __restrict__ out, int wt) {
+#pragma clang fp contract(off)
+  __shared__ PsgDecodeGqaScratch sc;
+  const int G = heads / kvh, parts = G / GQ;
+  const int unit = blockIdx.x;
+  const int part = unit % parts, rk = unit / parts;
+  const int row = rk / kvh, hk = rk % kvh;
+  const int h0 = hk * G + part * GQ;                           // first query head of this workgroup
+  const int pos = tok_pos[row];
+  if (pos < 0) return;                                         // whole workgroup (uniform)
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int hidden = heads * 128;
+  const int64_t W = (int64_t)(heads + 2 * kvh) * 128;          // row [q | k | v]
+  const int64_t sl = (int64_t)rows * W;                        // split-K slice stride
+  const int64_t cbase = ((int64_t)tok_pair[row] * kvh + hk) * ctx * 128;
+  const float scale = 0.08838834764831845f;                    // 1/sqrt(128)
+  auto rnd = [](float f) { return Act<T>::rnd(f); };
+  const int hf = lane >> 5, c = lane & 31;
+  const int kloc = 2 * (4 * ((c >> 4) & 1) + 2 * ((c >> 3) & 1) + ((c >> 2) & 1)) + hf;
+  typename Act<T>::raw4 kr[8], vr[8];
+  auto load_kv = [&](int b0) {
+    const int kbase = b0 + 16 * wid;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      const int j = kbase + 2 * d + hf;                        // rows >= pos: clamped to row 0 (written whenever pos > 0)
+      const int64_t off = cbase + (int64_t)(j < pos ? j : 0) * 128 + c * 4;
+      kr[d] = Act<T>::ldr4(kc, off);
+      vr[d] = Act<T>::ldr4(vc, off);
+    }
+  };
+  load_kv(0);                                                  // pos == 0: row 0, never used
+  auto ld = [&](const int64_t (&idx)[6], float (&x)[6]) {
+    if (qs > 0) {                                              // split-K partials: all slices of q, k, v in one pass
+      ldn_splits<float, 6>(qkv, qs, sl, idx, x);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) x[e] = Act<T>::rnd(x[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 6; ++e) x[e] = Act<T>::ld(reinterpret_cast<const T*>(qkv), idx[e]);
+    }
+  };
+  auto st = [&](T* base, int64_t i, float v) {
+    if constexpr (sizeof(T) == 4) {
+      if (wt) {                                                // option wt_stores: 4-byte agent-scope store = write-through
+        __hip_atomic_store(reinterpret_cast<unsigned*>(base) + i, __float_as_uint(v), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        return;
+      }
+    }
+    Act<T>::st(base, i, v);
+  };
+  float vn1 = 0.f, vn2 = 0.f;                                  // the new value row (the same for every head of the group)
+  {
+    const int64_t kb = (int64_t)row * W + hidden + (int64_t)hk * 128, vb = kb + (int64_t)kvh * 128;
+    const float cs = cos_tab[pos * 64 + lane], sn = sin_tab[pos * 64 + lane];
+#pragma unroll
+    for (int gi = 0; gi < 2; ++gi) {
+      const int g = wid + 4 * gi;
+      if (g >= GQ) break;
+      const int64_t qb = (int64_t)row * W + (int64_t)(h0 + g) * 128;
+      const int64_t idx[6] = {qb + lane, qb + lane + 64, kb + lane, kb + lane + 64, vb + lane, vb + lane + 64};
+      float x[6];
+      ld(idx, x);
+      float qa, qb_, ka, kb_;
+      psg_rope_pair(x[0], x[1], cs, sn, qa, qb_);
+      psg_rope_pair(x[2], x[3], cs, sn, ka, kb_);
+      qa = rnd(qa); qb_ = rnd(qb_); ka = rnd(ka); kb_ = rnd(kb_);
+      if (part == 0 && g == 0) {
+        st(kc, cbase + (int64_t)pos * 128 + lane, ka);
+        st(kc, cbase + (int64_t)pos * 128 + lane + 64, kb_);
+        st(vc, cbase + (int64_t)pos * 128 + lane, x[4]);
+        st(vc, cbase + (int64_t)pos * 128 + lane + 64, x[5]);
+      }
+      sc.q[g][lane] = qa;
+      sc.q[g][lane + 64] = qb_;
+      const float dot = __builtin_fmaf(qa, ka, qb_ * kb_);
+      const float s_ = wave_sum(dot) * scale;
+      if (lane == 0) sc.snew[g] = s_;
+      vn1 = rnd(x[4]);
+      vn2 = rnd(x[5]);
+    }
+  }
+  __syncthreads();
+  float m_run[GQ], l_run[GQ], o[GQ][4];
+#pragma unroll
+  for (int g = 0; g < GQ; ++g) {
+    m_run[g] = -INFINITY;
+    l_run[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[g][e] = 0.f;
+  }
+  for (int b0 = 0; b0 < pos; b0 += 64) {
+    const int kbase = b0 + 16 * wid;
+    if (kbase >= pos) break;                                   // this wave has no key from here on (uniform)
+    if (b0 > 0) load_kv(b0);
+    float kf[8][4], vf[8][4];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      Act<T>::cv4(kr[d], kf[d]);
+      Act<T>::cv4(vr[d], vf[d]);
+    }
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) {
+      const float4 q4 = *reinterpret_cast<const float4*>(sc.q[g] + c * 4);
+      float pt[8];
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {                            // this lane's 4 dims of key 2 d + hf
+        float acc = q4.x * kf[d][0];
+        acc = __builtin_fmaf(q4.y, kf[d][1], acc);
+        acc = __builtin_fmaf(q4.z, kf[d][2], acc);
+        acc = __builtin_fmaf(q4.w, kf[d][3], acc);
+        pt[d] = acc;
+      }
+      float p4[4], p2[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float keep = (c & 16) ? pt[i + 4] : pt[i], send = (c & 16) ? pt[i] : pt[i + 4];
+        p4[i] = keep + psg_swz_xor<16>(send);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const float keep = (c & 8) ? p4[i + 2] : p4[i], send = (c & 8) ? p4[i] : p4[i + 2];
+        p2[i] = keep + psg_swz_xor<8>(send);
+      }
+      float acc;
+      {
+        const float keep = (c & 4) ? p2[1] : p2[0], send = (c & 4) ? p2[0] : p2[1];
+        acc = keep + psg_swz_xor<4>(send);
+      }
+      acc = acc + psg_swz_xor<2>(acc);
+      acc = acc + psg_swz_xor<1>(acc);
+      const float s = (kbase + kloc < pos) ? acc * scale : -INFINITY;
+      const float m_new = fmaxf(m_run[g], wave_max(s));       // finite: key kbase < pos is this wave's
+      const float alpha = expf(m_run[g] - m_new);
+      const float pj = expf(s - m_new);                        // replicated over the 4 lanes of a key
+      l_run[g] = __builtin_fmaf(wave_sum(pj), 0.25f, l_run[g] * alpha);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[g][e] *= alpha;
+      if ((c & 3) == 0) sc.p[wid][g][kloc] = pj;
+      m_run[g] = m_new;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int g = 0; g < GQ; ++g)
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        const int kl2 = 2 * d + hf;
+        const float pv = kbase + kl2 < pos ? sc.p[wid][g][kl2] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[g][e] = __builtin_fmaf(pv, vf[d][e], o[g][e]);
+      }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int g = 0; g < GQ; ++g) {
+    *reinterpret_cast<float4*>(&sc.o[wid][hf][g][c * 4]) = make_float4(o[g][0], o[g][1], o[g][2], o[g][3]);
+    if (lane == 0) {
+      sc.ml[wid][g][0] = m_run[g];
+      sc.ml[wid][g][1] = l_run[g];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int gi = 0; gi < 2; ++gi) {
+    const int g = wid + 4 * gi;
+    if (g >= GQ) break;
+    const float sn_ = sc.snew[g];
+    float m = sn_;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) m = fmaxf(m, sc.ml[w][g][0]);
+    float e_new = expf(sn_ - m);
+    float l = e_new, r1 = e_new * vn1, r2 = e_new * vn2;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = expf(sc.ml[w][g][0] - m);                // exp(-inf) = 0 for a wave without keys
+      l = __builtin_fmaf(f, sc.ml[w][g][1], l);
+      r1 = __builtin_fmaf(f, sc.o[w][0][g][lane] + sc.o[w][1][g][lane], r1);
+      r2 = __builtin_fmaf(f, sc.o[w][0][g][lane + 64] + sc.o[w][1][g][lane + 64], r2);
+    }
+    const float inv = 1.0f / l;
+    st(out, (int64_t)row * hidden + (int64_t)(h0 + g) * 128 + lane, r1 * inv);
+    st(out, (int64_t)row * hidden + (int64_t)(h0 + g) * 128 + lane + 64, r2 * inv);
+  }
+}
+
+// Workgroups a group's query heads are dealt over (option decode_gqa_qparts, else the rule below).
+static int decode_gqa_parts(const psg_ctx* ctx, int rows, int kv_heads, int G) {
+  int parts = ctx->opt.decode_gqa_qparts;
+  if (parts <= 0) {
+    parts = 1;                                                 // more workgroups than CUs; a part re-reads the cache from L2
+    while (parts < G && (int64_t)rows * kv_heads * parts < ctx->num_cu) parts *= 2;
+  }
+  while (parts > G || G % parts) parts >>= 1;
+  return parts < 1 ? 1 : parts;
+}
+
+extern "C" int psg_decode_attn_gqa(psg_ctx* ctx_, const void* qkv, int qkv_splits, const int32_t* tok_pair,
+                                   const int32_t* tok_pos, const float* rope_cos, const float* rope_sin, int rows,
+                                   int heads, int kv_heads, int head_dim, int ctx, void* k_cache, void* v_cache, void* out,
+                                   int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && qkv && tok_pair && tok_pos && rope_cos && rope_sin && k_cache && v_cache && out, PSG_ERR_INVALID,
+              "psg_decode_attn_gqa: NULL argument");
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_decode_attn_gqa: head_dim=%d (kernel is built for 128)", head_dim);
+  PSG_REQUIRE(qkv_splits >= 0 && qkv_splits <= PSG_MAX_SPLITS, PSG_ERR_INVALID, "psg_decode_attn_gqa: qkv_splits=%d",
+              qkv_splits);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP &&
+                  ((heads / kv_heads) & (heads / kv_heads - 1)) == 0,
+              PSG_ERR_UNSUPPORTED, "psg_decode_attn_gqa: heads=%d kv_heads=%d (group a power of two <= %d)", heads,
+              kv_heads, PSG_GQA_MAX_GROUP);
+  PSG_REQUIRE(rows >= 0, PSG_ERR_INVALID, "psg_decode_attn_gqa: rows=%d", rows);
+  if (rows == 0) return PSG_OK;
+  const int G = heads / kv_heads;
+  const int parts = decode_gqa_parts(ctx_, rows, kv_heads, G);
+  const int GQ = G / parts;
+  const unsigned units = (unsigned)((int64_t)rows * kv_heads * parts);
+  const int wt = ctx_->opt.wt_stores & 1;
+  hipStream_t st = (hipStream_t)stream;
+#define GQA_LAUNCH(N)                                                                                                     \
+  decode_attn_gqa_kernel<T, N><<<units, 256, 0, st>>>(qkv, qkv_splits, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, \
+                                                      kv_heads, ctx, (T*)k_cache, (T*)v_cache, (T*)out, wt)
+  PSG_DISPATCH_DTYPE(dtype, "psg_decode_attn_gqa", {
+    switch (GQ) {
+      case 1: GQA_LAUNCH(1); break;
+      case 2: GQA_LAUNCH(2); break;
+      case 4: GQA_LAUNCH(4); break;
+      default: GQA_LAUNCH(8); break;
+    }
+  });
+#undef GQA_LAUNCH
+  PSG_CHECK_LAUNCH("psg_decode_attn_gqa");
   return PSG_OK;
 }

@@ -456,7 +456,7 @@ struct AfCausal {
 __global__ void __launch_bounds__(256) prefill_attn_f32_kernel(const float* __restrict__ q, const float* __restrict__ kc,
                                                                const float* __restrict__ vc,
                                                                const int32_t* __restrict__ tok_pos, int pairs, int rpp,
-                                                               int heads, int ctx, float* __restrict__ out) {
+                                                               int heads, int kvh, int ctx, float* __restrict__ out) {
   __shared__ int32_t s_keys[4][64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, n = lane & 15;
   const int qtiles = (rpp + 15) >> 4;
@@ -494,7 +494,7 @@ __global__ void __launch_bounds__(256) prefill_attn_f32_kernel(const float* __re
   const int rc = min(row, qt * 16 + seen - 1);
   const float* q1[1] = {q + ((int64_t)p * rpp + rc) * hidden + h * 128};
   float* o1[1] = {orow};
-  const int64_t cbase = ((int64_t)p * heads + h) * ctx * 128;
+  const int64_t cbase = ((int64_t)p * kvh + h / (heads / kvh)) * ctx * 128;   // key / value head of query head h
   const AfCausal mk{pos >= 0 ? pos : 1 << 30};                         // a padding row of a mixed tile: any finite result
   af_tiles<128, 1>(q1, keys, nk, kc + cbase, vc + cbase, 128, 0.08838834764831845f, mk, o1);
   if (pos < 0 && orow) {                                               // padding rows of a mixed tile: zeros, as the scalar kernel
@@ -508,11 +508,12 @@ __global__ void __launch_bounds__(256) prefill_attn_f32_kernel(const float* __re
 }
 
 int psg_prefill_attn_f32_launch(const void* q, const void* kc, const void* vc, const int32_t* tok_pos, int pairs, int rpp,
-                                int heads, int ctx, void* out, hipStream_t st) {
+                                int heads, int kv_heads, int ctx, void* out, hipStream_t st) {
   PSG_REQUIRE(rpp >= 1 && rpp <= 64, PSG_ERR_UNSUPPORTED, "psg_prefill_attn(f32): %d rows per pair (1..64)", rpp);
   const int64_t units = (int64_t)pairs * heads * ((rpp + 15) / 16);
   prefill_attn_f32_kernel<<<(unsigned)((units + 3) / 4), 256, 0, st>>>((const float*)q, (const float*)kc, (const float*)vc,
-                                                                       tok_pos, pairs, rpp, heads, ctx, (float*)out);
+                                                                       tok_pos, pairs, rpp, heads, kv_heads, ctx,
+                                                                       (float*)out);
   PSG_CHECK_LAUNCH("psg_prefill_attn(f32)");
   return PSG_OK;
 }

@@ -47,6 +47,8 @@ struct psg_opts {
                                 // operands through psg_dense_gemm_split (3 products from one staging; 0: the K' = 3K form)
   int decode_persistent = 0;    // fp32 decode steps: one persistent launch per decoder layer (psg_decode_layer) instead of the
                                 // chain of eight launches (bit-identical; Llama-2-7B width, 13..24 rows, 256 CUs)
+  int decode_gqa_qparts = 0;    // grouped-query decode attention: workgroups a group's query heads are dealt over (1, 2, 4, 8;
+                                // each re-reads the key / value head's cache); 0 = the measured rule of psg_decode_attn_gqa
   int llm_w16 = 1;              // fp32 engines: stream projection weights that are fp16 VALUES (verified per tensor) as fp16
   int batch_gemm_bn = 0;        // psg_batch_gemm: forced slab height (256 or 128 weight rows); 0 = the planner's estimate
   int batch_gemm_mode = 0;      // psg_batch_gemm: 1 = slab-aligned slices, 2 = stream-K ranges; 0 = the planner's estimate
@@ -274,6 +276,7 @@ __device__ __forceinline__ float quad_sum(float v) {
 }
 
 #define PSG_MAX_SPLITS 16  // split-K slices a consumer kernel can sum (psg_skinny_gemm_plan stays below)
+#define PSG_GQA_MAX_GROUP 8  // grouped-query attention: query heads per key / value head the *_gqa kernels take
 
 #define PSG_FMIN (-3.402823466e+38f)  // torch.finfo(float32).min, the legacy additive mask value
 

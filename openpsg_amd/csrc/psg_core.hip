@@ -38,7 +38,7 @@ static const OptName kOpts[] = {
     {"ln_half_wave", &psg_opts::ln_half_wave},         {"xattn_poll", &psg_opts::xattn_poll},
     {"xattn_wt", &psg_opts::xattn_wt},
     {"xattn_dynamic", &psg_opts::xattn_dynamic},
-    {"llm_w16", &psg_opts::llm_w16},
+    {"llm_w16", &psg_opts::llm_w16},                   {"decode_gqa_qparts", &psg_opts::decode_gqa_qparts},
     {"batch_gemm_bn", &psg_opts::batch_gemm_bn},       {"decode_batch_gemm", &psg_opts::decode_batch_gemm},
     {"batch_gemm_var", &psg_opts::batch_gemm_var},     {"batch_gemm_mode", &psg_opts::batch_gemm_mode},
     {"batch_gemm_grid", &psg_opts::batch_gemm_grid},

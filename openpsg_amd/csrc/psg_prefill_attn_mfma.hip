@@ -25,13 +25,14 @@ template <typename E>
 __global__ void __launch_bounds__(64)
 prefill_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
                          const uint16_t* __restrict__ vc, const int32_t* __restrict__ tok_pos, int pairs, int S,
-                         int heads, int ctx, uint16_t* __restrict__ out) {
+                         int heads, int kvh, int ctx, uint16_t* __restrict__ out) {
   const int unit = blockIdx.x;
   const int p = unit / heads, h = unit % heads;
   const int lane = threadIdx.x, l31 = lane & 31, hi = lane >> 5;
   const int hidden = heads * 128;
   const int64_t row0 = (int64_t)p * S;
-  const int64_t cbase = ((int64_t)p * heads + h) * ctx * 128;
+  // caches [pair][kvh][ctx][128]: query head h reads key / value head h / (heads / kvh) (kvh == heads: multi-head)
+  const int64_t cbase = ((int64_t)p * kvh + h / (heads / kvh)) * ctx * 128;
   // position of token `lane` of this pair (-1: padding row, also for lane >= S)
   const int mypos = lane < S ? tok_pos[row0 + lane] : -1;
   const unsigned long long valid64 = __ballot(mypos >= 0);
@@ -166,15 +167,21 @@ template <typename E>
 __global__ void __launch_bounds__(64)
 prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* __restrict__ tok_pos,
                               const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, int pairs, int S,
-                              int heads, int ctx, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
+                              int heads, int kvh, int ctx, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
                               uint16_t* __restrict__ out) {
   const int unit = blockIdx.x;
   const int p = unit / heads, h = unit % heads;
   const int lane = threadIdx.x, l31 = lane & 31, hi = lane >> 5;
   const int hidden = heads * 128;
-  const int64_t ld = 3 * (int64_t)hidden;
+  // grouped-query attention: query head h uses key / value head hk of the row [q | k | v] of width (heads + 2 kvh) 128,
+  // and the group's first query head writes that head's cache rows (kvh == heads: the multi-head layout, every head writes)
+  const int G = heads / kvh, hk = h / G;
+  const bool writer = h == hk * G;
+  const int64_t ld = (int64_t)(heads + 2 * kvh) * 128;
+  const int64_t kofs = hidden + (int64_t)(hk - h) * 128;        // K column of head hk relative to Q column of head h
+  const int64_t vcol = hidden + (int64_t)(kvh + hk) * 128;
   const int64_t row0 = (int64_t)p * S;
-  const int64_t cbase = ((int64_t)p * heads + h) * ctx * 128;
+  const int64_t cbase = ((int64_t)p * kvh + hk) * ctx * 128;
   const int mypos = lane < S ? tok_pos[row0 + lane] : -1;
   const unsigned long long valid64 = __ballot(mypos >= 0);
   auto rclamp = [&](int j) { return j < S ? j : S - 1; };
@@ -183,14 +190,14 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
   // first store: as a load -> store loop this was up to 16 dependent round trips at the head of a latency-bound kernel.
   // The stores are unconditional (a conditional one pulls its load down next to it): a piece of a padding row or past
   // the last row is redirected to row 0, whose own data it then rewrites - cache rows of padding tokens stay untouched.
-  if (valid64 & 1ull) {                                        // compact sequences: a pair with any token has row 0
+  if ((valid64 & 1ull) && writer) {                            // compact sequences: a pair with any token has row 0
     uint4 vx[16];
     int rv[16];
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
       const int i = lane + 64 * it, r = i >> 4, c = i & 15;
       rv[it] = (i < S * 16 && ((valid64 >> (r & 63)) & 1ull)) ? r : 0;
-      vx[it] = *reinterpret_cast<const uint4*>(qkv + (row0 + rv[it]) * ld + 2 * hidden + h * 128 + c * 8);
+      vx[it] = *reinterpret_cast<const uint4*>(qkv + (row0 + rv[it]) * ld + vcol + c * 8);
     }
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
@@ -228,8 +235,8 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
       const uint16_t* rp = qkv + (row0 + rr[t]) * ld + h * 128 + 16 * s + 8 * hi;
       qa[s][t].u = *reinterpret_cast<const uint4*>(rp);
       qb[s][t].u = *reinterpret_cast<const uint4*>(rp + 64);
-      ka[s][t].u = *reinterpret_cast<const uint4*>(rp + hidden);
-      kb[s][t].u = *reinterpret_cast<const uint4*>(rp + hidden + 64);
+      ka[s][t].u = *reinterpret_cast<const uint4*>(rp + kofs);
+      kb[s][t].u = *reinterpret_cast<const uint4*>(rp + kofs + 64);
       // position of a real token == its row index inside the pair (compact sequences)
       const float* cp = cos_tab + rr[t] * 64 + 16 * s + 8 * hi;
       const float* sp = sin_tab + rr[t] * 64 + 16 * s + 8 * hi;
@@ -239,7 +246,7 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
       snr[s][t][1] = *reinterpret_cast<const float4*>(sp + 4);
     }
   // V^T fragments: lane (l31, hi) gathers head dim l31 + 32 dt of 8 keys per (key tile, half): 2-byte loads
-  const uint16_t* vbase = qkv + row0 * ld + 2 * hidden + h * 128 + l31;
+  const uint16_t* vbase = qkv + row0 * ld + vcol + l31;
   uint16_t ve[2][2][4][8];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
@@ -275,7 +282,7 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
       qb[s][t] = qb2;
       ka[s][t] = ka2;
       kb[s][t] = kb2;
-      if (rreal[t]) {
+      if (rreal[t] && writer) {
         uint16_t* kp = kc + cbase + (int64_t)rr[t] * 128 + 16 * s + 8 * hi;
         *reinterpret_cast<uint4*>(kp) = ka2.u;
         *reinterpret_cast<uint4*>(kp + 64) = kb2.u;
@@ -367,47 +374,82 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
   }
 }
 
-extern "C" int psg_prefill_attn_rope(psg_ctx* ctx_, const void* qkv, const int32_t* tok_pos, const float* rope_cos,
-                                     const float* rope_sin, int pairs, int rows_per_pair, int heads, int head_dim,
-                                     int ctx, void* k_cache, void* v_cache, void* out, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && qkv && tok_pos && rope_cos && rope_sin && k_cache && v_cache && out, PSG_ERR_INVALID,
-              "psg_prefill_attn_rope: NULL argument");
-  PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "psg_prefill_attn_rope: 16-bit activations only");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_prefill_attn_rope: head_dim=%d (kernel is built for 128)",
-              head_dim);
+static int prefill_attn_rope_launch(const char* name, const void* qkv, const int32_t* tok_pos, const float* rope_cos,
+                                    const float* rope_sin, int pairs, int rows_per_pair, int heads, int kv_heads,
+                                    int head_dim, int ctx, void* k_cache, void* v_cache, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(qkv && tok_pos && rope_cos && rope_sin && k_cache && v_cache && out, PSG_ERR_INVALID, "%s: NULL argument",
+              name);
+  PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "%s: 16-bit activations only", name);
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "%s: head_dim=%d (kernel is built for 128)", name, head_dim);
   PSG_REQUIRE(rows_per_pair >= 1 && rows_per_pair <= 64 && rows_per_pair <= ctx, PSG_ERR_UNSUPPORTED,
-              "psg_prefill_attn_rope: rows_per_pair=%d (1..64, <= ctx=%d)", rows_per_pair, ctx);
-  PSG_REQUIRE(pairs >= 0 && heads > 0, PSG_ERR_INVALID, "psg_prefill_attn_rope: pairs=%d heads=%d", pairs, heads);
+              "%s: rows_per_pair=%d (1..64, <= ctx=%d)", name, rows_per_pair, ctx);
+  PSG_REQUIRE(pairs >= 0 && heads > 0, PSG_ERR_INVALID, "%s: pairs=%d heads=%d", name, pairs, heads);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "%s: heads=%d kv_heads=%d (a divisor, group <= %d)", name, heads, kv_heads, PSG_GQA_MAX_GROUP);
   if (pairs == 0) return PSG_OK;
-  PSG_DISPATCH_E16(dtype, "psg_prefill_attn_rope",
+  PSG_DISPATCH_E16(dtype, name,
                    (prefill_attn_rope_mfma_kernel<E><<<(unsigned)(pairs * heads), 64, 0, (hipStream_t)stream>>>(
-                       (const uint16_t*)qkv, tok_pos, rope_cos, rope_sin, pairs, rows_per_pair, heads, ctx,
+                       (const uint16_t*)qkv, tok_pos, rope_cos, rope_sin, pairs, rows_per_pair, heads, kv_heads, ctx,
                        (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out)));
-  PSG_CHECK_LAUNCH("psg_prefill_attn_rope");
+  PSG_CHECK_LAUNCH(name);
   return PSG_OK;
 }
 
+extern "C" int psg_prefill_attn_rope(psg_ctx* ctx_, const void* qkv, const int32_t* tok_pos, const float* rope_cos,
+                                     const float* rope_sin, int pairs, int rows_per_pair, int heads, int head_dim,
+                                     int ctx, void* k_cache, void* v_cache, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_prefill_attn_rope: NULL argument");
+  return prefill_attn_rope_launch("psg_prefill_attn_rope", qkv, tok_pos, rope_cos, rope_sin, pairs, rows_per_pair, heads,
+                                  heads, head_dim, ctx, k_cache, v_cache, out, dtype, stream);
+}
+
+extern "C" int psg_prefill_attn_rope_gqa(psg_ctx* ctx_, const void* qkv, const int32_t* tok_pos, const float* rope_cos,
+                                         const float* rope_sin, int pairs, int rows_per_pair, int heads, int kv_heads,
+                                         int head_dim, int ctx, void* k_cache, void* v_cache, void* out, int dtype,
+                                         void* stream) {
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_prefill_attn_rope_gqa: NULL argument");
+  return prefill_attn_rope_launch("psg_prefill_attn_rope_gqa", qkv, tok_pos, rope_cos, rope_sin, pairs, rows_per_pair,
+                                  heads, kv_heads, head_dim, ctx, k_cache, v_cache, out, dtype, stream);
+}
+
 int psg_prefill_attn_f32_launch(const void* q, const void* kc, const void* vc, const int32_t* tok_pos, int pairs, int rpp,
-                                int heads, int ctx, void* out, hipStream_t st);
+                                int heads, int kv_heads, int ctx, void* out, hipStream_t st);
+
+static int prefill_attn_launch(const char* name, const void* q, const void* k_cache, const void* v_cache,
+                               const int32_t* tok_pos, int pairs, int rows_per_pair, int heads, int kv_heads, int head_dim,
+                               int ctx, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(q && k_cache && v_cache && tok_pos && out, PSG_ERR_INVALID, "%s: NULL argument", name);
+  PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16 || dtype == PSG_F32, PSG_ERR_UNSUPPORTED, "%s: dtype %d", name, dtype);
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "%s: head_dim=%d (kernel is built for 128)", name, head_dim);
+  PSG_REQUIRE(rows_per_pair >= 1 && rows_per_pair <= 64 && rows_per_pair <= ctx, PSG_ERR_UNSUPPORTED,
+              "%s: rows_per_pair=%d (1..64, <= ctx=%d); longer prompts: psg_llm_attn", name, rows_per_pair, ctx);
+  PSG_REQUIRE(pairs >= 0 && heads > 0, PSG_ERR_INVALID, "%s: pairs=%d heads=%d", name, pairs, heads);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "%s: heads=%d kv_heads=%d (a divisor, group <= %d)", name, heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (pairs == 0) return PSG_OK;
+  if (dtype == PSG_F32)                                      // exact f32 matrix instructions (psg_attn_f32.hip)
+    return psg_prefill_attn_f32_launch(q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, kv_heads, ctx, out,
+                                       (hipStream_t)stream);
+  PSG_DISPATCH_E16(dtype, name,
+                   (prefill_attn_mfma_kernel<E><<<(unsigned)(pairs * heads), 64, 0, (hipStream_t)stream>>>(
+                       (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache, tok_pos, pairs,
+                       rows_per_pair, heads, kv_heads, ctx, (uint16_t*)out)));
+  PSG_CHECK_LAUNCH(name);
+  return PSG_OK;
+}
 
 extern "C" int psg_prefill_attn(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
                                 const int32_t* tok_pos, int pairs, int rows_per_pair, int heads, int head_dim, int ctx,
                                 void* out, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && q && k_cache && v_cache && tok_pos && out, PSG_ERR_INVALID, "psg_prefill_attn: NULL argument");
-  PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16 || dtype == PSG_F32, PSG_ERR_UNSUPPORTED,
-              "psg_prefill_attn: dtype %d", dtype);
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_prefill_attn: head_dim=%d (kernel is built for 128)", head_dim);
-  PSG_REQUIRE(rows_per_pair >= 1 && rows_per_pair <= 64 && rows_per_pair <= ctx, PSG_ERR_UNSUPPORTED,
-              "psg_prefill_attn: rows_per_pair=%d (1..64, <= ctx=%d); longer prompts: psg_llm_attn", rows_per_pair, ctx);
-  PSG_REQUIRE(pairs >= 0 && heads > 0, PSG_ERR_INVALID, "psg_prefill_attn: pairs=%d heads=%d", pairs, heads);
-  if (pairs == 0) return PSG_OK;
-  if (dtype == PSG_F32)                                      // exact f32 matrix instructions (psg_attn_f32.hip)
-    return psg_prefill_attn_f32_launch(q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, ctx, out,
-                                       (hipStream_t)stream);
-  PSG_DISPATCH_E16(dtype, "psg_prefill_attn",
-                   (prefill_attn_mfma_kernel<E><<<(unsigned)(pairs * heads), 64, 0, (hipStream_t)stream>>>(
-                       (const uint16_t*)q, (const uint16_t*)k_cache, (const uint16_t*)v_cache, tok_pos, pairs,
-                       rows_per_pair, heads, ctx, (uint16_t*)out)));
-  PSG_CHECK_LAUNCH("psg_prefill_attn");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_prefill_attn: NULL argument");
+  return prefill_attn_launch("psg_prefill_attn", q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, heads, head_dim,
+                             ctx, out, dtype, stream);
+}
+
+extern "C" int psg_prefill_attn_gqa(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
+                                    const int32_t* tok_pos, int pairs, int rows_per_pair, int heads, int kv_heads,
+                                    int head_dim, int ctx, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_prefill_attn_gqa: NULL argument");
+  return prefill_attn_launch("psg_prefill_attn_gqa", q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, kv_heads,
+                             head_dim, ctx, out, dtype, stream);
 }

@@ -780,7 +780,7 @@ template <typename T>
 __global__ void rope_kvwrite_kernel(const void* __restrict__ qkv, int qs, const int32_t* __restrict__ tok_pair,
                                     const int32_t* __restrict__ tok_pos, const int32_t* __restrict__ rope_pos,
                                     const float* __restrict__ cos_tab,
-                                    const float* __restrict__ sin_tab, int64_t rows, int heads, int ctx,
+                                    const float* __restrict__ sin_tab, int64_t rows, int heads, int kvh, int ctx,
                                     T* __restrict__ q_out, T* __restrict__ kc, T* __restrict__ vc) {
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
@@ -790,25 +790,30 @@ __global__ void rope_kvwrite_kernel(const void* __restrict__ qkv, int qs, const 
   const int pos = tok_pos[row];
   if (pos < 0) return;  // padding row
   const int hidden = heads * 128;
-  const int64_t base = row * 3 * hidden + h * 128;
+  // grouped-query attention (kvh < heads): query head h reads key / value head h / G of the row [q | k | v] of width
+  // (heads + 2 kvh) 128; with kvh == heads this is the [rows][3 hidden] layout of the multi-head model
+  const int G = heads / kvh, hk = h / G;
+  const int64_t W = (int64_t)(heads + 2 * kvh) * 128;
+  const int64_t base = row * W + h * 128, kbase = row * W + hidden + hk * 128, vbase = kbase + (int64_t)kvh * 128;
   // cos/sin(pos * inv_freq) from the caller's table: a precise cosf/sinf per wave cost ~9 us of
   // large-argument range reduction, more than the rest of the kernel
   // rope_pos (optional): rotary position when it differs from the cache slot (training forward: HF numbers the
   // positions over the PADDED sequence, V4:327-330, while the cache holds the compacted tokens)
   const int rp = rope_pos ? rope_pos[row] : pos;
   const float cs = cos_tab[rp * 64 + lane], sn = sin_tab[rp * 64 + lane];
-  const int64_t sl = rows * 3 * hidden;  // split-K slice stride
+  const int64_t sl = rows * W;  // split-K slice stride
   const float q1 = ld1_in<T>(qkv, qs, sl, base + lane), q2 = ld1_in<T>(qkv, qs, sl, base + lane + 64);
-  const float k1 = ld1_in<T>(qkv, qs, sl, base + hidden + lane), k2 = ld1_in<T>(qkv, qs, sl, base + hidden + lane + 64);
-  const float v1 = ld1_in<T>(qkv, qs, sl, base + 2 * hidden + lane);
-  const float v2 = ld1_in<T>(qkv, qs, sl, base + 2 * hidden + lane + 64);
+  const float k1 = ld1_in<T>(qkv, qs, sl, kbase + lane), k2 = ld1_in<T>(qkv, qs, sl, kbase + lane + 64);
+  const float v1 = ld1_in<T>(qkv, qs, sl, vbase + lane);
+  const float v2 = ld1_in<T>(qkv, qs, sl, vbase + lane + 64);
   // q*cos + rotate_half(q)*sin, rotate_half(x) = cat(-x2, x1)   (HF-LL:130-160)
   float qa, qb, ka, kb;
   psg_rope_pair(q1, q2, cs, sn, qa, qb);                    // pinned form (psg_decode_math.h), shared with the decode step
   psg_rope_pair(k1, k2, cs, sn, ka, kb);
   Act<T>::st(q_out, row * hidden + h * 128 + lane, qa);
   Act<T>::st(q_out, row * hidden + h * 128 + lane + 64, qb);
-  const int64_t cbase = (((int64_t)tok_pair[row] * heads + h) * ctx + pos) * 128;
+  if (h != hk * G) return;                                 // the group's first query head writes its key / value row
+  const int64_t cbase = (((int64_t)tok_pair[row] * kvh + hk) * ctx + pos) * 128;
   Act<T>::st(kc, cbase + lane, ka);
   Act<T>::st(kc, cbase + lane + 64, kb);
   Act<T>::st(vc, cbase + lane, v1);
@@ -827,9 +832,29 @@ extern "C" int psg_rope_kvwrite(psg_ctx* ctx_, const void* qkv, int qkv_splits, 
   int64_t waves = rows * heads;
   PSG_DISPATCH_DTYPE(dtype, "psg_rope_kvwrite",
                      (rope_kvwrite_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, ctx, (T*)q_out,
-                         (T*)k_cache, (T*)v_cache)));
+                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, heads, ctx,
+                         (T*)q_out, (T*)k_cache, (T*)v_cache)));
   PSG_CHECK_LAUNCH("psg_rope_kvwrite");
+  return PSG_OK;
+}
+
+extern "C" int psg_rope_kvwrite_gqa(psg_ctx* ctx_, const void* qkv, int qkv_splits, const int32_t* tok_pair,
+                                    const int32_t* tok_pos, const int32_t* rope_pos, const float* rope_cos,
+                                    const float* rope_sin, int64_t rows, int heads, int kv_heads, int head_dim, int ctx,
+                                    void* q_out, void* k_cache, void* v_cache, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && qkv && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache && v_cache, PSG_ERR_INVALID,
+              "psg_rope_kvwrite_gqa: NULL argument");
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite_gqa: head_dim=%d (kernel is built for 128)",
+              head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "psg_rope_kvwrite_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  int64_t waves = rows * heads;
+  PSG_DISPATCH_DTYPE(dtype, "psg_rope_kvwrite_gqa",
+                     (rope_kvwrite_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx,
+                         (T*)q_out, (T*)k_cache, (T*)v_cache)));
+  PSG_CHECK_LAUNCH("psg_rope_kvwrite_gqa");
   return PSG_OK;
 }
 

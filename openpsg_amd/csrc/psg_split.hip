@@ -425,7 +425,7 @@ extern "C" int psg_silu_mul_split(psg_ctx* ctx, const float* gate_up, const floa
 __global__ void rope_kvwrite_scaled_kernel(const float* __restrict__ qkv, const float* __restrict__ rsv,
                                            const float* __restrict__ csv, const int32_t* __restrict__ tok_pair,
                                            const int32_t* __restrict__ tok_pos, const float* __restrict__ cos_tab,
-                                           const float* __restrict__ sin_tab, int64_t rows, int heads, int ctx,
+                                           const float* __restrict__ sin_tab, int64_t rows, int heads, int kvh, int ctx,
                                            float* __restrict__ q_out, float* __restrict__ kc, float* __restrict__ vc,
                                            int slices) {
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -436,24 +436,27 @@ __global__ void rope_kvwrite_scaled_kernel(const float* __restrict__ qkv, const 
   const int pos = tok_pos[row];
   if (pos < 0) return;
   const int hidden = heads * 128;
-  const int c0 = h * 128 + lane;
-  const int64_t base = row * 3 * hidden;
+  const int G = heads / kvh, hk = h / G;                    // grouped-query attention: key / value head of query head h
+  const int64_t W = (int64_t)(heads + 2 * kvh) * 128;       // row [q | k | v]; 3 hidden when kvh == heads
+  const int c0 = h * 128 + lane, ck = hidden + hk * 128 + lane, cv = ck + kvh * 128;
+  const int64_t base = row * W;
   const float rs = rsv[row];
   const float cs = cos_tab[pos * 64 + lane], sn = sin_tab[pos * 64 + lane];
-  const int64_t sstride = rows * 3 * (int64_t)hidden;
+  const int64_t sstride = rows * W;
   auto ld = [&](int col) {
     float v = qkv[base + col];
     for (int sl = 1; sl < slices; ++sl) v += qkv[sl * sstride + base + col];
     return v * (rs * csv[col]);
   };
-  const float q1 = ld(c0), q2 = ld(c0 + 64), k1 = ld(hidden + c0), k2 = ld(hidden + c0 + 64);
-  const float v1 = ld(2 * hidden + c0), v2 = ld(2 * hidden + c0 + 64);
+  const float q1 = ld(c0), q2 = ld(c0 + 64), k1 = ld(ck), k2 = ld(ck + 64);
+  const float v1 = ld(cv), v2 = ld(cv + 64);
   float qa, qb, ka, kb;
   psg_rope_pair(q1, q2, cs, sn, qa, qb);
   psg_rope_pair(k1, k2, cs, sn, ka, kb);
   q_out[row * hidden + c0] = qa;
   q_out[row * hidden + c0 + 64] = qb;
-  const int64_t cbase = (((int64_t)tok_pair[row] * heads + h) * ctx + pos) * 128;
+  if (h != hk * G) return;                                  // the group's first query head writes its key / value row
+  const int64_t cbase = (((int64_t)tok_pair[row] * kvh + hk) * ctx + pos) * 128;
   kc[cbase + lane] = ka;
   kc[cbase + lane + 64] = kb;
   vc[cbase + lane] = v1;
@@ -470,8 +473,30 @@ extern "C" int psg_rope_kvwrite_scaled(psg_ctx* ctx_, const float* qkv, const fl
   if (rows == 0) return PSG_OK;
   const int64_t waves = rows * heads;
   rope_kvwrite_scaled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, ctx, q_out, k_cache, v_cache, slices);
+      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, heads, ctx, q_out, k_cache, v_cache,
+      slices);
   PSG_CHECK_LAUNCH("psg_rope_kvwrite_scaled");
+  return PSG_OK;
+}
+
+extern "C" int psg_rope_kvwrite_scaled_gqa(psg_ctx* ctx_, const float* qkv, const float* row_scale, const float* col_scale,
+                                           const int32_t* tok_pair, const int32_t* tok_pos, const float* rope_cos,
+                                           const float* rope_sin, int slices, int64_t rows, int heads, int kv_heads,
+                                           int head_dim, int ctx, float* q_out, float* k_cache, float* v_cache,
+                                           void* stream) {
+  PSG_REQUIRE(ctx_ && qkv && row_scale && col_scale && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache &&
+                  v_cache, PSG_ERR_INVALID, "psg_rope_kvwrite_scaled_gqa: NULL argument");
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite_scaled_gqa: head_dim=%d (kernel is built for 128)",
+              head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "psg_rope_kvwrite_scaled_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads,
+              PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  const int64_t waves = rows * heads;
+  rope_kvwrite_scaled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx, q_out, k_cache, v_cache,
+      slices);
+  PSG_CHECK_LAUNCH("psg_rope_kvwrite_scaled_gqa");
   return PSG_OK;
 }
 

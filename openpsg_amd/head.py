@@ -286,7 +286,8 @@ class RelationTransformerHeadV4(nn.Module):
         if llm_config is not None:
             llm = llm_config
         elif pretrained_dir:
-            llm = read_hf_llama_config(llm_model_name)                     # the architecture from_pretrained would build
+            # the architecture from_pretrained would build; grouped-query checkpoints (Mistral-7B, ...) included
+            llm = read_hf_llama_config(llm_model_name, grouped_query=True)
         else:
             llm = LlamaConfig(hidden=llm_feature_size, heads=llm_feature_size // 128)
         if llm.hidden != llm_feature_size:
@@ -404,6 +405,10 @@ class RelationTransformerHeadV4(nn.Module):
                    not (".layers." in k and int(k.split(".layers.")[1].split(".")[0]) >= n_layers)]
         if missing:
             raise PsgHipError(f"LLM weights missing {len(missing)} tensors, e.g. {missing[:3]}")
+        wrong = [(k, tuple(weights[k].shape), need[k]) for k in need if k in weights and tuple(weights[k].shape) != need[k]]
+        if wrong:                                       # e.g. a grouped-query checkpoint under a multi-head config
+            raise PsgHipError(f"LLM weights of the wrong shape ({len(wrong)}), e.g. {wrong[:2]} "
+                              f"({self.cfg.llm.heads} query / {self.cfg.llm.n_kv_heads} key-value heads)")
         w = dict(weights)
         w["language_projection.weight"] = self.language_projection.weight.data
         w["language_projection.bias"] = self.language_projection.bias.data
@@ -605,8 +610,10 @@ class RelationTransformerHeadV4(nn.Module):
         steps hold library GEMMs too and nothing may overlap."""
         if self._front_done is not None:
             st.wait_event(self._front_done)
+        rows = max(self.cfg.num_selected, self.max_selected if self.pair_selector == "threshold" else 0)
         if self._decode_done is not None and (self.cfg.num_selected > 32 or (
-                self.pair_selector == "threshold" and self.max_selected > 32) or not self.llm_engine.use_skinny):
+                self.pair_selector == "threshold" and self.max_selected > 32) or not self.llm_engine.use_skinny
+                or self.llm_engine.decode_uses_library(rows)):
             st.wait_event(self._decode_done)
 
     def _enqueue_decode(self, st, rq, names, slot, selected=None, pair_features=None, defer=False):
@@ -1277,7 +1284,7 @@ class RelationTransformerHeadV4(nn.Module):
         eng = self.llm_engine
         # deferring leaves later chunks un-enqueued when the next image's front half starts: only when the decode steps
         # hold own kernels alone (library GEMMs of two streams side by side were seen to hang, `submit`)
-        defer = bool(defer) and eng.use_skinny and sel_in.numel() <= 32
+        defer = bool(defer) and eng.use_skinny and sel_in.numel() <= 32 and not eng.decode_uses_library(sel_in.numel())
         res = eng.generate(X, plen, suppress_eos=self.suppress_eos, return_first_logits=True, slot=slot, gate=gate,
                            defer=defer)
         out = dict(llm_inputs=X[:K], prompt_len=plen[:K])

@@ -11,7 +11,7 @@ Layout decisions (all per-pair results are independent of K and of the other pai
     (== cumsum(mask)-1, probe-verified in SURVEY Appendix B), so the only mask is causal;
   * prefill runs on a fixed [K, 32+T_p] token grid (rows beyond a pair's length carry pos = -1 and
     are skipped by the kernels), decode on [K] rows: static shapes, no host sync, graph-capturable;
-  * KV cache [layers][K, heads, ctx, 128] in the activation dtype;
+  * KV cache [layers][K, kv_heads, ctx, 128] in the activation dtype (kv_heads = heads unless grouped-query);
   * the greedy step (argmax, EOS bookkeeping, next ids, positions) is a device kernel.
 
 Dense projections go through torch (`F.linear` -> hipBLASLt) or, for the decode steps, through the
@@ -228,6 +228,14 @@ class LlamaDecodeEngine:
         m = cfg.llm
         if m.head_dim != 128:
             raise PsgHipError(f"LLM head_dim {m.head_dim} unsupported (kernels are built for 128)")
+        try:
+            m.check_kv_heads()
+        except ValueError as e:
+            raise PsgHipError(f"LLM: {e}") from None
+        # grouped-query attention (kv_heads < heads): the q|k|v rows are (heads + 2 kv_heads) 128 wide, the KV caches hold
+        # kv_heads heads, and the attention launches are the *_gqa entry points; None keeps every multi-head launch as it was
+        self.kv = m.n_kv_heads if m.n_kv_heads != m.heads else None
+        self.qkv_width = m.hidden + 2 * m.kv_dim
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         self.n_layers = m.layers if n_layers is None else n_layers        # llm_truncate_num (V4:101-103)
         f32 = lambda k: weights[k].to(device=self.device, dtype=torch.float32).contiguous()   # noqa: E731
@@ -240,6 +248,11 @@ class LlamaDecodeEngine:
         self.layers = []
         for l in range(self.n_layers):
             p = f"language_model.model.layers.{l}."
+            for n, rows_ in (("q", m.hidden), ("k", m.kv_dim), ("v", m.kv_dim)):
+                shp = tuple(weights[p + f"self_attn.{n}_proj.weight"].shape)
+                if shp != (rows_, m.hidden):
+                    raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
+                                      f"({m.heads} query / {m.n_kv_heads} key-value heads of 128)")
             self.layers.append(dict(
                 wqkv=act(torch.cat([weights[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], 0)),
                 wo=act(weights[p + "self_attn.o_proj.weight"]),
@@ -365,11 +378,14 @@ class LlamaDecodeEngine:
         """The weight-streaming kernel keeps the rows' K slice in LDS beside its weight rings: the fp32 kernel takes 32 rows up
         to K = 11776 and 20 rows up to K = 20480 (every Llama-2-7B / 13B shape at the reference's 20 selected pairs).  A wider
         model falls through to the library GEMM for that projection (exact fp32, not batch-invariant) instead of failing."""
-        key = (x.shape[0], tuple(w.shape), x.dtype)
+        return self._skinny_fits_shape(x.shape[0], w, x.dtype)
+
+    def _skinny_fits_shape(self, rows, w, dtype):
+        key = (rows, tuple(w.shape), dtype)
         ok = self._skinny_ok.get(key)
         if ok is None:
             try:
-                ops.skinny_gemm_plan(x.shape[0], w.shape[0], w.shape[1], x.dtype, self.device)
+                ops.skinny_gemm_plan(rows, w.shape[0], w.shape[1], dtype, self.device)
                 ok = True
             except PsgHipError:
                 ok = False
@@ -420,6 +436,23 @@ class LlamaDecodeEngine:
             return self.linear_split(x, ws, w)
         return F.linear(x, w)
 
+    def decode_uses_library(self, rows) -> bool:
+        """Does a decode step of `rows` rows run a library GEMM?  Above 32 rows, without the weight-streaming kernel, or
+        when a projection's K slice does not fit it at this row count (`_skinny_fits`: fp32 at K = 14336, Mistral-7B's
+        down projection, above 20 rows).  Two library decodes must not run side by side on two streams (`head.submit`)."""
+        rows = int(rows)
+        if not self.use_skinny or rows > 32:
+            return True
+        if self._can_w16(rows):                                # psg_split_gemm_w16 for every projection
+            return False
+        L = self.layers[0] if self.layers else None
+        ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
+        for w in ws:
+            if not (w.shape[0] % 16 == 0 and w.shape[1] % 64 == 0 and w.shape[1] >= 256
+                    and self._skinny_fits_shape(rows, w, self.dtype)):
+                return True
+        return False
+
     def logits(self, h):
         """lm_head.  <= 32 rows: the weight-streaming kernel (fp32 split-K partials, summed inside the greedy step);
         more rows (several images' pairs decoded together): the library GEMM with an fp32 result, so that the greedy
@@ -466,18 +499,19 @@ class LlamaDecodeEngine:
         for l, L in enumerate(self.layers):
             qkv = self.linear(n, L["wqkv"], L.get("wqkv_s"), decode=decode)
             if decode:
-                ops.decode_attn(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, kc[l], vc[l], att)
+                ops.decode_attn(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, kc[l], vc[l], att,
+                                kv_heads=self.kv)
             elif fused_rope and isinstance(qkv, torch.Tensor) and rope_pos is None:
                 ops.prefill_attn_rope(qkv, tok_pos, self.rope, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim,
-                                      ctx_len, kc[l], vc[l], att)
+                                      ctx_len, kc[l], vc[l], att, kv_heads=self.kv)
             else:
                 ops.rope_kvwrite(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
-                                 rope_pos=rope_pos)
+                                 rope_pos=rope_pos, kv_heads=self.kv)
                 if mfma_prefill:
                     ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim,
-                                     ctx_len, att)
+                                     ctx_len, att, kv_heads=self.kv)
                 else:
-                    ops.llm_attn(q, kc[l], vc[l], tok_pair, tok_pos, m.heads, m.head_dim, ctx_len, att)
+                    ops.llm_attn(q, kc[l], vc[l], tok_pair, tok_pos, m.heads, m.head_dim, ctx_len, att, kv_heads=self.kv)
             if keep_rows is not None and l == len(self.layers) - 1:
                 k = keep_rows.numel()
                 att_k, resid_k = torch.empty((k, D), device=self.device, dtype=self.dtype), torch.empty(
@@ -512,8 +546,10 @@ class LlamaDecodeEngine:
         n = None
         for l, L in enumerate(self.layers):
             qkv = ops.Scaled(mm(a3, L["wqkv_s"]), inv_r, L["wqkv_s"][1])
-            ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l])
-            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att)
+            ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
+                                    kv_heads=self.kv)
+            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
+                             kv_heads=self.kv)
             last = l == len(self.layers) - 1
             if keep_rows is not None and last:
                 k = keep_rows.numel()
@@ -562,9 +598,11 @@ class LlamaDecodeEngine:
         att = torch.empty_like(q)
         n = None
         for l, L in enumerate(self.layers):
-            qkv = ops.Scaled(mm(a2, L["wqkv"]), inv_r, one(3 * D))
-            ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l])
-            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att)
+            qkv = ops.Scaled(mm(a2, L["wqkv"]), inv_r, one(self.qkv_width))
+            ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
+                                    kv_heads=self.kv)
+            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
+                             kv_heads=self.kv)
             last = l == len(self.layers) - 1
             if keep_rows is not None and last:
                 k = keep_rows.numel()
@@ -589,6 +627,7 @@ class LlamaDecodeEngine:
     def _can_persist(self, rows, slot):
         m = self.cfg.llm
         return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32
+                and self.kv is None                            # the persistent decoder layer is multi-head only
                 and ops.decode_layer_supported(rows, m.hidden, m.inter, m.heads, self.dtype, self.device))
 
     def _decode_step_persistent(self, st, counters):
@@ -637,7 +676,7 @@ class LlamaDecodeEngine:
         for l, L in enumerate(self.layers):
             qkv = ops.split_gemm_w16(a2, inv, wh[L["wqkv"].data_ptr()])
             ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
-                            st["vc"][l], att)
+                            st["vc"][l], att, kv_heads=self.kv)
             # a row's maximum spans all heads / 11 008 columns: a split launch of its own behind attention and SwiGLU.  Folding
             # it into the producers needs a rendezvous of the row's 32 / 11 workgroups - built and measured in round 6
             # (profiles/r06_split2_rendezvous_ab.txt): inside a graph the launch costs 2.6 / 3.5 us, the rendezvous 9.3 / 3.4
@@ -689,7 +728,7 @@ class LlamaDecodeEngine:
         for l, L in enumerate(self.layers):
             qkv = norm_proj(delta, L["ln1"], L["wqkv"])
             ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"],
-                            st["kc"][l], st["vc"][l], att)
+                            st["kc"][l], st["vc"][l], att, kv_heads=self.kv)
             o = ops.skinny_gemm(att, L["wo"])
             gu = norm_proj(o, L["ln2"], L["wgu"])
             ops.silu_mul(gu, act)
@@ -733,8 +772,8 @@ class LlamaDecodeEngine:
         t = torch.arange(S, device=dev, dtype=torch.int32)[None, :].expand(K, -1)
         tok_pos = torch.where(t < seq_len[:, None].to(torch.int32), t, torch.full_like(t, -1)).reshape(-1).contiguous()
         tok_pair = torch.arange(K, device=dev, dtype=torch.int32)[:, None].expand(-1, S).reshape(-1).contiguous()
-        kc = [torch.empty((K, m.heads, S, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
-        vc = [torch.empty((K, m.heads, S, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
+        kc = [torch.empty((K, m.n_kv_heads, S, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
+        vc = [torch.empty((K, m.n_kv_heads, S, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
         resid = X.reshape(K * S, D).to(self.resid_dtype, copy=True)
         h = self._forward(resid, tok_pair, tok_pos, kc, vc, S, rope_pos=rope_pos.contiguous())
         h_rows = torch.empty((rows.numel(), D), device=dev, dtype=self.dtype)
@@ -877,8 +916,8 @@ class LlamaDecodeEngine:
         tok_pos = torch.where(t < seq_len[:, None], t, torch.full_like(t, -1)).reshape(-1).contiguous()
         tok_pair = torch.arange(K, device=dev, dtype=torch.int32)[:, None].expand(-1, maxlen).reshape(-1).contiguous()
         # no zero fill (650 MB of stores per image for Llama-2-7B): every kernel reads only cache rows that were written
-        kc = [torch.empty((K, m.heads, ctx_len, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
-        vc = [torch.empty((K, m.heads, ctx_len, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
+        kc = [torch.empty((K, m.n_kv_heads, ctx_len, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
+        vc = [torch.empty((K, m.n_kv_heads, ctx_len, m.head_dim), device=dev, dtype=self.dtype) for _ in self.layers]
         resid = X.reshape(K * maxlen, D).to(self.resid_dtype, copy=True)
         last_rows = (torch.arange(K, device=dev, dtype=torch.int32) * maxlen + seq_len - 1).contiguous()
         h_last = self._forward(resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape=(K, maxlen), keep_rows=last_rows)

@@ -432,9 +432,16 @@ def rmsnorm(resid, delta, w, eps, out):
     return out
 
 
-def rope_kvwrite(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, k_cache, v_cache, rope_pos=None):
+def _gqa(heads, kv_heads):
+    """True when `kv_heads` names grouped-query attention (the *_gqa entry points); None / == heads: multi-head."""
+    return kv_heads is not None and int(kv_heads) != int(heads)
+
+
+def rope_kvwrite(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, k_cache, v_cache, rope_pos=None,
+                 kv_heads=None):
     """rope = (cos, sin) fp32 tables [>= ctx_len, head_dim/2].  rope_pos int32 [rows]: rotary positions when they
-    differ from the cache slots (training forward)."""
+    differ from the cache slots (training forward).  kv_heads < heads: grouped-query attention (psg_rope_kvwrite_gqa:
+    qkv rows [q | k | v] of (heads + 2 kv_heads) * head_dim, caches [pairs, kv_heads, ctx, head_dim])."""
     lib, ctx, st = _env(q_out)
     rows = q_out.shape[0]
     qp, qs = _in(qkv, q_out.dtype)
@@ -445,35 +452,61 @@ def rope_kvwrite(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, 
         top = int(rope_pos.max().item()) if rope_pos.numel() else -1
         if top >= rope[0].shape[0]:
             raise PsgHipError(f"rope_kvwrite: rotary position {top} exceeds the {rope[0].shape[0]}-row rotary table")
+    if _gqa(heads, kv_heads):
+        check(lib.psg_rope_kvwrite_gqa(ctx, qp, qs, _p(tok_pair, torch.int32), _p(tok_pos, torch.int32),
+                                       _p(rope_pos, torch.int32), _p(rope[0], torch.float32), _p(rope[1], torch.float32),
+                                       rows, heads, int(kv_heads), head_dim, ctx_len, _p(q_out), _p(k_cache, q_out.dtype),
+                                       _p(v_cache, q_out.dtype), _dt(q_out), st), "psg_rope_kvwrite_gqa")
+        return q_out
     check(lib.psg_rope_kvwrite(ctx, qp, qs, _p(tok_pair, torch.int32), _p(tok_pos, torch.int32),
                                _p(rope_pos, torch.int32), _p(rope[0], torch.float32), _p(rope[1], torch.float32), rows, heads, head_dim, ctx_len, _p(q_out),
                                _p(k_cache, q_out.dtype), _p(v_cache, q_out.dtype), _dt(q_out), st), "psg_rope_kvwrite")
     return q_out
 
 
-def llm_attn(q, k_cache, v_cache, tok_pair, tok_pos, heads, head_dim, ctx_len, out):
+def llm_attn(q, k_cache, v_cache, tok_pair, tok_pos, heads, head_dim, ctx_len, out, kv_heads=None):
     lib, ctx, st = _env(q)
+    if _gqa(heads, kv_heads):
+        check(lib.psg_llm_attn_gqa(ctx, _p(q), _p(k_cache, q.dtype), _p(v_cache, q.dtype), _p(tok_pair, torch.int32),
+                                   _p(tok_pos, torch.int32), q.shape[0], heads, int(kv_heads), head_dim, ctx_len,
+                                   _p(out, q.dtype), _dt(q), st), "psg_llm_attn_gqa")
+        return out
     check(lib.psg_llm_attn(ctx, _p(q), _p(k_cache, q.dtype), _p(v_cache, q.dtype), _p(tok_pair, torch.int32),
                            _p(tok_pos, torch.int32), q.shape[0], heads, head_dim, ctx_len, _p(out, q.dtype), _dt(q),
                            st), "psg_llm_attn")
     return out
 
 
-def prefill_attn(q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, head_dim, ctx_len, out):
-    """Causal attention of a pair-major prompt batch on the matrix cores (bf16 / fp16 / exact fp32, rows_per_pair <= 64)."""
+def prefill_attn(q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, head_dim, ctx_len, out, kv_heads=None):
+    """Causal attention of a pair-major prompt batch on the matrix cores (bf16 / fp16 / exact fp32, rows_per_pair <= 64).
+    kv_heads < heads: grouped-query attention over caches [pairs, kv_heads, ctx, head_dim] (psg_prefill_attn_gqa)."""
     lib, ctx, st = _env(q)
     assert q.shape[0] == pairs * rows_per_pair
+    if _gqa(heads, kv_heads):
+        check(lib.psg_prefill_attn_gqa(ctx, _p(q, name="q"), _p(k_cache, q.dtype), _p(v_cache, q.dtype),
+                                       _p(tok_pos, torch.int32), pairs, rows_per_pair, heads, int(kv_heads), head_dim,
+                                       ctx_len, _p(out, q.dtype), _dt(q), st), "psg_prefill_attn_gqa")
+        return out
     check(lib.psg_prefill_attn(ctx, _p(q, name="q"), _p(k_cache, q.dtype), _p(v_cache, q.dtype),
                                _p(tok_pos, torch.int32), pairs, rows_per_pair, heads, head_dim, ctx_len,
                                _p(out, q.dtype), _dt(q), st), "psg_prefill_attn")
     return out
 
 
-def prefill_attn_rope(qkv, tok_pos, rope, pairs, rows_per_pair, heads, head_dim, ctx_len, k_cache, v_cache, out):
-    """Rotary + KV-cache write + causal attention of a pair-major prompt batch in one launch (bf16 / fp16)."""
+def prefill_attn_rope(qkv, tok_pos, rope, pairs, rows_per_pair, heads, head_dim, ctx_len, k_cache, v_cache, out,
+                      kv_heads=None):
+    """Rotary + KV-cache write + causal attention of a pair-major prompt batch in one launch (bf16 / fp16).
+    kv_heads < heads: grouped-query attention (psg_prefill_attn_rope_gqa)."""
     lib, ctx, st = _env(out)
-    assert qkv.shape == (pairs * rows_per_pair, 3 * heads * head_dim) and rope[0].shape[1] == head_dim // 2
+    kv = heads if kv_heads is None else int(kv_heads)
+    assert qkv.shape == (pairs * rows_per_pair, (heads + 2 * kv) * head_dim) and rope[0].shape[1] == head_dim // 2
     assert rope[0].shape[0] >= rows_per_pair
+    if _gqa(heads, kv_heads):
+        check(lib.psg_prefill_attn_rope_gqa(ctx, _p(qkv, out.dtype, "qkv"), _p(tok_pos, torch.int32),
+                                            _p(rope[0], torch.float32), _p(rope[1], torch.float32), pairs, rows_per_pair,
+                                            heads, kv, head_dim, ctx_len, _p(k_cache, out.dtype), _p(v_cache, out.dtype),
+                                            _p(out), _dt(out), st), "psg_prefill_attn_rope_gqa")
+        return out
     check(lib.psg_prefill_attn_rope(ctx, _p(qkv, out.dtype, "qkv"), _p(tok_pos, torch.int32),
                                     _p(rope[0], torch.float32), _p(rope[1], torch.float32), pairs, rows_per_pair, heads,
                                     head_dim, ctx_len, _p(k_cache, out.dtype), _p(v_cache, out.dtype), _p(out),
@@ -481,11 +514,22 @@ def prefill_attn_rope(qkv, tok_pos, rope, pairs, rows_per_pair, heads, head_dim,
     return out
 
 
-def decode_attn(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, k_cache, v_cache, out):
-    """Fused rotary + KV append + attention for rows that each hold the newest token of their pair."""
+def decode_attn(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, k_cache, v_cache, out, kv_heads=None):
+    """Fused rotary + KV append + attention for rows that each hold the newest token of their pair.
+    kv_heads < heads: grouped-query attention (psg_decode_attn_gqa: one workgroup streams a key / value head's cache once
+    for the query heads of its group)."""
     lib, ctx, st = _env(out)
     qp, qs = _in(qkv, out.dtype)
     assert rope[0].shape[0] >= ctx_len and rope[0].shape[1] == head_dim // 2
+    if _gqa(heads, kv_heads):
+        rows = out.shape[0]
+        assert tuple(qkv.shape)[-2:] == (rows, (heads + 2 * int(kv_heads)) * head_dim)
+        assert k_cache.shape[1] == int(kv_heads) and k_cache.shape[2] >= ctx_len and v_cache.shape == k_cache.shape
+        check(lib.psg_decode_attn_gqa(ctx, qp, qs, _p(tok_pair, torch.int32), _p(tok_pos, torch.int32),
+                                      _p(rope[0], torch.float32), _p(rope[1], torch.float32), rows, heads, int(kv_heads),
+                                      head_dim, ctx_len, _p(k_cache, out.dtype), _p(v_cache, out.dtype), _p(out), _dt(out),
+                                      st), "psg_decode_attn_gqa")
+        return out
     check(lib.psg_decode_attn(ctx, qp, qs, _p(tok_pair, torch.int32), _p(tok_pos, torch.int32),
                               _p(rope[0], torch.float32), _p(rope[1], torch.float32), out.shape[0], heads, head_dim, ctx_len,
                               _p(k_cache, out.dtype), _p(v_cache, out.dtype), _p(out), _dt(out), st), "psg_decode_attn")
@@ -955,11 +999,20 @@ def rmsnorm_split(resid, delta, w, eps, planes=3):
     return out, inv
 
 
-def rope_kvwrite_scaled(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, k_cache, v_cache):
+def rope_kvwrite_scaled(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, k_cache, v_cache, kv_heads=None):
     lib, ctx, st = _env(q_out)
     rows = q_out.shape[0]
-    assert isinstance(qkv, Scaled) and qkv.y.shape[-2:] == (rows, 3 * heads * head_dim)
+    kv = heads if kv_heads is None else int(kv_heads)
+    assert isinstance(qkv, Scaled) and qkv.y.shape[-2:] == (rows, (heads + 2 * kv) * head_dim)
     nsl = 1 if qkv.y.dim() == 2 else qkv.y.shape[0]
+    if _gqa(heads, kv_heads):
+        check(lib.psg_rope_kvwrite_scaled_gqa(ctx, _p(qkv.y), _p(qkv.row_scale, torch.float32),
+                                              _p(qkv.col_scale, torch.float32), _p(tok_pair, torch.int32),
+                                              _p(tok_pos, torch.int32), _p(rope[0], torch.float32),
+                                              _p(rope[1], torch.float32), nsl, rows, heads, kv, head_dim, ctx_len,
+                                              _p(q_out, torch.float32), _p(k_cache, torch.float32),
+                                              _p(v_cache, torch.float32), st), "psg_rope_kvwrite_scaled_gqa")
+        return
     check(lib.psg_rope_kvwrite_scaled(ctx, _p(qkv.y), _p(qkv.row_scale, torch.float32), _p(qkv.col_scale, torch.float32),
                                       _p(tok_pair, torch.int32), _p(tok_pos, torch.int32), _p(rope[0], torch.float32),
                                       _p(rope[1], torch.float32), nsl, rows, heads, head_dim, ctx_len, _p(q_out, torch.float32),

@@ -383,8 +383,17 @@ def llama_teacher_forcing(engine, cfg, X, seq_len, rope_pos, rows):
         n1 = RMSNormFn.apply(x, L["ln1"], m.rms_eps)
         qkv = F.linear(n1, L["wqkv"])
         qh = RopeFn.apply(qkv[..., :D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
-        kh = RopeFn.apply(qkv[..., D:2 * D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
-        att = AttnFn.apply(qh, kh, qkv[..., 2 * D:].contiguous(), keep, m.heads, scale)
+        if m.n_kv_heads == m.heads:
+            kh = RopeFn.apply(qkv[..., D:2 * D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
+            vh = qkv[..., 2 * D:].contiguous()
+        else:
+            # grouped-query attention: rotate the kv_heads key heads, then give every query head its group's key / value
+            # head (repeat_interleave; autograd sums dK / dV over each group)
+            Dk, G = m.kv_dim, m.kv_group
+            kg = RopeFn.apply(qkv[..., D:D + Dk].reshape(K * S, Dk), pos, cos, sin, m.n_kv_heads)
+            kh = kg.view(K, S, m.n_kv_heads, 1, m.head_dim).expand(-1, -1, -1, G, -1).reshape(K, S, D)
+            vh = qkv[..., D + Dk:].reshape(K, S, m.n_kv_heads, 1, m.head_dim).expand(-1, -1, -1, G, -1).reshape(K, S, D)
+        att = AttnFn.apply(qh, kh, vh, keep, m.heads, scale)
         x = x + F.linear(att, L["wo"])
         n2 = RMSNormFn.apply(x, L["ln2"], m.rms_eps)
         act = SiluMulFn.apply(F.linear(n2, L["wgu"]).view(K * S, -1)).view(K, S, -1)

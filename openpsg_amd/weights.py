@@ -76,8 +76,8 @@ def llm_shapes(cfg: PSGConfig) -> dict:
     }
     for l in range(m.layers):
         p = f"language_model.model.layers.{l}."
-        for n in ("q_proj", "k_proj", "v_proj", "o_proj"):
-            s[p + f"self_attn.{n}.weight"] = (m.hidden, m.hidden)
+        for n in ("q_proj", "k_proj", "v_proj", "o_proj"):           # k / v: [kv_heads 128, hidden] (grouped-query)
+            s[p + f"self_attn.{n}.weight"] = (m.kv_dim if n in ("k_proj", "v_proj") else m.hidden, m.hidden)
         s[p + "mlp.gate_proj.weight"] = (m.inter, m.hidden)
         s[p + "mlp.up_proj.weight"] = (m.inter, m.hidden)
         s[p + "mlp.down_proj.weight"] = (m.hidden, m.inter)
@@ -225,33 +225,54 @@ def hf_checkpoint_has_weights(path) -> bool:
                ("model.safetensors.index.json", "model.safetensors", "pytorch_model.bin.index.json", "pytorch_model.bin"))
 
 
-def read_hf_llama_config(path):
+def read_hf_llama_config(path, grouped_query=False):
     """LlamaConfig of the checkpoint directory `path` (its config.json).  Raises PsgHipError for an architecture the
-    decode kernels are not built for (grouped-query attention, head_dim != 128, tied embeddings without an lm_head)."""
+    decode kernels are not built for (head_dim != 128, tied embeddings without an lm_head, rope_scaling, an active sliding
+    window) or that would load but compute something else (biases, an activation other than SiLU).
+    model_type 'llama' and 'mistral' (Mistral's sliding window never applies below the 4096-row rotary table).
+    grouped_query=False refuses grouped-query attention (num_key_value_heads < num_attention_heads) as the multi-head
+    readers did; the head's constructor passes True: groups of up to 8 query heads per key / value head."""
     import json
     import os
     from .config import LlamaConfig
     from ._lib import PsgHipError
     with open(os.path.join(path, "config.json")) as f:
         c = json.load(f)
+    mt = c.get("model_type", "llama")
+    if mt not in ("llama", "mistral"):
+        raise PsgHipError(f"{path}: model_type {mt!r} is not built (llama, mistral)")
     heads = int(c["num_attention_heads"])
     kv = int(c.get("num_key_value_heads") or heads)
-    if kv != heads:
+    if kv != heads and not grouped_query:
         raise PsgHipError(f"{path}: num_key_value_heads={kv} != num_attention_heads={heads} (grouped-query attention is "
                           "not built; the reference's LLM is Llama-2-7b, multi-head)")
     hidden = int(c["hidden_size"])
     if hidden % heads or hidden // heads != 128:
         raise PsgHipError(f"{path}: head_dim {hidden / heads:g} unsupported (kernels are built for 128)")
+    if c.get("head_dim") is not None and int(c["head_dim"]) != 128:
+        raise PsgHipError(f"{path}: head_dim={c['head_dim']} unsupported (kernels are built for 128)")
+    if kv <= 0 or heads % kv or heads // kv > 8 or (heads // kv) & (heads // kv - 1):
+        raise PsgHipError(f"{path}: num_key_value_heads={kv} with {heads} query heads is not built (grouped-query "
+                          "attention takes a power-of-two group of at most 8 query heads per key / value head)")
     if c.get("rope_scaling"):
         raise PsgHipError(f"{path}: rope_scaling={c['rope_scaling']!r} is not built (Llama-2 has none)")
+    sw = c.get("sliding_window")
+    if sw is not None and int(sw) < 4096:
+        raise PsgHipError(f"{path}: sliding_window={sw} is not built (null or >= 4096: a window that never applies)")
+    for key in ("attention_bias", "mlp_bias"):
+        if c.get(key):
+            raise PsgHipError(f"{path}: {key}=true is not built (Llama / Mistral projections have no bias)")
+    act = c.get("hidden_act", "silu")
+    if act != "silu":
+        raise PsgHipError(f"{path}: hidden_act={act!r} is not built (SwiGLU with silu)")
 
     def tok(name, default):
         v = c.get(name, default)
         return int(v[0] if isinstance(v, (list, tuple)) else default if v is None else v)
     return LlamaConfig(hidden=hidden, heads=heads, layers=int(c["num_hidden_layers"]), inter=int(c["intermediate_size"]),
-                       vocab=int(c["vocab_size"]), rms_eps=float(c.get("rms_norm_eps", 1e-5)),
+                       vocab=int(c["vocab_size"]), rms_eps=float(c.get("rms_norm_eps", 1e-6)),
                        rope_theta=float(c.get("rope_theta", 10000.0)), bos=tok("bos_token_id", 1),
-                       eos=tok("eos_token_id", 2), pad=0)
+                       eos=tok("eos_token_id", 2), pad=0, kv_heads=None if kv == heads else kv)
 
 
 def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
@@ -304,4 +325,7 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
             del sd
     if prefix + "lm_head.weight" not in out:
         raise PsgHipError(f"{path}: no lm_head.weight (tied embeddings are not Llama-2's layout)")
+    bias = sorted(k for k in out if k.endswith(".bias"))
+    if bias:
+        raise PsgHipError(f"{path}: bias tensors are not built (Llama / Mistral projections have none): {bias[:3]}")
     return out

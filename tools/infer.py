@@ -58,7 +58,7 @@ def build_head(a, dev):
     if getattr(a, "llm_dir", None):
         # the LLM of a real checkpoint directory; --llm-layers > 0 keeps its first layers (llm_truncate_num, V4:101-103)
         from openpsg_amd.weights import read_hf_llama_config
-        llm = read_hf_llama_config(a.llm_dir)
+        llm = read_hf_llama_config(a.llm_dir, grouped_query=True)      # Llama / Mistral, multi-head or grouped-query
         trunc = a.llm_layers if 0 < a.llm_layers < llm.layers else -1
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
                                          llm_model_name=a.llm_dir, llm_feature_size=llm.hidden, llm_truncate_num=trunc,
