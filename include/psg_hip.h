@@ -69,8 +69,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   600  round 6 (psg_dense_gemm_split added; psg_split_f16x3 order 2)
  *   601  psg_multiclass_head, psg_topk_large(_workspace), psg_train_mlcce_fwd / _bwd added
  *   602  grouped-query attention: psg_rope_kvwrite_gqa, psg_rope_kvwrite_scaled_gqa, psg_llm_attn_gqa, psg_prefill_attn_gqa,
- *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added */
-#define PSG_ABI_VERSION 602
+ *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added
+ *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added */
+#define PSG_ABI_VERSION 603
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -515,6 +516,27 @@ int psg_dense_gemm_split(psg_ctx*, const void* x2, const void* w2, const float* 
 int psg_greedy_step(psg_ctx*, const void* logits, int splits, int K, int vocab, int step, int max_new,
                     int eos, int suppress_token, int32_t* tokens, int32_t* done, int32_t* next_ids, int32_t* tok_pos,
                     const void* embed, int embed_dtype, int hidden, void* x_out, int x_dtype, int dtype, void* stream);
+
+/* ---- relation likelihoods of the LLM stage (rel_score of the LLM triples) -------------------------------
+ * psg_tree_attn: attention of the rows of a token trie over the candidate relation names.  Row r belongs to pair
+ * row_pair[r] and trie node row_node[r] < n_int; its query q[r] (heads x 128, already rotated) attends to the pair's
+ * prompt keys, cache slots [0, prefix_len[pair]), then to slots trie_base + anc[node][d] for d = 0.. up to the first
+ * -1 (the node's ancestors root-side first, the node itself last; anc is [n_int][max_depth]).  Caches
+ * [pairs][kv_heads][ctx][128]; kv_heads divides heads in groups of 1..8.  Softmax in fp32; dtype PSG_F32 is exact fp32
+ * arithmetic, PSG_BF16 / PSG_F16 read 16-bit q / k / v and write 16-bit rows.  trie_base + n_int <= ctx,
+ * trie_base + max_depth <= 1024; a prefix_len above trie_base is read as trie_base.
+ * psg_token_logprobs: for each logit row r ([rows][vocab] of `dtype`, or fp32 split-K partials [splits][rows][vocab]
+ * summed in slice order), lse = log sum exp over the vocabulary in fp32 (one pass, running max and sum), then
+ * out[row_out[r] + c] = logit[child_tok[child_off[n] + c]] - lse for the children c of node n = row_node[r]
+ * (CSR lists child_off[n_nodes + 1], child_tok[n_edges]).  Indices outside out_len are not written; a token outside
+ * the vocabulary gives NaN.  Deterministic: fixed reduction order, no atomics. */
+int psg_tree_attn(psg_ctx*, const void* q, const void* k_cache, const void* v_cache, const int32_t* row_pair,
+                  const int32_t* row_node, const int32_t* prefix_len, const int32_t* anc, int n_int, int max_depth,
+                  int trie_base, int64_t rows, int heads, int kv_heads, int pairs, int head_dim, int ctx, void* out,
+                  int dtype, void* stream);
+int psg_token_logprobs(psg_ctx*, const void* logits, int splits, int64_t rows, int vocab, const int32_t* row_node,
+                       const int64_t* row_out, const int32_t* child_off, const int32_t* child_tok, int n_nodes,
+                       int n_edges, float* out, int64_t out_len, int dtype, void* stream);
 
 /* ---- masked-mean object pooling of the v1-v3 detectors
  * (kings_sgg/models/detectors/openseed_relation.py:453-468):

@@ -276,6 +276,7 @@ __device__ __forceinline__ float quad_sum(float v) {
 }
 
 #define PSG_MAX_SPLITS 16  // split-K slices a consumer kernel can sum (psg_skinny_gemm_plan stays below)
+#define PSG_TREE_MAX_KEYS 1024  // psg_tree_attn: prompt slots + trie depth one row attends to
 #define PSG_GQA_MAX_GROUP 8  // grouped-query attention: query heads per key / value head the *_gqa kernels take
 
 #define PSG_FMIN (-3.402823466e+38f)  // torch.finfo(float32).min, the legacy additive mask value

@@ -1,0 +1,215 @@
+// Relation-likelihood pass of the LLM stage: every relation class of every selected pair scored by the
+// decoder in ONE batched forward over a token trie of the candidate sequences.
+//
+//   psg_tree_attn       attention of trie rows: a row of pair p at trie node i attends to p's prompt keys (cache slots
+//                       [0, prefix_len[p])) and to the slots of i's ancestors and i itself (trie_base + anc[i][d]).
+//                       One wave per (row, query head).  Scores and softmax in fp32 for every storage type; the fp32
+//                       variant is exact fp32 arithmetic (no split, no 16-bit products), like psg_attn_f32.hip.
+//   psg_token_logprobs  per logit row: log-sum-exp in fp32 (one pass, running max and sum), then logit[tok] - lse for
+//                       the row's trie children (CSR lists shared by all pairs).  Fixed reduction order, no atomics.
+#include "psg_common.h"
+
+namespace {
+
+constexpr int TREE_WAVES = 4;
+
+// One wave per (row, head).  Lane j of the score phase computes the full 128-wide dot product of key j (keys j, j + 64,
+// ...; k-ordered fp32 sum), the softmax statistics are wave reductions (butterfly: every lane ends with the same
+// value), and in the output phase lane l owns dims 2l, 2l + 1 and sums the keys in key order.
+template <typename T>
+__global__ void __launch_bounds__(64 * TREE_WAVES)
+    tree_attn_kernel(const T* __restrict__ q, const T* __restrict__ kc, const T* __restrict__ vc,
+                     const int32_t* __restrict__ row_pair, const int32_t* __restrict__ row_node,
+                     const int32_t* __restrict__ prefix_len, const int32_t* __restrict__ anc, int n_int, int max_depth,
+                     int trie_base, int64_t rows, int heads, int kv_heads, int pairs, int ctx, T* __restrict__ out) {
+  __shared__ float s_q[TREE_WAVES][128];
+  __shared__ float s_p[TREE_WAVES][PSG_TREE_MAX_KEYS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t task = (int64_t)blockIdx.x * TREE_WAVES + w;
+  const int64_t r = task / heads;
+  const int h = (int)(task % heads);
+  bool ok = r < rows;
+  int p = 0, nd = 0;
+  if (ok) {
+    p = row_pair[r];
+    nd = row_node[r];
+    ok = p >= 0 && p < pairs && nd >= 0 && nd < n_int;
+  }
+  int plen = 0, depth = 0;
+  if (ok) {
+    plen = prefix_len[p];
+    plen = plen < 0 ? 0 : (plen > trie_base ? trie_base : plen);       // the host keeps trie_base + max_depth <= MAX_KEYS
+    for (; depth < max_depth; ++depth) {
+      const int a = anc[(int64_t)nd * max_depth + depth];
+      if (a < 0 || a >= n_int) break;
+    }
+  }
+  const int nk = plen + depth;
+  const int g = h / (heads / kv_heads);
+  const int64_t hd = (int64_t)heads * 128;
+  const T* kb = kc + ((int64_t)p * kv_heads + g) * ctx * 128;
+  const T* vb = vc + ((int64_t)p * kv_heads + g) * ctx * 128;
+  const int32_t* an = anc + (int64_t)nd * max_depth;
+  if (ok) {
+    s_q[w][2 * lane] = Act<T>::ld(q, r * hd + h * 128 + 2 * lane);
+    s_q[w][2 * lane + 1] = Act<T>::ld(q, r * hd + h * 128 + 2 * lane + 1);
+  }
+  __syncthreads();
+  for (int j = lane; j < nk; j += 64) {
+    const int slot = j < plen ? j : trie_base + an[j - plen];
+    const T* kr = kb + (int64_t)slot * 128;
+    float acc = 0.f;
+#pragma unroll 4
+    for (int d = 0; d < 128; d += 4) {
+      float kv4[4];
+      Act<T>::ld4(kr, d, kv4);
+      acc = fmaf(s_q[w][d], kv4[0], acc);
+      acc = fmaf(s_q[w][d + 1], kv4[1], acc);
+      acc = fmaf(s_q[w][d + 2], kv4[2], acc);
+      acc = fmaf(s_q[w][d + 3], kv4[3], acc);
+    }
+    s_p[w][j] = acc * 0.08838834764831845f;                             // 1 / sqrt(128)
+  }
+  __syncthreads();
+  float m = -INFINITY;
+  for (int j = lane; j < nk; j += 64) m = fmaxf(m, s_p[w][j]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float sum = 0.f;
+  for (int j = lane; j < nk; j += 64) {
+    const float e = expf(s_p[w][j] - m);
+    s_p[w][j] = e;
+    sum += e;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  __syncthreads();
+  if (!ok) return;
+  float a0 = 0.f, a1 = 0.f;
+  for (int j = 0; j < nk; ++j) {
+    const int slot = j < plen ? j : trie_base + an[j - plen];
+    const float pj = s_p[w][j] / sum;                                   // softmax first, then P.V (HF-LL:208-210)
+    const T* vr = vb + (int64_t)slot * 128;
+    a0 = fmaf(pj, Act<T>::ld(vr, 2 * lane), a0);
+    a1 = fmaf(pj, Act<T>::ld(vr, 2 * lane + 1), a1);
+  }
+  Act<T>::st(out, r * hd + h * 128 + 2 * lane, a0);
+  Act<T>::st(out, r * hd + h * 128 + 2 * lane + 1, a1);
+}
+
+__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {
+  if (s2 == 0.f) return;
+  if (s == 0.f) { m = m2; s = s2; return; }
+  const float mn = fmaxf(m, m2);
+  s = s * expf(m - mn) + s2 * expf(m2 - mn);
+  m = mn;
+}
+
+template <typename T>
+__device__ __forceinline__ float logit_at(const void* logits, int S, int64_t slice, int64_t i) {
+  if (S <= 0) return Act<T>::ld(reinterpret_cast<const T*>(logits), i);
+  const float* p = reinterpret_cast<const float*>(logits);
+  float a = p[i];
+  for (int s = 1; s < S; ++s) a += p[(int64_t)s * slice + i];        // slice order, as psg_greedy_step sums them
+  return a;
+}
+
+// One workgroup per logit row.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    token_logprobs_kernel(const void* __restrict__ logits, int S, int64_t rows, int vocab,
+                          const int32_t* __restrict__ row_node, const int64_t* __restrict__ row_out,
+                          const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_tok, int n_nodes,
+                          int n_edges, float* __restrict__ out, int64_t out_len) {
+  __shared__ float s_m[4], s_s[4], s_lse;
+  const int64_t r = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t slice = rows * vocab;
+  const int64_t base = r * vocab;
+  float m = -INFINITY, s = 0.f;
+  for (int v = tid; v < vocab; v += 256) {
+    const float x = logit_at<T>(logits, S, slice, base + v);
+    if (x == -INFINITY) continue;                                       // exp(-inf) = 0; keeps a -inf first entry from NaN
+    if (x > m) {
+      s = s * expf(m - x) + 1.f;                                        // (s == 0 on the first element: 0 * 0)
+      m = x;
+    } else {
+      s += expf(x - m);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_combine(m, s, m2, s2);
+  }
+  if (lane == 0) { s_m[w] = m; s_s[w] = s; }
+  __syncthreads();
+  if (tid == 0) {
+    float mm = s_m[0], ss = s_s[0];
+    for (int i = 1; i < 4; ++i) lse_combine(mm, ss, s_m[i], s_s[i]);
+    s_lse = mm + logf(ss);
+  }
+  __syncthreads();
+  const int nd = row_node[r];
+  if (nd < 0 || nd >= n_nodes) return;
+  const int c0 = child_off[nd], c1 = child_off[nd + 1];
+  const int64_t o0 = row_out[r];
+  const float lse = s_lse;
+  for (int c = c0 + tid; c < c1; c += 256) {
+    if (c < 0 || c >= n_edges) continue;
+    const int64_t oi = o0 + (c - c0);
+    if (oi < 0 || oi >= out_len) continue;
+    const int tok = child_tok[c];
+    out[oi] = (tok >= 0 && tok < vocab) ? logit_at<T>(logits, S, slice, base + tok) - lse : NAN;
+  }
+}
+
+}  // namespace
+
+extern "C" int psg_tree_attn(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
+                             const int32_t* row_pair, const int32_t* row_node, const int32_t* prefix_len,
+                             const int32_t* anc, int n_int, int max_depth, int trie_base, int64_t rows, int heads,
+                             int kv_heads, int pairs, int head_dim, int ctx, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && q && k_cache && v_cache && row_pair && row_node && prefix_len && anc && out, PSG_ERR_INVALID,
+              "psg_tree_attn: NULL argument");
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_tree_attn: head_dim=%d (kernel is built for 128)", head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "psg_tree_attn: heads=%d kv_heads=%d (groups of 1..%d query heads per key / value head)", heads, kv_heads,
+              PSG_GQA_MAX_GROUP);
+  PSG_REQUIRE(n_int > 0 && max_depth > 0 && trie_base >= 0 && pairs > 0 && rows >= 0, PSG_ERR_INVALID,
+              "psg_tree_attn: n_int=%d max_depth=%d trie_base=%d pairs=%d rows=%lld", n_int, max_depth, trie_base, pairs,
+              (long long)rows);
+  PSG_REQUIRE((int64_t)trie_base + n_int <= ctx, PSG_ERR_INVALID,
+              "psg_tree_attn: trie slots [%d, %d) exceed the %d-slot cache", trie_base, trie_base + n_int, ctx);
+  PSG_REQUIRE(trie_base + max_depth <= PSG_TREE_MAX_KEYS, PSG_ERR_UNSUPPORTED,
+              "psg_tree_attn: %d prompt slots + depth %d exceed %d keys per row", trie_base, max_depth, PSG_TREE_MAX_KEYS);
+  if (rows == 0) return PSG_OK;
+  const int64_t tasks = rows * heads;
+  const unsigned grid = (unsigned)((tasks + TREE_WAVES - 1) / TREE_WAVES);
+  PSG_DISPATCH_DTYPE(dtype, "psg_tree_attn",
+                     (tree_attn_kernel<T><<<grid, 64 * TREE_WAVES, 0, (hipStream_t)stream>>>(
+                         (const T*)q, (const T*)k_cache, (const T*)v_cache, row_pair, row_node, prefix_len, anc, n_int,
+                         max_depth, trie_base, rows, heads, kv_heads, pairs, ctx, (T*)out)));
+  PSG_CHECK_LAUNCH("psg_tree_attn");
+  return PSG_OK;
+}
+
+extern "C" int psg_token_logprobs(psg_ctx* ctx_, const void* logits, int splits, int64_t rows, int vocab,
+                                  const int32_t* row_node, const int64_t* row_out, const int32_t* child_off,
+                                  const int32_t* child_tok, int n_nodes, int n_edges, float* out, int64_t out_len,
+                                  int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && logits && row_node && row_out && child_off && child_tok && out, PSG_ERR_INVALID,
+              "psg_token_logprobs: NULL argument");
+  PSG_REQUIRE(rows >= 0 && vocab > 0 && n_nodes > 0 && n_edges >= 0 && out_len >= 0 && splits >= 0 && splits <= 64,
+              PSG_ERR_INVALID, "psg_token_logprobs: rows=%lld vocab=%d n_nodes=%d n_edges=%d splits=%d", (long long)rows,
+              vocab, n_nodes, n_edges, splits);
+  if (rows == 0) return PSG_OK;
+  PSG_REQUIRE(rows <= 0x7fffffff, PSG_ERR_UNSUPPORTED, "psg_token_logprobs: %lld rows", (long long)rows);
+  if (splits > 0) dtype = PSG_F32;                                      // split-K partials are fp32 slices
+  PSG_DISPATCH_DTYPE(dtype, "psg_token_logprobs",
+                     (token_logprobs_kernel<T><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(
+                         logits, splits, rows, vocab, row_node, row_out, child_off, child_tok, n_nodes, n_edges, out,
+                         out_len)));
+  PSG_CHECK_LAUNCH("psg_token_logprobs");
+  return PSG_OK;
+}

@@ -86,6 +86,9 @@ class HipBackend:
             # the multiclass scores of all pairs would need an all-gather of [pairs, R] and a global top-k merge
             raise PsgHipError(f"pair-sharded pipelines run rel_cls_type='binary' heads only, not {head.rel_cls_type!r} "
                               "(the multiclass head runs on one GPU: head.forward / submit / forward_batch)")
+        if getattr(head, "llm_rel_scores", "constant") != "constant":
+            raise PsgHipError("pair-sharded pipelines score LLM triples with the constant 1 only; "
+                              "llm_rel_scores='likelihood' runs on one GPU (head.forward / submit)")
         self.head = head
         # the same object truncation (V4:136) and selector options as head.forward, so sharded == single GPU
         self._ids = lambda scene: [int(i) for i in scene["object_id_list"][:head.max_object_num]]

@@ -33,6 +33,7 @@ from .config import REL_CLS_TYPES, LlamaConfig, PSGConfig, QFormerConfig
 from .llm import LlamaDecodeEngine
 from .qformer import RelationQueryEngine
 from .registry import HEADS
+from .rel_scores import MAX_RANKED_TRIPLES, assemble, build_relation_trie
 from .tokenizers import WordTokenizer
 from .weights import (head_shapes, hf_checkpoint_has_weights, is_hf_checkpoint_dir, llm_shapes, read_hf_llama_config,
                       read_hf_llama_weights)
@@ -74,12 +75,13 @@ class _Pending:
             if out["tokens"] is not None:
                 out["tokens_host"] = out["tokens"].cpu().numpy()           # waits for this stream's work only
                 out["selected_host"] = sel.cpu().numpy()
+                if out.get("rel_logscores") is not None:
+                    out["logscores_host"] = out["rel_logscores"].cpu().numpy()
             if h.has_multiclass:
                 out["mc_host"] = self.rq["mc_topk"].cpu().numpy()
         self.rq.update(out)
         h.last = self.rq
-        rel_pred, rel_score = ([], []) if out["tokens_host"] is None else h.parse(out["tokens_host"], out["selected_host"],
-                                                                                 self.N)
+        rel_pred, rel_score = ([], []) if out["tokens_host"] is None else h._parse_out(out, self.N)
         mc_pred, mc_score = h.parse_multiclass(out.get("mc_host"), self.N)
         self.rq = self.out = self.inputs = None
         self._result = dict(rel_pred=rel_pred + mc_pred, rel_score=rel_score + mc_score)
@@ -223,10 +225,29 @@ class RelationTransformerHeadV4(nn.Module):
                  train_losses_without_grad=False,   # forward() in training mode returns the two losses WITHOUT a graph
                                                # (forward_train); off: it raises, so that an mmdet-style loop cannot sum
                                                # them and silently train nothing in this head
+                 llm_rel_scores='constant',    # rel_score of the LLM triples: 'constant' = 1 each (V4:326) | 'likelihood' =
+                                               # the decoder's probability of emitting the relation name and stopping
+                 num_llm_ranked_triples=0,     # 'likelihood': the N best remaining (pair, class) triples of the selected
+                                               # pairs follow the generated ones (at most 4096)
                  **kwargs):
         super().__init__()
         if rel_cls_type not in REL_CLS_TYPES:
             raise ValueError(f"rel_cls_type must be one of {REL_CLS_TYPES} (V4:31, 91-95), got {rel_cls_type!r}")
+        if llm_rel_scores not in ("constant", "likelihood"):
+            raise PsgHipError(f"llm_rel_scores must be 'constant' or 'likelihood', got {llm_rel_scores!r}")
+        self.llm_rel_scores = llm_rel_scores
+        self.num_llm_ranked_triples = int(num_llm_ranked_triples)
+        if not 0 <= self.num_llm_ranked_triples <= MAX_RANKED_TRIPLES:
+            raise PsgHipError(f"num_llm_ranked_triples must be in 0..{MAX_RANKED_TRIPLES}, got {num_llm_ranked_triples}")
+        if self.num_llm_ranked_triples > 0 and llm_rel_scores != "likelihood":
+            raise PsgHipError("num_llm_ranked_triples > 0 ranks (pair, class) triples by their decoder likelihood: it needs "
+                              "llm_rel_scores='likelihood'")
+        if llm_rel_scores == "likelihood" and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_rel_scores='likelihood' scores the LLM triples; rel_cls_type={rel_cls_type!r} has no "
+                              "LLM stage")
+        if llm_rel_scores == "likelihood" and not implicit_bos:
+            raise PsgHipError("llm_rel_scores='likelihood' needs implicit_bos=True: a candidate is what generate emits after "
+                              "the prompt, and with implicit_bos=False parse reads nothing from a text without '<s>'")
         # 'binary': existence head -> top-20 pairs -> LLM decode (V4:206-209, 235-237).  'multiclass' in the type: one
         # sigmoid score per (pair, relation class) from multiclass_rel_cls_pred, the diagonal zeroed, the top
         # `num_multiclass_triples` (pair, class) scores returned behind the LLM triples (V4:238-257, 355-356)
@@ -332,6 +353,9 @@ class RelationTransformerHeadV4(nn.Module):
         else:
             self.relation_qformer_tokenizer, self.llm_tokenizer = tokenizers
         self.llm_tokenizer.pad_token = self.llm_tokenizer.unk_token        # V4:105
+        self._rel_trie = self._rel_trie_tok = None
+        if self.llm_rel_scores == "likelihood":
+            self.relation_trie()                                            # checks the candidates now: fails early
         self.last = {}
         self._gather_cache = {}
         # Two slots whose streams share a hardware queue run one after the other (67.8 instead of 57 ms per image), and
@@ -544,7 +568,7 @@ class RelationTransformerHeadV4(nn.Module):
             out["mc_host"] = rq["mc_topk"].cpu().numpy()
         rq.update(out)                                        # keeps a lazy rq lazy (`hidden` on demand)
         self.last = rq
-        rel_pred, rel_score = self.parse(out["tokens_host"], out["selected_host"], N) if is_generation else ([], [])
+        rel_pred, rel_score = self._parse_out(out, N) if is_generation else ([], [])
         mc_pred, mc_score = self.parse_multiclass(out.get("mc_host"), N)
         return dict(rel_pred=rel_pred + mc_pred, rel_score=rel_score + mc_score)   # V4:355-356
 
@@ -903,6 +927,9 @@ class RelationTransformerHeadV4(nn.Module):
         tools/inflight_stress.py batch.)"""
         if self.training:
             raise NotImplementedError("training branch (V4:114-133, 360-406) is out of scope of this build")
+        if self.llm_rel_scores != "constant":
+            raise PsgHipError("forward_batch scores LLM triples with the constant 1 only; llm_rel_scores='likelihood' runs "
+                              "through forward / submit")
         st, gslot = torch.cuda.current_stream(self.device), 0
         items, results, tokens, mcs = [], [None] * len(batch), None, {}
         with torch.cuda.stream(st):
@@ -1285,20 +1312,31 @@ class RelationTransformerHeadV4(nn.Module):
         # deferring leaves later chunks un-enqueued when the next image's front half starts: only when the decode steps
         # hold own kernels alone (library GEMMs of two streams side by side were seen to hang, `submit`)
         defer = bool(defer) and eng.use_skinny and sel_in.numel() <= 32 and not eng.decode_uses_library(sel_in.numel())
+        trie = self.relation_trie() if self.llm_rel_scores == "likelihood" else None
         res = eng.generate(X, plen, suppress_eos=self.suppress_eos, return_first_logits=True, slot=slot, gate=gate,
-                           defer=defer)
+                           defer=defer, trie=trie)
         out = dict(llm_inputs=X[:K], prompt_len=plen[:K])
 
         def finish():
-            tokens, first_logits = res() if defer else res
-            out["tokens"], out["first_logits"] = tokens[:K], first_logits[:K]
+            r = res() if defer else res
+            out["tokens"], out["first_logits"] = r[0][:K], r[1][:K]
+            if trie is not None:                                # padding copies of the threshold selector are cut here
+                out["rel_logscores"] = r[2][:K]
         if defer:
             out["_finish"] = finish
             return out
         finish()
         if to_host:
             out["tokens_host"], out["selected_host"] = out["tokens"].cpu().numpy(), sel.cpu().numpy()
+            if trie is not None:
+                out["logscores_host"] = out["rel_logscores"].cpu().numpy()
         return out
+
+    def _parse_out(self, out, N):
+        """rel_pred / rel_score of the LLM stage from a decode's host copies."""
+        if self.llm_rel_scores == "likelihood":
+            return self.parse_scored(out["tokens_host"], out["selected_host"], N, out["logscores_host"])
+        return self.parse(out["tokens_host"], out["selected_host"], N)
 
     def parse(self, tokens_host, selected_host, object_num):
         """A10 (V4:313-326): decode -> text between '<s>' and '</s>' -> names split on two spaces.
@@ -1312,24 +1350,61 @@ class RelationTransformerHeadV4(nn.Module):
         as if it followed one.  `implicit_bos=False` keeps the literal V4:315 behaviour
         (IndexError unless on_parse_error='skip')."""
         rel_pred, rel_score = [], []
+        for _, t in self._parse_pairs(tokens_host, selected_host, object_num):
+            rel_pred.append(t)
+            rel_score.append(1)
+        return rel_pred, rel_score
+
+    def _relation_names(self, seq):
+        """Class indices (into relation_categories) that V4:313-321 reads from one generated id sequence, in text order;
+        None when the text is skipped (no '<s>', implicit_bos=False, on_parse_error='skip')."""
+        text = self.llm_tokenizer.batch_decode([seq])[0]
+        parts = text.split('<s>')
+        if len(parts) > 1:
+            body = parts[1]
+        elif self.implicit_bos:
+            body = parts[0]
+        elif self.on_parse_error == "raise":
+            raise IndexError("no '<s>' in the generated text (V4:315-316); construct the head with "
+                             "implicit_bos=True or on_parse_error='skip'")
+        else:
+            return None
+        pred = body.split('</s>')[0].strip()
+        return [relation_categories.index(name) for name in pred.split('  ') if name in relation_categories]
+
+    def _parse_pairs(self, tokens_host, selected_host, object_num):
+        """[(selection rank k, [sub, obj, rel])] of V4:313-326, new triples only, in parse order."""
+        out, seen = [], []
         for k, si in enumerate(selected_host.tolist()):
             seq = [int(t) for t in tokens_host[k] if t >= 0]
-            text = self.llm_tokenizer.batch_decode([seq])[0]
-            parts = text.split('<s>')
-            if len(parts) > 1:
-                body = parts[1]
-            elif self.implicit_bos:
-                body = parts[0]
-            elif self.on_parse_error == "raise":
-                raise IndexError("no '<s>' in the generated text (V4:315-316); construct the head with "
-                                 "implicit_bos=True or on_parse_error='skip'")
-            else:
-                continue
-            pred = body.split('</s>')[0].strip()
-            for name in pred.split('  '):
-                if name in relation_categories:
-                    t = [si // object_num, si % object_num, relation_categories.index(name)]
-                    if t not in rel_pred:
-                        rel_pred.append(t)
-                        rel_score.append(1)
-        return rel_pred, rel_score
+            rels = self._relation_names(seq)
+            for r in rels or ():
+                t = [si // object_num, si % object_num, r]
+                if t not in seen:
+                    seen.append(t)
+                    out.append((k, t))
+        return out
+
+    def parse_scored(self, tokens_host, selected_host, object_num, log_scores):
+        """`parse` with llm_rel_scores='likelihood': the generated triples scored s(p, r) = exp(log_scores[k, r]), then
+        the num_llm_ranked_triples best remaining (pair, class) triples (rel_scores.assemble)."""
+        return assemble(self._parse_pairs(tokens_host, selected_host, object_num), log_scores, selected_host, object_num,
+                        self.num_llm_ranked_triples)
+
+    def relation_trie(self):
+        """The token trie of the relation classes' candidate sequences under the current LLM tokenizer (rel_scores.py),
+        built and checked at construction and again whenever `llm_tokenizer` is replaced."""
+        if self._rel_trie is None or self._rel_trie_tok is not self.llm_tokenizer:
+            tok = self.llm_tokenizer
+
+            def parse_classes(ids):
+                saved = self.on_parse_error
+                try:
+                    self.on_parse_error = "skip"
+                    return set(self._relation_names(list(ids)) or ())
+                finally:
+                    self.on_parse_error = saved
+            self._rel_trie = build_relation_trie(tok, list(relation_categories), self.cfg.llm.eos, self.cfg.llm.vocab,
+                                                 parse_classes)
+            self._rel_trie_tok = tok
+        return self._rel_trie

@@ -470,9 +470,21 @@ class LlamaDecodeEngine:
             return torch.mm(h, self.lm_head.t(), out_dtype=torch.float32)
         return out.float()
 
+    def _lm_head_f32(self, h):
+        """lm_head of 16-bit rows with an fp32 result (the values `logits` hands the greedy step above 32 rows)."""
+        if self._mm_out_dtype is None:
+            try:
+                torch.mm(h[:1], self.lm_head[:16].t(), out_dtype=torch.float32)
+                self._mm_out_dtype = True
+            except (TypeError, RuntimeError):
+                self._mm_out_dtype = False
+        if self._mm_out_dtype:
+            return torch.mm(h, self.lm_head.t(), out_dtype=torch.float32)
+        return F.linear(h, self.lm_head).float()
+
     # ---- one pass over `rows` token rows -------------------------------------------------------
     def _forward(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, decode=False, prefill_shape=None, rope_pos=None,
-                 keep_rows=None):
+                 keep_rows=None, tree=None):
         """resid [rows, D] is updated in place (residual stream); returns final-norm hidden [rows, D].
         decode=True: every row is the newest token of its pair -> fused rotary + KV append + attention.
         prefill_shape=(pairs, rows_per_pair): the rows are a pair-major prompt batch -> matrix-core attention
@@ -480,7 +492,9 @@ class LlamaDecodeEngine:
         rope_pos int32 [rows]: rotary positions when they differ from the cache slots `tok_pos` (training).
         keep_rows int32 [k]: the caller reads only these rows of the result (prompt pass: the last token of every
         pair).  The last layer then writes K/V for every row (the cache needs them) and runs everything behind the
-        attention - output projection, norms, MLP - on those k rows only; returns [k, D]."""
+        attention - output projection, norms, MLP - on those k rows only; returns [k, D].
+        tree (the relation-likelihood pass, `_rank_pass`): dict(row_node, prefix_len, anc, base, rope_bound) - the rows are
+        token-trie nodes whose attention is psg_tree_attn over their pair's prompt slots and their trie ancestors."""
         m = self.cfg.llm
         rows, D = resid.shape
         if (self.prefill_split and self.fuse_split and not self.row_invariant and not decode and prefill_shape is not None
@@ -504,6 +518,11 @@ class LlamaDecodeEngine:
             elif fused_rope and isinstance(qkv, torch.Tensor) and rope_pos is None:
                 ops.prefill_attn_rope(qkv, tok_pos, self.rope, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim,
                                       ctx_len, kc[l], vc[l], att, kv_heads=self.kv)
+            elif tree is not None:
+                ops.rope_kvwrite(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
+                                 rope_pos=rope_pos, kv_heads=self.kv, rope_pos_bound=tree["rope_bound"])
+                ops.tree_attn(q, kc[l], vc[l], tok_pair, tree["row_node"], tree["prefix_len"], tree["anc"], tree["base"],
+                              m.heads, m.head_dim, ctx_len, att, kv_heads=self.kv)
             else:
                 ops.rope_kvwrite(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
                                  rope_pos=rope_pos, kv_heads=self.kv)
@@ -782,7 +801,7 @@ class LlamaDecodeEngine:
 
     @torch.no_grad()
     def generate(self, X, prompt_len, max_new_tokens=None, suppress_eos=False, return_first_logits=False, slot=0,
-                 gate=None, defer=False):
+                 gate=None, defer=False, trie=None):
         """Batched greedy decode.  X [K, 32+Tp, D]; prompt_len int32 [K] (# of prompt tokens).
         Returns tokens int32 [K, max_new] (device; -1 after a pair's EOS) and optionally the
         first-step logits [K, vocab].
@@ -801,16 +820,20 @@ class LlamaDecodeEngine:
         defer (natural EOS only): enqueue the prompt pass and the first chunk of steps WITHOUT a host wait and return a
         callable instead of the results; calling it replays the remaining chunks (with their "all done?" read-backs) and
         returns what the direct call returns.  `head.submit` hands it to the pending result, so that `result()` stays
-        the only host wait of an image in flight."""
+        the only host wait of an image in flight.
+        trie (`rel_scores.RelationTrie`): the relation-likelihood pass runs inside the prompt-pass graph (`_rank_pass`)
+        and the result gains a third entry, the log scores [K, R] (fp32) - returned as (tokens, first_logits, scores)."""
         max_new = self.cfg.max_new_tokens if max_new_tokens is None else max_new_tokens
         if not self.use_graph:
-            outs = self._finish(self._generate_eager(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot),
-                                return_first_logits)
+            outs = self._finish(self._generate_eager(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot,
+                                                     trie=trie), return_first_logits)
             return (lambda: outs) if defer else outs
         chunk = 0 if suppress_eos else int(self.early_exit_chunk)
         split = gate is not None and max_new > 1
         key = (tuple(X.shape), max_new, bool(suppress_eos), bool(return_first_logits), chunk, int(slot), split,
                bool(self.row_invariant))
+        if trie is not None:
+            key = key + (trie.key,)
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)
@@ -826,7 +849,7 @@ class LlamaDecodeEngine:
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):                      # warm-up: lazy library init must not be captured
-                self._generate_eager(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot)
+                self._generate_eager(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
             if self.persistent_layer:
@@ -840,7 +863,7 @@ class LlamaDecodeEngine:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=graphs[0][0].pool() if graphs else None):
                     if st is None:
-                        st = self._prefill(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot)
+                        st = self._prefill(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
                         self._steps(st, 1, hi)
                     else:
                         self._steps(st, lo, hi)
@@ -875,7 +898,10 @@ class LlamaDecodeEngine:
             self._check_persistent(st)
             # the graph's static buffers are overwritten by the next replay: hand out copies
             fl = st["first_logits"]
-            return self._finish((st["tokens"].clone(), None if fl is None else fl.clone()), return_first_logits)
+            outs = (st["tokens"].clone(), None if fl is None else fl.clone())
+            if st.get("rank") is not None:
+                outs = outs + (st["rank"].clone(),)
+            return self._finish(outs, return_first_logits)
         if defer and chunk > 0:
             advance(2 if split else 1)                          # prompt pass (+ gate) + the first chunk of steps: no host wait
             return finish
@@ -884,7 +910,7 @@ class LlamaDecodeEngine:
 
     @staticmethod
     def _finish(outs, want_first):
-        return outs if want_first else outs[0]
+        return outs if want_first or len(outs) > 2 else outs[0]
 
     def _check_persistent(self, st):
         """psg_decode_layer bounds every hand-off poll and reports a producer that never arrived through word
@@ -897,19 +923,22 @@ class LlamaDecodeEngine:
                 raise PsgHipError("psg_decode_layer: a hand-off poll timed out (cnt[PSG_DL_TIMEOUT] set); the tokens of this "
                                   "generation are invalid - disable option decode_persistent")
 
-    def _generate_eager(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0):
-        st = self._prefill(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot)
+    def _generate_eager(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None):
+        st = self._prefill(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
         self._steps(st, 1, max_new)
         if not torch.cuda.is_current_stream_capturing():
             self._check_persistent(st)
+        if trie is not None:
+            return st["tokens"], st["first_logits"], st["rank"]
         return st["tokens"], st["first_logits"]
 
-    def _prefill(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0):
-        """Prompt pass + first greedy token.  Returns the decode state (KV caches, token / flag buffers)."""
+    def _prefill(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None):
+        """Prompt pass + first greedy token (+ the relation-likelihood pass over `trie`, whose rows own the cache slots
+        behind the decode region).  Returns the decode state (KV caches, token / flag buffers)."""
         m = self.cfg.llm
         K, maxlen, D = X.shape
         nv = self.cfg.qformer.num_query
-        ctx_len = maxlen + max_new
+        ctx_len = maxlen + max_new + (trie.n_int if trie is not None else 0)
         dev = self.device
         seq_len = (prompt_len.to(torch.int32) + nv)                                   # valid tokens per pair
         t = torch.arange(maxlen, device=dev, dtype=torch.int32)[None, :].expand(K, -1)
@@ -925,6 +954,9 @@ class LlamaDecodeEngine:
         first_logits = None
         if return_first_logits:
             first_logits = logits.reduce(self.dtype) if isinstance(logits, ops.Partials) else logits.to(self.dtype)
+        rank = None
+        if trie is not None:
+            rank = self._rank_pass(logits, seq_len, kc, vc, ctx_len, maxlen, maxlen + max_new, trie)
         tokens = torch.full((K, max_new), -1, device=dev, dtype=torch.int32)
         done = torch.zeros(K, device=dev, dtype=torch.int32)
         next_ids = torch.zeros(K, device=dev, dtype=torch.int32)
@@ -936,7 +968,48 @@ class LlamaDecodeEngine:
         ops.greedy_step(logits, 0, max_new, m.eos, sup, tokens, done, next_ids, dec_pos,
                         dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed, x_out=x)
         return dict(kc=kc, vc=vc, ctx_len=ctx_len, tokens=tokens, done=done, next_ids=next_ids, dec_pos=dec_pos,
-                    dec_pair=dec_pair, sup=sup, x=x, max_new=max_new, first_logits=first_logits, slot=int(slot))
+                    dec_pair=dec_pair, sup=sup, x=x, max_new=max_new, first_logits=first_logits, slot=int(slot), rank=rank,
+                    # a captured graph reads the trie's device tables by address: the decode state (which the graph entry
+                    # holds) keeps the trie and its tables alive as long as the graph, whatever becomes of the head's trie
+                    rank_trie=trie, rank_tables=None if trie is None else trie.device(dev))
+
+    def _rank_pass(self, root_logits, seq_len, kc, vc, ctx_len, maxlen, base, trie):
+        """The relation-likelihood pass: log s(p, r) for every selected pair p and every class r of `trie`.
+        Every internal trie node is one row per pair - its token's embedding at rotary position seq_len + depth - 1, cache
+        slot base + node - and ONE forward over all K x n_int rows runs every layer on them (projections through
+        `linear`, as the prompt pass; attention over the pair's prompt slots and the node's trie ancestors,
+        psg_tree_attn).  psg_token_logprobs turns the lm_head rows (and the prompt's last rows, `root_logits`) into the
+        log-probabilities of the trie edges; a class's score is the sum over its path.  Static shapes, no host wait:
+        captured with the prompt pass.  Returns fp32 [K, R]."""
+        m = self.cfg.llm
+        dev = self.device
+        K = seq_len.numel()
+        T = trie.device(dev)
+        n, E = trie.n_int, trie.n_edges
+        if base + n > ctx_len:
+            raise PsgHipError(f"relation-likelihood pass: trie slots [{base}, {base + n}) exceed the {ctx_len}-slot cache")
+        lp = torch.zeros((K, E + 1), device=dev, dtype=torch.float32)       # column E: the zero that pads the paths
+        pair_ids = torch.arange(K, device=dev, dtype=torch.int32)
+        ops.token_logprobs(root_logits, torch.zeros(K, device=dev, dtype=torch.int32),
+                           pair_ids.to(torch.int64) * (E + 1), T["child_off"], T["child_tok"], lp)
+        row_pair = pair_ids[:, None].expand(K, n).reshape(-1).contiguous()
+        row_node = torch.arange(n, device=dev, dtype=torch.int32).repeat(K)
+        tok_pos = (row_node + base).contiguous()
+        rope_pos = (seq_len.to(torch.int32)[row_pair.long()] + T["node_depth"][row_node.long()] - 1).contiguous()
+        ids = T["node_tok"][row_node.long()].contiguous()
+        emb = torch.empty((K * n, m.hidden), device=dev, dtype=self.dtype)
+        ops.gather_rows(self.embed, ids, emb)
+        resid = emb.to(self.resid_dtype, copy=True)
+        tree = dict(row_node=row_node, prefix_len=seq_len.to(torch.int32).contiguous(), anc=T["anc"], base=int(base),
+                    rope_bound=int(maxlen + trie.max_depth))
+        h = self._forward(resid, row_pair, tok_pos, kc, vc, ctx_len, rope_pos=rope_pos, tree=tree)
+        if h.dtype == torch.float32:
+            logits = self.logits(h)
+        else:                                                  # fp32 logits of the 16-bit modes, ONE product (`logits` would
+            logits = self._lm_head_f32(h)                      # run the 16-bit product first and discard it)
+        row_out = (row_pair.to(torch.int64) * (E + 1) + T["child_off"][(row_node + 1).long()].to(torch.int64)).contiguous()
+        ops.token_logprobs(logits, (row_node + 1).contiguous(), row_out, T["child_off"], T["child_tok"], lp)
+        return lp[:, T["path"]].sum(-1)
 
     def _steps(self, st, lo, hi):
         """Decode steps lo .. hi-1 (step s writes tokens[:, s])."""

@@ -438,15 +438,21 @@ def _gqa(heads, kv_heads):
 
 
 def rope_kvwrite(qkv, tok_pair, tok_pos, rope, heads, head_dim, ctx_len, q_out, k_cache, v_cache, rope_pos=None,
-                 kv_heads=None):
+                 kv_heads=None, rope_pos_bound=None):
     """rope = (cos, sin) fp32 tables [>= ctx_len, head_dim/2].  rope_pos int32 [rows]: rotary positions when they
     differ from the cache slots (training forward).  kv_heads < heads: grouped-query attention (psg_rope_kvwrite_gqa:
-    qkv rows [q | k | v] of (heads + 2 kv_heads) * head_dim, caches [pairs, kv_heads, ctx, head_dim])."""
+    qkv rows [q | k | v] of (heads + 2 kv_heads) * head_dim, caches [pairs, kv_heads, ctx, head_dim]).
+    rope_pos_bound: a bound the caller knows on the host (every rope_pos < it) - no read-back, so the launch can be
+    captured into a graph (the relation-likelihood pass)."""
     lib, ctx, st = _env(q_out)
     rows = q_out.shape[0]
     qp, qs = _in(qkv, q_out.dtype)
     assert rope[0].shape[0] >= ctx_len and rope[0].shape[1] == head_dim // 2
-    if rope_pos is not None:
+    if rope_pos is not None and rope_pos_bound is not None:
+        if int(rope_pos_bound) > rope[0].shape[0]:
+            raise PsgHipError(f"rope_kvwrite: rotary positions up to {int(rope_pos_bound) - 1} exceed the "
+                              f"{rope[0].shape[0]}-row rotary table")
+    elif rope_pos is not None:
         # positions of the reference's PADDED sequence may exceed the compact context length: the kernel indexes the
         # rotary tables with them unchecked, so bound them here (training forward only; one scalar read-back)
         top = int(rope_pos.max().item()) if rope_pos.numel() else -1
@@ -490,6 +496,42 @@ def prefill_attn(q, k_cache, v_cache, tok_pos, pairs, rows_per_pair, heads, head
     check(lib.psg_prefill_attn(ctx, _p(q, name="q"), _p(k_cache, q.dtype), _p(v_cache, q.dtype),
                                _p(tok_pos, torch.int32), pairs, rows_per_pair, heads, head_dim, ctx_len,
                                _p(out, q.dtype), _dt(q), st), "psg_prefill_attn")
+    return out
+
+
+def tree_attn(q, k_cache, v_cache, row_pair, row_node, prefix_len, anc, trie_base, heads, head_dim, ctx_len, out,
+              kv_heads=None):
+    """Attention of token-trie rows (psg_tree_attn): row r of pair row_pair[r] at trie node row_node[r] attends to the
+    pair's prompt slots [0, prefix_len[pair]) and to slots trie_base + anc[node][d] (ancestors, then the node itself;
+    anc int32 [n_int, max_depth], -1 padded).  q / out [rows, heads * head_dim], caches [pairs, kv_heads, ctx, head_dim]:
+    all fp32 (exact) or all 16-bit."""
+    lib, ctx, st = _env(q)
+    kv = heads if kv_heads is None else int(kv_heads)
+    n_int, max_depth = anc.shape
+    pairs = k_cache.shape[0]
+    assert q.shape[1] == heads * head_dim and tuple(k_cache.shape) == (pairs, kv, ctx_len, head_dim)
+    assert prefix_len.numel() == pairs and row_pair.numel() == q.shape[0] == row_node.numel()
+    check(lib.psg_tree_attn(ctx, _p(q, name="q"), _p(k_cache, q.dtype), _p(v_cache, q.dtype), _p(row_pair, torch.int32),
+                            _p(row_node, torch.int32), _p(prefix_len, torch.int32), _p(anc, torch.int32), n_int, max_depth,
+                            int(trie_base), q.shape[0], heads, kv, pairs, head_dim, ctx_len, _p(out, q.dtype), _dt(q), st),
+          "psg_tree_attn")
+    return out
+
+
+def token_logprobs(logits, row_node, row_out, child_off, child_tok, out, dtype=None):
+    """logit[tok] - logsumexp(logit row) for the trie children of every logit row (psg_token_logprobs).  logits [rows,
+    vocab] (fp32 / 16-bit) or `Partials` (summed in slice order); row_node int32 [rows], row_out int64 [rows] = flat index
+    in `out` (fp32) of the row's first child; child_off int32 [n_nodes + 1] / child_tok int32 [n_edges]: CSR lists."""
+    lib, ctx, st = _env(out)
+    rows, vocab = logits.shape
+    if isinstance(logits, Partials):
+        lp, ls, dt = _p(logits.t), logits.splits, PSG_F32
+    else:
+        lp, ls, dt = _p(logits), 0, _dt(logits)
+    assert row_node.numel() == rows == row_out.numel()
+    check(lib.psg_token_logprobs(ctx, lp, ls, rows, vocab, _p(row_node, torch.int32), _p(row_out, torch.int64),
+                                 _p(child_off, torch.int32), _p(child_tok, torch.int32), child_off.numel() - 1,
+                                 child_tok.numel(), _p(out, torch.float32), out.numel(), dt, st), "psg_token_logprobs")
     return out
 
 
