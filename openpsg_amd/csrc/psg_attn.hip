@@ -670,38 +670,37 @@ __global__ void __launch_bounds__(256) llm_attn_kernel(const T* __restrict__ q, 
   Act<T>::st(out, row * hidden + h * 128 + lane + 64, o2 * inv);
 }
 
+static int llm_attn_launch(const char* name, const void* q, const void* k_cache, const void* v_cache,
+                           const int32_t* tok_pair, const int32_t* tok_pos, int64_t rows, int heads, int kv_heads,
+                           int head_dim, int ctx, void* out, int dtype, void* stream) {
+  PSG_REQUIRE(q && k_cache && v_cache && tok_pair && tok_pos && out, PSG_ERR_INVALID, "%s: NULL argument", name);
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "%s: head_dim=%d (kernel is built for 128)", name, head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "%s: heads=%d kv_heads=%d (a divisor, group <= %d)", name, heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  int64_t waves = rows * heads;
+  PSG_DISPATCH_DTYPE(dtype, name,
+                     (llm_attn_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, kv_heads,
+                         ctx, (T*)out)));
+  PSG_CHECK_LAUNCH(name);
+  return PSG_OK;
+}
+
 extern "C" int psg_llm_attn(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
                             const int32_t* tok_pair, const int32_t* tok_pos, int64_t rows, int heads, int head_dim,
                             int ctx, void* out, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && q && k_cache && v_cache && tok_pair && tok_pos && out, PSG_ERR_INVALID,
-              "psg_llm_attn: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_llm_attn: head_dim=%d (kernel is built for 128)", head_dim);
-  if (rows == 0) return PSG_OK;
-  int64_t waves = rows * heads;
-  PSG_DISPATCH_DTYPE(dtype, "psg_llm_attn",
-                     (llm_attn_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, heads,
-                         ctx, (T*)out)));
-  PSG_CHECK_LAUNCH("psg_llm_attn");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_llm_attn: NULL argument");
+  return llm_attn_launch("psg_llm_attn", q, k_cache, v_cache, tok_pair, tok_pos, rows, heads, heads, head_dim, ctx, out,
+                         dtype, stream);
 }
 
 extern "C" int psg_llm_attn_gqa(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
                                 const int32_t* tok_pair, const int32_t* tok_pos, int64_t rows, int heads, int kv_heads,
                                 int head_dim, int ctx, void* out, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && q && k_cache && v_cache && tok_pair && tok_pos && out, PSG_ERR_INVALID,
-              "psg_llm_attn_gqa: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_llm_attn_gqa: head_dim=%d (kernel is built for 128)", head_dim);
-  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
-              "psg_llm_attn_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads, PSG_GQA_MAX_GROUP);
-  if (rows == 0) return PSG_OK;
-  int64_t waves = rows * heads;
-  PSG_DISPATCH_DTYPE(dtype, "psg_llm_attn_gqa",
-                     (llm_attn_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         (const T*)q, (const T*)k_cache, (const T*)v_cache, tok_pair, tok_pos, rows, heads, kv_heads,
-                         ctx, (T*)out)));
-  PSG_CHECK_LAUNCH("psg_llm_attn_gqa");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_llm_attn_gqa: NULL argument");
+  return llm_attn_launch("psg_llm_attn_gqa", q, k_cache, v_cache, tok_pair, tok_pos, rows, heads, kv_heads, head_dim, ctx,
+                         out, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

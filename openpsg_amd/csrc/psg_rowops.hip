@@ -820,42 +820,41 @@ __global__ void rope_kvwrite_kernel(const void* __restrict__ qkv, int qs, const 
   Act<T>::st(vc, cbase + lane + 64, v2);
 }
 
+static int rope_kvwrite_launch(const char* name, const void* qkv, int qkv_splits, const int32_t* tok_pair,
+                               const int32_t* tok_pos, const int32_t* rope_pos, const float* rope_cos,
+                               const float* rope_sin, int64_t rows, int heads, int kv_heads, int head_dim, int ctx,
+                               void* q_out, void* k_cache, void* v_cache, int dtype, void* stream) {
+  PSG_REQUIRE(qkv && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache && v_cache, PSG_ERR_INVALID,
+              "%s: NULL argument", name);
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "%s: head_dim=%d (kernel is built for 128)", name, head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "%s: heads=%d kv_heads=%d (a divisor, group <= %d)", name, heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  int64_t waves = rows * heads;
+  PSG_DISPATCH_DTYPE(dtype, name,
+                     (rope_kvwrite_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx,
+                         (T*)q_out, (T*)k_cache, (T*)v_cache)));
+  PSG_CHECK_LAUNCH(name);
+  return PSG_OK;
+}
+
 extern "C" int psg_rope_kvwrite(psg_ctx* ctx_, const void* qkv, int qkv_splits, const int32_t* tok_pair,
                                 const int32_t* tok_pos, const int32_t* rope_pos, const float* rope_cos,
                                 const float* rope_sin, int64_t rows, int heads, int head_dim, int ctx, void* q_out,
                                 void* k_cache, void* v_cache, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && qkv && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache && v_cache, PSG_ERR_INVALID,
-              "psg_rope_kvwrite: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite: head_dim=%d (kernel is built for 128)",
-              head_dim);
-  if (rows == 0) return PSG_OK;
-  int64_t waves = rows * heads;
-  PSG_DISPATCH_DTYPE(dtype, "psg_rope_kvwrite",
-                     (rope_kvwrite_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, heads, ctx,
-                         (T*)q_out, (T*)k_cache, (T*)v_cache)));
-  PSG_CHECK_LAUNCH("psg_rope_kvwrite");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_rope_kvwrite: NULL argument");
+  return rope_kvwrite_launch("psg_rope_kvwrite", qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows,
+                             heads, heads, head_dim, ctx, q_out, k_cache, v_cache, dtype, stream);
 }
 
 extern "C" int psg_rope_kvwrite_gqa(psg_ctx* ctx_, const void* qkv, int qkv_splits, const int32_t* tok_pair,
                                     const int32_t* tok_pos, const int32_t* rope_pos, const float* rope_cos,
                                     const float* rope_sin, int64_t rows, int heads, int kv_heads, int head_dim, int ctx,
                                     void* q_out, void* k_cache, void* v_cache, int dtype, void* stream) {
-  PSG_REQUIRE(ctx_ && qkv && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache && v_cache, PSG_ERR_INVALID,
-              "psg_rope_kvwrite_gqa: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite_gqa: head_dim=%d (kernel is built for 128)",
-              head_dim);
-  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
-              "psg_rope_kvwrite_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads, PSG_GQA_MAX_GROUP);
-  if (rows == 0) return PSG_OK;
-  int64_t waves = rows * heads;
-  PSG_DISPATCH_DTYPE(dtype, "psg_rope_kvwrite_gqa",
-                     (rope_kvwrite_kernel<T><<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-                         qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx,
-                         (T*)q_out, (T*)k_cache, (T*)v_cache)));
-  PSG_CHECK_LAUNCH("psg_rope_kvwrite_gqa");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_rope_kvwrite_gqa: NULL argument");
+  return rope_kvwrite_launch("psg_rope_kvwrite_gqa", qkv, qkv_splits, tok_pair, tok_pos, rope_pos, rope_cos, rope_sin,
+                             rows, heads, kv_heads, head_dim, ctx, q_out, k_cache, v_cache, dtype, stream);
 }
 
 // ---- SwiGLU gate ------------------------------------------------------------------------------

@@ -463,20 +463,31 @@ __global__ void rope_kvwrite_scaled_kernel(const float* __restrict__ qkv, const 
   vc[cbase + lane + 64] = v2;
 }
 
+static int rope_kvwrite_scaled_launch(const char* name, const float* qkv, const float* row_scale, const float* col_scale,
+                                      const int32_t* tok_pair, const int32_t* tok_pos, const float* rope_cos,
+                                      const float* rope_sin, int slices, int64_t rows, int heads, int kv_heads,
+                                      int head_dim, int ctx, float* q_out, float* k_cache, float* v_cache, void* stream) {
+  PSG_REQUIRE(qkv && row_scale && col_scale && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache && v_cache,
+              PSG_ERR_INVALID, "%s: NULL argument", name);
+  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "%s: head_dim=%d (kernel is built for 128)", name, head_dim);
+  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
+              "%s: heads=%d kv_heads=%d (a divisor, group <= %d)", name, heads, kv_heads, PSG_GQA_MAX_GROUP);
+  if (rows == 0) return PSG_OK;
+  const int64_t waves = rows * heads;
+  rope_kvwrite_scaled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx, q_out, k_cache, v_cache,
+      slices);
+  PSG_CHECK_LAUNCH(name);
+  return PSG_OK;
+}
+
 extern "C" int psg_rope_kvwrite_scaled(psg_ctx* ctx_, const float* qkv, const float* row_scale, const float* col_scale,
                                        const int32_t* tok_pair, const int32_t* tok_pos, const float* rope_cos,
                                        const float* rope_sin, int slices, int64_t rows, int heads, int head_dim, int ctx,
                                        float* q_out, float* k_cache, float* v_cache, void* stream) {
-  PSG_REQUIRE(ctx_ && qkv && row_scale && col_scale && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache &&
-                  v_cache, PSG_ERR_INVALID, "psg_rope_kvwrite_scaled: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite_scaled: head_dim=%d (kernel is built for 128)", head_dim);
-  if (rows == 0) return PSG_OK;
-  const int64_t waves = rows * heads;
-  rope_kvwrite_scaled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, heads, ctx, q_out, k_cache, v_cache,
-      slices);
-  PSG_CHECK_LAUNCH("psg_rope_kvwrite_scaled");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_rope_kvwrite_scaled: NULL argument");
+  return rope_kvwrite_scaled_launch("psg_rope_kvwrite_scaled", qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos,
+                                    rope_sin, slices, rows, heads, heads, head_dim, ctx, q_out, k_cache, v_cache, stream);
 }
 
 extern "C" int psg_rope_kvwrite_scaled_gqa(psg_ctx* ctx_, const float* qkv, const float* row_scale, const float* col_scale,
@@ -484,20 +495,10 @@ extern "C" int psg_rope_kvwrite_scaled_gqa(psg_ctx* ctx_, const float* qkv, cons
                                            const float* rope_sin, int slices, int64_t rows, int heads, int kv_heads,
                                            int head_dim, int ctx, float* q_out, float* k_cache, float* v_cache,
                                            void* stream) {
-  PSG_REQUIRE(ctx_ && qkv && row_scale && col_scale && tok_pair && tok_pos && rope_cos && rope_sin && q_out && k_cache &&
-                  v_cache, PSG_ERR_INVALID, "psg_rope_kvwrite_scaled_gqa: NULL argument");
-  PSG_REQUIRE(head_dim == 128, PSG_ERR_UNSUPPORTED, "psg_rope_kvwrite_scaled_gqa: head_dim=%d (kernel is built for 128)",
-              head_dim);
-  PSG_REQUIRE(kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= PSG_GQA_MAX_GROUP, PSG_ERR_UNSUPPORTED,
-              "psg_rope_kvwrite_scaled_gqa: heads=%d kv_heads=%d (a divisor, group <= %d)", heads, kv_heads,
-              PSG_GQA_MAX_GROUP);
-  if (rows == 0) return PSG_OK;
-  const int64_t waves = rows * heads;
-  rope_kvwrite_scaled_kernel<<<(unsigned)((waves + 3) / 4), 256, 0, (hipStream_t)stream>>>(
-      qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos, rope_sin, rows, heads, kv_heads, ctx, q_out, k_cache, v_cache,
-      slices);
-  PSG_CHECK_LAUNCH("psg_rope_kvwrite_scaled_gqa");
-  return PSG_OK;
+  PSG_REQUIRE(ctx_, PSG_ERR_INVALID, "psg_rope_kvwrite_scaled_gqa: NULL argument");
+  return rope_kvwrite_scaled_launch("psg_rope_kvwrite_scaled_gqa", qkv, row_scale, col_scale, tok_pair, tok_pos, rope_cos,
+                                    rope_sin, slices, rows, heads, kv_heads, head_dim, ctx, q_out, k_cache, v_cache,
+                                    stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

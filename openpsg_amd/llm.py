@@ -270,9 +270,10 @@ class LlamaDecodeEngine:
         self._w16 = {}
         self._skinny_ok = {}
         self._w16_all = False
-        self._ones = {}
-        from . import _lib as _lib0
-        if dtype == torch.float32 and _lib0.get_option(self.device.index or 0, "llm_w16"):
+        self._ones_cache = {}
+        from . import _lib
+        dev_i = self.device.index or 0
+        if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
             tensors = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
             for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
                 h = t.half()
@@ -291,7 +292,7 @@ class LlamaDecodeEngine:
         # job) then gives the bits it gives in the batch of 20.  ~1.3x the prompt pass's GEMM time: the sharded
         # pipeline switches it on, a single GPU does not need it
         self.row_invariant = False
-        self.split_i2 = bool(_lib0.get_option(self.device.index or 0, "split_i2"))
+        self.split_i2 = bool(_lib.get_option(dev_i, "split_i2"))
         self._i2_w = {}
         self.proj_s = ops.split_f16x3(self.proj_w, weights=True) if self.prefill_split else None
         # greedy argmax over the fp32 split-K sums of the lm_head, NOT over their 16-bit rounding: HF computes the logits of
@@ -304,8 +305,6 @@ class LlamaDecodeEngine:
         # psg_skinny_gemm_fused).  Built for "rmsnorm", bit-identical, and OFF by default: measured 26.6 vs 25.6 us
         # per (RMSNorm + q/k/v projection), 75.2 vs 74.0 ms per image - the in-launch hand-off (write-through
         # publish, counter, poll, x staged after it) costs what the separate launch costs
-        from . import _lib
-        dev_i = self.device.index or 0
         self.fuse_rowops = frozenset({"rmsnorm"}) if _lib.get_option(dev_i, "llm_fuse_rmsnorm") else frozenset()
         self.prefill_attn_scalar = bool(_lib.get_option(dev_i, "prefill_attn_scalar"))
         # decode steps as ONE persistent launch per layer (psg_decode_layer; fp32 engines at Llama-2-7B width on a 256-CU
@@ -338,22 +337,27 @@ class LlamaDecodeEngine:
         ang = torch.arange(4096, dtype=torch.float32)[:, None] * inv_freq[None, :]
         self.rope = (ang.cos().contiguous().to(self.device), ang.sin().contiguous().to(self.device))
 
-    def linear_split(self, x, ws, w=None):
-        """x [rows, K] fp32 @ w.T as ONE fp16 matrix-core GEMM over 3K: [xh | xh | xl] . [wh | wl | wh]^T with fp32
+    def _dense_split(self, ws):
+        """Does `linear_split` run this split weight on psg_dense_gemm (the row-invariant path)?"""
+        return self.row_invariant and ws is not None and ws[0].shape[0] % 256 == 0 and ws[0].shape[1] % 64 == 0
+
+    def linear_split(self, x, ws, w=None, bias=None):
+        """x [rows, K] fp32 @ w.T (+ bias) as ONE fp16 matrix-core GEMM over 3K: [xh | xh | xl] . [wh | wl | wh]^T with fp32
         accumulation, rows and columns rescaled by their powers of two afterwards (exact).  Products of fp16 values
         are exact in fp32, so what is lost against an fp32 GEMM is the xl.wl term and the split residuals: ~7e-7
         relative per product (fp32 rounds each product to 6e-8), at 3/16 of the fp32 matrix time."""
-        if self.row_invariant and ws[0].shape[0] % 256 == 0 and ws[0].shape[1] % 64 == 0:
+        if self._dense_split(ws):
             if self.split_i2 and w is not None and w.shape[1] % 32 == 0:
                 # round 6: interleaved hi / lo images, the three products from one staging (psg_dense_gemm_split)
                 w2 = self._i2_weight(w)
                 a2, inv_r = ops.split_f16i2(x)
-                return ops.dense_gemm_split(a2, w2[0], None, inv_r, w2[1], tile="256x256")
+                return ops.dense_gemm_split(a2, w2[0], bias, inv_r, w2[1], tile="256x256")
             a3, inv_r = ops.split_f16x3(x)
-            return ops.dense_gemm(a3, ws[0], None, out_dtype=torch.float32, row_scale=inv_r, col_scale=ws[1])
+            return ops.dense_gemm(a3, ws[0], bias, out_dtype=torch.float32, row_scale=inv_r, col_scale=ws[1])
         a3, inv_r = ops.split_f16x3(x)
         y = _split_mm(a3, ws[0], _plan_split_mm(a3.shape[0], ws[0]) if self.plan_split else None)
-        return ops.scale_rows_cols(y, inv_r, ws[1])
+        y = ops.scale_rows_cols(y, inv_r, ws[1])
+        return y if bias is None else y + bias
 
     def set_projection(self, weight, bias):
         """Replaces the packed copy of `language_projection` (a checkpoint loaded after the engine was built, an optimizer
@@ -374,13 +378,13 @@ class LlamaDecodeEngine:
             ent = self._i2_w[w.data_ptr()] = ops.split_f16i2(w)
         return ent
 
-    def _skinny_fits(self, x, w):
-        """The weight-streaming kernel keeps the rows' K slice in LDS beside its weight rings: the fp32 kernel takes 32 rows up
-        to K = 11776 and 20 rows up to K = 20480 (every Llama-2-7B / 13B shape at the reference's 20 selected pairs).  A wider
-        model falls through to the library GEMM for that projection (exact fp32, not batch-invariant) instead of failing."""
-        return self._skinny_fits_shape(x.shape[0], w, x.dtype)
-
-    def _skinny_fits_shape(self, rows, w, dtype):
+    def _streams(self, rows, w, dtype):
+        """Can the weight-streaming kernel run `rows` rows of `dtype` against w?  It keeps the rows' K slice in LDS beside its
+        weight rings: the fp32 kernel takes 32 rows up to K = 11776 and 20 rows up to K = 20480 (every Llama-2-7B / 13B shape
+        at the reference's 20 selected pairs).  A wider model falls through to the library GEMM for that projection (exact
+        fp32, not batch-invariant) instead of failing."""
+        if not (w.shape[0] % 16 == 0 and w.shape[1] % 64 == 0 and w.shape[1] >= 256):
+            return False
         key = (rows, tuple(w.shape), dtype)
         ok = self._skinny_ok.get(key)
         if ok is None:
@@ -392,13 +396,19 @@ class LlamaDecodeEngine:
             self._skinny_ok[key] = ok
         return ok
 
+    def _ones(self, n):
+        """fp32 ones [n]: the column scale of a product against an fp16-valued weight (it has no scale of its own)."""
+        t = self._ones_cache.get(n)
+        if t is None:
+            t = self._ones_cache[n] = torch.ones(n, device=self.device, dtype=torch.float32)
+        return t
+
     def linear(self, x, w, ws=None, decode=False):
         """Bias-free projection.  Decode-step shapes (<= 32 rows) use the hand-written weight-streaming kernel - in
         the 16-bit modes and in the fp32 mode (the reference's own precision, V4:99-100) alike; the prompt pass goes
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
         psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm)."""
-        if (self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and w.shape[0] % 16 == 0
-                and w.shape[1] % 64 == 0 and w.shape[1] >= 256 and self._skinny_fits(x, w)):
+        if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
             if wh is not None and self.prefill_split:         # fp32s: two fp16 products of the split rows, 2 bytes per weight
                 x2, inv = ops.split_f16x2(x)
@@ -427,10 +437,7 @@ class LlamaDecodeEngine:
             if wh is not None and w.shape[1] % 8 == 0:
                 a2, inv = ops.split_f16x2(x)
                 y2 = torch.mm(a2.view(2 * x.shape[0], x.shape[1]), wh.t(), out_dtype=torch.float32)
-                ones = self._ones.get(w.shape[0])
-                if ones is None:
-                    ones = self._ones[w.shape[0]] = torch.ones(w.shape[0], device=self.device, dtype=torch.float32)
-                return ops.Scaled(y2.view(2, x.shape[0], w.shape[0]), inv, ones).dense()
+                return ops.Scaled(y2.view(2, x.shape[0], w.shape[0]), inv, self._ones(w.shape[0])).dense()
             return F.linear(x, w)
         if ws is not None and x.dtype == torch.float32:
             return self.linear_split(x, ws, w)
@@ -438,7 +445,7 @@ class LlamaDecodeEngine:
 
     def decode_uses_library(self, rows) -> bool:
         """Does a decode step of `rows` rows run a library GEMM?  Above 32 rows, without the weight-streaming kernel, or
-        when a projection's K slice does not fit it at this row count (`_skinny_fits`: fp32 at K = 14336, Mistral-7B's
+        when a projection's K slice does not fit it at this row count (`_streams`: fp32 at K = 14336, Mistral-7B's
         down projection, above 20 rows).  Two library decodes must not run side by side on two streams (`head.submit`)."""
         rows = int(rows)
         if not self.use_skinny or rows > 32:
@@ -447,11 +454,7 @@ class LlamaDecodeEngine:
             return False
         L = self.layers[0] if self.layers else None
         ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
-        for w in ws:
-            if not (w.shape[0] % 16 == 0 and w.shape[1] % 64 == 0 and w.shape[1] >= 256
-                    and self._skinny_fits_shape(rows, w, self.dtype)):
-                return True
-        return False
+        return not all(self._streams(rows, w, self.dtype) for w in ws)
 
     def logits(self, h):
         """lm_head.  <= 32 rows: the weight-streaming kernel (fp32 split-K partials, summed inside the greedy step);
@@ -460,18 +463,11 @@ class LlamaDecodeEngine:
         out = self.linear(h, self.lm_head, decode=True)
         if isinstance(out, ops.Partials) or not self.exact_argmax or h.dtype == torch.float32:
             return out
-        if self._mm_out_dtype is None:
-            try:
-                torch.mm(h[:1], self.lm_head[:16].t(), out_dtype=torch.float32)
-                self._mm_out_dtype = True
-            except (TypeError, RuntimeError):
-                self._mm_out_dtype = False
-        if self._mm_out_dtype:
-            return torch.mm(h, self.lm_head.t(), out_dtype=torch.float32)
-        return out.float()
+        return self._lm_head_f32(h, out)
 
-    def _lm_head_f32(self, h):
-        """lm_head of 16-bit rows with an fp32 result (the values `logits` hands the greedy step above 32 rows)."""
+    def _lm_head_f32(self, h, rounded=None):
+        """lm_head of 16-bit rows with an fp32 result (the values `logits` hands the greedy step above 32 rows).
+        rounded: the 16-bit product, where the caller has it: without `out_dtype` it is widened instead of computed again."""
         if self._mm_out_dtype is None:
             try:
                 torch.mm(h[:1], self.lm_head[:16].t(), out_dtype=torch.float32)
@@ -480,7 +476,7 @@ class LlamaDecodeEngine:
                 self._mm_out_dtype = False
         if self._mm_out_dtype:
             return torch.mm(h, self.lm_head.t(), out_dtype=torch.float32)
-        return F.linear(h, self.lm_head).float()
+        return (F.linear(h, self.lm_head) if rounded is None else rounded).float()
 
     # ---- one pass over `rows` token rows -------------------------------------------------------
     def _forward(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, decode=False, prefill_shape=None, rope_pos=None,
@@ -532,14 +528,9 @@ class LlamaDecodeEngine:
                 else:
                     ops.llm_attn(q, kc[l], vc[l], tok_pair, tok_pos, m.heads, m.head_dim, ctx_len, att, kv_heads=self.kv)
             if keep_rows is not None and l == len(self.layers) - 1:
-                k = keep_rows.numel()
-                att_k, resid_k = torch.empty((k, D), device=self.device, dtype=self.dtype), torch.empty(
-                    (k, D), device=self.device, dtype=resid.dtype)
-                ops.gather_rows(att, keep_rows, att_k)
-                ops.gather_rows(resid, keep_rows, resid_k)
-                att, resid = att_k, resid_k
+                att, resid = self._gather_kept(att, resid, keep_rows)
                 n = torch.empty_like(att)
-                act = torch.empty((k, m.inter), device=self.device, dtype=self.dtype)
+                act = torch.empty((keep_rows.numel(), m.inter), device=self.device, dtype=self.dtype)
             o = self.linear(att, L["wo"], L.get("wo_s"), decode=decode)
             ops.rmsnorm(resid, o, L["ln2"], m.rms_eps, n)                      # resid += o ; n = norm(resid)
             gu = self.linear(n, L["wgu"], L.get("wgu_s"), decode=decode)
@@ -549,98 +540,70 @@ class LlamaDecodeEngine:
             ops.rmsnorm(resid, d, nxt, m.rms_eps, n)                           # resid += d ; n = norm(resid)
         return n
 
+    def _gather_kept(self, att, resid, keep_rows):
+        """Last layer of a pass whose caller reads only `keep_rows`: the attention output and the residual stream of those
+        rows - everything behind the attention then runs on them alone."""
+        k, D = keep_rows.numel(), att.shape[1]
+        att_k = torch.empty((k, D), device=self.device, dtype=att.dtype)
+        resid_k = torch.empty((k, D), device=self.device, dtype=resid.dtype)
+        ops.gather_rows(att, keep_rows, att_k)
+        ops.gather_rows(resid, keep_rows, resid_k)
+        return att_k, resid_k
+
     def _forward_split(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape, keep_rows):
         """`_forward` for the prompt pass of the fp32s mode with the operand splits and result scalings fused into the row
-        kernels: RMSNorm and SwiGLU write [hi | hi | lo] fp16 segments, every projection result stays raw (`ops.Scaled`)
-        until its reader applies the scales while loading.  Same arithmetic as `_forward` + linear_split, bit for bit."""
+        kernels: RMSNorm and SwiGLU write the split fp16 operand, every projection result stays raw (`ops.Scaled`) until
+        its reader applies the scales while loading.  Same arithmetic as `_forward` + linear_split, bit for bit.
+        Three planes (generic fp32 weights): [hi | hi | lo] K segments against the split weight [wh | wl | wh] and its
+        column scale.  Two planes (every matrix an fp16 value, `self._w16`): a weight has no low part, so a product is ONE
+        library GEMM of the operand [xh; xl] (2 x rows rows) against the fp16 weight over K - two thirds of the flops, and
+        no split copy of the weights at all; its [2, rows, N] result is summed by the reader (`slices`), the only scale
+        left is the row's."""
         m = self.cfg.llm
         rows, D = resid.shape
         plan = _plan_split_mm if self.plan_split else (lambda r, w, k3=False: None)
-        if self._w16_all:
-            return self._forward_split_w16(resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape, keep_rows, plan)
-        mm = lambda a3, ws, k3=False: _split_mm(a3, ws[0], plan(a3.shape[0], ws[0], k3=k3))     # noqa: E731
-        a3, inv_r = ops.rmsnorm_split(resid, None, self.layers[0]["ln1"], m.rms_eps)
+        planes = 2 if self._w16_all else 3
+        if planes == 3:
+            weight = lambda L, k: L[k + "_s"]                                               # noqa: E731
+            mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
+            split = ops.split_f16x3
+        else:
+            weight = lambda L, k: (self._w16[L[k].data_ptr()], self._ones(L[k].shape[0]))   # noqa: E731
+            split = ops.split_f16x2
+
+            def mm(a2, w16, k3):                               # a2 [2, r, K] -> raw product slices [S, r, N]
+                r = a2.shape[1]
+                y = _split_mm(a2.view(2 * r, a2.shape[2]), w16, plan(2 * r, w16, k3=k3))
+                return y.view(-1, r, w16.shape[0])
+
+        def proj(a, inv, L, k, k3=False):                      # k3: the reader (rmsnorm_split) can sum K slices
+            w, col = weight(L, k)
+            return ops.Scaled(mm(a, w, k3), inv, col)
+
+        a, inv_r = ops.rmsnorm_split(resid, None, self.layers[0]["ln1"], m.rms_eps, planes=planes)
         q = torch.empty((rows, D), device=self.device, dtype=torch.float32)
         att = torch.empty_like(q)
         n = None
         for l, L in enumerate(self.layers):
-            qkv = ops.Scaled(mm(a3, L["wqkv_s"]), inv_r, L["wqkv_s"][1])
+            qkv = proj(a, inv_r, L, "wqkv")
             ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
                                     kv_heads=self.kv)
             ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
                              kv_heads=self.kv)
             last = l == len(self.layers) - 1
             if keep_rows is not None and last:
-                k = keep_rows.numel()
-                att_k = torch.empty((k, D), device=self.device, dtype=torch.float32)
-                resid_k = torch.empty((k, D), device=self.device, dtype=torch.float32)
-                ops.gather_rows(att, keep_rows, att_k)
-                ops.gather_rows(resid, keep_rows, resid_k)
-                att, resid = att_k, resid_k
-            a3o, inv_o = ops.split_f16x3(att)                   # a row's maximum spans all heads: stays a kernel of its own
-            o = ops.Scaled(mm(a3o, L["wo_s"], k3=True), inv_o, L["wo_s"][1])          # read by rmsnorm_split: may be K slices
-            a3, inv_r = ops.rmsnorm_split(resid, o, L["ln2"], m.rms_eps)
-            gu = ops.Scaled(mm(a3, L["wgu_s"]), inv_r, L["wgu_s"][1])
-            a3a, inv_a = ops.silu_mul_split(gu, m.inter)
-            d = ops.Scaled(mm(a3a, L["wdown_s"], k3=True), inv_a, L["wdown_s"][1])
+                att, resid = self._gather_kept(att, resid, keep_rows)
+            ao, inv_o = split(att)                              # a row's maximum spans all heads: stays a kernel of its own
+            o = proj(ao, inv_o, L, "wo", k3=True)
+            a, inv_r = ops.rmsnorm_split(resid, o, L["ln2"], m.rms_eps, planes=planes)
+            gu = proj(a, inv_r, L, "wgu")
+            aa, inv_a = ops.silu_mul_split(gu, m.inter, planes=planes)
+            d = proj(aa, inv_a, L, "wdown", k3=True)
             if last:                                            # the lm_head reads fp32 rows
                 n = torch.empty_like(resid)
                 ops.rmsnorm(resid, d.dense(), self.final_norm, m.rms_eps, n)
             else:
-                a3, inv_r = ops.rmsnorm_split(resid, d, self.layers[l + 1]["ln1"], m.rms_eps)
-        return n
-
-    def _forward_split_w16(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape, keep_rows, plan):
-        """`_forward_split` when the LLM's matrices are fp16 values (`self._w16`): a weight has no low part, so a product is
-        ONE library GEMM of the two-plane operand [xh; xl] (2 x rows rows) against the fp16 weight over K - two thirds of
-        the three-segment form's flops, and no split copy of the weights at all; its [2, rows, N] result is summed by the
-        reader (`slices`), the only scale left is the row's."""
-        m = self.cfg.llm
-        rows, D = resid.shape
-        wh = self._w16
-        ones = self._ones
-
-        def one(n):
-            t = ones.get(n)
-            if t is None:
-                t = ones[n] = torch.ones(n, device=self.device, dtype=torch.float32)
-            return t
-
-        def mm(a2, w, k3=False):                               # a2 [2, r, K] -> raw product slices [S, r, N]
-            r = a2.shape[1]
-            w16 = wh[w.data_ptr()]
-            y = _split_mm(a2.view(2 * r, a2.shape[2]), w16, plan(2 * r, w16, k3=k3))
-            return y.view(-1, r, w16.shape[0])
-
-        a2, inv_r = ops.rmsnorm_split(resid, None, self.layers[0]["ln1"], m.rms_eps, planes=2)
-        q = torch.empty((rows, D), device=self.device, dtype=torch.float32)
-        att = torch.empty_like(q)
-        n = None
-        for l, L in enumerate(self.layers):
-            qkv = ops.Scaled(mm(a2, L["wqkv"]), inv_r, one(self.qkv_width))
-            ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
-                                    kv_heads=self.kv)
-            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
-                             kv_heads=self.kv)
-            last = l == len(self.layers) - 1
-            if keep_rows is not None and last:
-                k = keep_rows.numel()
-                att_k = torch.empty((k, D), device=self.device, dtype=torch.float32)
-                resid_k = torch.empty((k, D), device=self.device, dtype=torch.float32)
-                ops.gather_rows(att, keep_rows, att_k)
-                ops.gather_rows(resid, keep_rows, resid_k)
-                att, resid = att_k, resid_k
-            a2o, inv_o = ops.split_f16x2(att)
-            o = ops.Scaled(mm(a2o, L["wo"], k3=True), inv_o, one(D))
-            a2, inv_r = ops.rmsnorm_split(resid, o, L["ln2"], m.rms_eps, planes=2)
-            gu = ops.Scaled(mm(a2, L["wgu"]), inv_r, one(2 * m.inter))
-            a2a, inv_a = ops.silu_mul_split(gu, m.inter, planes=2)
-            d = ops.Scaled(mm(a2a, L["wdown"], k3=True), inv_a, one(D))
-            if last:
-                n = torch.empty_like(resid)
-                ops.rmsnorm(resid, d.dense(), self.final_norm, m.rms_eps, n)
-            else:
-                a2, inv_r = ops.rmsnorm_split(resid, d, self.layers[l + 1]["ln1"], m.rms_eps, planes=2)
+                a, inv_r = ops.rmsnorm_split(resid, d, self.layers[l + 1]["ln1"], m.rms_eps, planes=planes)
         return n
 
     def _can_persist(self, rows, slot):
@@ -762,18 +725,11 @@ class LlamaDecodeEngine:
         K, Tp = prompt_ids.shape
         nv = self.cfg.qformer.num_query
         X = torch.empty((K, nv + Tp, m.hidden), device=self.device, dtype=self.dtype)
-        if self.row_invariant and self.proj_s is not None and m.hidden % 256 == 0 and pair_feature_rows.shape[1] % 64 == 0:
-            if self.split_i2 and pair_feature_rows.shape[1] % 32 == 0:
-                w2 = self._i2_weight(self.proj_w)
-                a2, inv_r = ops.split_f16i2(pair_feature_rows.contiguous())
-                vis = ops.dense_gemm_split(a2, w2[0], self.proj_b, inv_r, w2[1], tile="256x256").view(K, nv, m.hidden)
-            else:
-                a3, inv_r = ops.split_f16x3(pair_feature_rows.contiguous())
-                vis = ops.dense_gemm(a3, self.proj_s[0], self.proj_b, out_dtype=torch.float32, row_scale=inv_r,
-                                     col_scale=self.proj_s[1]).view(K, nv, m.hidden)
-        else:
-            vis = F.linear(pair_feature_rows, self.proj_w, self.proj_b).view(K, nv, m.hidden)
-        X[:, :nv] = vis
+        if self._dense_split(self.proj_s):
+            vis = self.linear_split(pair_feature_rows.contiguous(), self.proj_s, self.proj_w, bias=self.proj_b)
+        else:                                                  # the exact library product: `linear_split`'s fallback is not
+            vis = F.linear(pair_feature_rows, self.proj_w, self.proj_b)
+        X[:, :nv] = vis.view(K, nv, m.hidden)
         tok = torch.empty((K * Tp, m.hidden), device=self.device, dtype=self.dtype)
         ops.gather_rows(self.embed, prompt_ids.reshape(-1).contiguous(), tok)
         X[:, nv:] = tok.view(K, Tp, m.hidden)
