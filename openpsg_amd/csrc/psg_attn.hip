@@ -368,7 +368,7 @@ __global__ void __launch_bounds__(256) qformer_cls_attn_input_kernel(const T* __
         for (int k = 0; k < NK; ++k)
 #pragma unroll
           for (int e = 0; e < 4; ++e) a = fmaf(gq[hh][k][e], xv[k][e], a);
-        a = wave_sum_dpp(a) * 0.125f;                               // 1/sqrt(64)
+        a = wave_sum(a) * 0.125f;                               // 1/sqrt(64)
         a = ((valid64 >> j) & 1ull) ? a : PSG_FMIN;                 // additive finfo.min absorbs the score
         if (lane == 0) sc[(wv * HPW + hh) * 64 + j] = a;
       }

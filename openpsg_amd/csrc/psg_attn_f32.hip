@@ -28,28 +28,7 @@
 #include <stdlib.h>
 
 #include "psg_common.h"
-
-typedef float af4 __attribute__((ext_vector_type(4)));
-
-// max / sum over the four 16-lane rows of a wave, result in every lane (v_permlane16_swap / v_permlane32_swap; inline
-// asm as in psg_gemm_f32.hip: the ROCm 7.2 builtin returns its first result twice, and an asm operand gets no hazard
-// padding from hipcc - s_nop covers VALU write -> permlane read)
-__device__ __forceinline__ float af_rows4_sum(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  const float s = a + b;
-  float c = s, d = s;
-  asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-  return c + d;
-}
-__device__ __forceinline__ float af_rows4_max(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 3\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  const float s = fmaxf(a, b);
-  float c = s, d = s;
-  asm volatile("s_nop 3\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-  return fmaxf(c, d);
-}
+#include "psg_wave.h"
 
 // The shared tile loop.  HD: head dim (64 / 128); NQT: query tiles (16 rows each) that share the key loop.
 //   qrow[t]   this lane's query row of tile t (row n = lane & 15), pointing at the head's first dim
@@ -64,13 +43,13 @@ __device__ __forceinline__ void af_tiles(const float* const (&qrow)[NQT], const 
                                          float scale, Mask mask, float* const (&out)[NQT]) {
   constexpr int NJ = HD / 16, NH = HD / 64, NDT = HD / 16;
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
-  af4 qf[NQT][NJ], acc[NQT][NDT];
+  psg_f32x4 qf[NQT][NJ], acc[NQT][NDT];
   float mrun[NQT], lrun[NQT];
-  const af4 zero = {0.f, 0.f, 0.f, 0.f};
+  const psg_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < NQT; ++t) {
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) qf[t][j] = *reinterpret_cast<const af4*>(qrow[t] + 16 * j + 4 * g);
+    for (int j = 0; j < NJ; ++j) qf[t][j] = *reinterpret_cast<const psg_f32x4*>(qrow[t] + 16 * j + 4 * g);
 #pragma unroll
     for (int d = 0; d < NDT; ++d) acc[t][d] = zero;
     mrun[t] = -INFINITY;
@@ -82,22 +61,22 @@ __device__ __forceinline__ void af_tiles(const float* const (&qrow)[NQT], const 
     const int32_t ki = keys[16 * kt + n];
     const int32_t* vk = keys + 16 * kt + 4 * g;
     const float* kp = kbase + (int64_t)ki * kstride + 4 * g;
-    af4 kf[NJ], vf[4][NH];
+    psg_f32x4 kf[NJ], vf[4][NH];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) kf[j] = *reinterpret_cast<const af4*>(kp + 16 * j);
+    for (int j = 0; j < NJ; ++j) kf[j] = *reinterpret_cast<const psg_f32x4*>(kp + 16 * j);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const bool live = 16 * kt + 4 * g + r < nk;                    // a listed key: its V row is defined
       const float* vp = vbase + (int64_t)vk[r] * kstride + 4 * n;
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        af4 v = *reinterpret_cast<const af4*>(vp + 64 * h);
+        psg_f32x4 v = *reinterpret_cast<const psg_f32x4*>(vp + 64 * h);
         vf[r][h] = live ? v : zero;                                  // 0 * NaN of an unwritten cache row would poison the row
       }
     }
 #pragma unroll
     for (int t = 0; t < NQT; ++t) {
-      af4 s = zero;
+      psg_f32x4 s = zero;
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -111,7 +90,7 @@ __device__ __forceinline__ void af_tiles(const float* const (&qrow)[NQT], const 
         s[r] = v;
         tmax = fmaxf(tmax, v);
       }
-      tmax = af_rows4_max(tmax);
+      tmax = psg_rows4_max(tmax);
       const float mnew = fmaxf(mrun[t], tmax);
       const bool none = mnew == -INFINITY;                           // nothing admitted so far for this row
       const float alpha = none ? 1.f : expf(mrun[t] - mnew);
@@ -121,7 +100,7 @@ __device__ __forceinline__ void af_tiles(const float* const (&qrow)[NQT], const 
         s[r] = none ? 0.f : expf(s[r] - mnew);
         psum += s[r];
       }
-      lrun[t] = lrun[t] * alpha + af_rows4_sum(psum);
+      lrun[t] = lrun[t] * alpha + psg_rows4_sum(psum);
       mrun[t] = mnew;
 #pragma unroll
       for (int d = 0; d < NDT; ++d) acc[t][d] *= alpha;
@@ -142,10 +121,10 @@ __device__ __forceinline__ void af_tiles(const float* const (&qrow)[NQT], const 
     for (int h = 0; h < NH; ++h)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        af4 o;
+        psg_f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = acc[t][4 * h + e][r] * inv;
-        *reinterpret_cast<af4*>(out[t] + 64 * h + 16 * g + 4 * r) = o;
+        *reinterpret_cast<psg_f32x4*>(out[t] + 64 * h + 16 * g + 4 * r) = o;
       }
   }
 }
@@ -356,17 +335,17 @@ __global__ void __launch_bounds__(256) qformer_self_attn_f32_kernel(const float*
   __builtin_amdgcn_wave_barrier();
   const int nrows = q_only == 2 ? 1 : (q_only ? nq : S);
   const float scale = 0.125f;
-  const af4 zero = {0.f, 0.f, 0.f, 0.f};
+  const psg_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   for (int r0 = 0; r0 < nrows; r0 += 32) {
     const bool two = r0 + 16 < nrows;                                  // a second query tile shares the key loop
-    af4 qf[2][4], acc[2][4];
+    psg_f32x4 qf[2][4], acc[2][4];
     float mrun[2], lrun[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int row = r0 + 16 * t + n;
       const float* qp = qkv + off[row < nrows ? row : nrows - 1] + h * 64 + 4 * g;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) qf[t][j] = *reinterpret_cast<const af4*>(qp + 16 * j);
+      for (int j = 0; j < 4; ++j) qf[t][j] = *reinterpret_cast<const psg_f32x4*>(qp + 16 * j);
 #pragma unroll
       for (int d = 0; d < 4; ++d) acc[t][d] = zero;
       mrun[t] = -INFINITY;
@@ -374,16 +353,16 @@ __global__ void __launch_bounds__(256) qformer_self_attn_f32_kernel(const float*
     }
     for (int kt = 0; kt < (up >> 4); ++kt) {
       const float* kp = qkv + off[keys[16 * kt + n]] + hidden + h * 64 + 4 * g;
-      af4 kf[4], vf[4];
+      psg_f32x4 kf[4], vf[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) kf[j] = *reinterpret_cast<const af4*>(kp + 16 * j);
+      for (int j = 0; j < 4; ++j) kf[j] = *reinterpret_cast<const psg_f32x4*>(kp + 16 * j);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        vf[r] = *reinterpret_cast<const af4*>(qkv + off[keys[16 * kt + 4 * g + r]] + 2 * hidden + h * 64 + 4 * n);
+        vf[r] = *reinterpret_cast<const psg_f32x4*>(qkv + off[keys[16 * kt + 4 * g + r]] + 2 * hidden + h * 64 + 4 * n);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (t == 1 && !two) continue;
-        af4 s = zero;
+        psg_f32x4 s = zero;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -394,7 +373,7 @@ __global__ void __launch_bounds__(256) qformer_self_attn_f32_kernel(const float*
           s[r] = 16 * kt + 4 * g + r < cnt ? s[r] * scale : -INFINITY;
           tmax = fmaxf(tmax, s[r]);
         }
-        tmax = af_rows4_max(tmax);
+        tmax = psg_rows4_max(tmax);
         const float mnew = fmaxf(mrun[t], tmax);                       // finite: every tile holds a listed key
         const float alpha = expf(mrun[t] - mnew);
         float psum = 0.f;
@@ -403,7 +382,7 @@ __global__ void __launch_bounds__(256) qformer_self_attn_f32_kernel(const float*
           s[r] = expf(s[r] - mnew);
           psum += s[r];
         }
-        lrun[t] = lrun[t] * alpha + af_rows4_sum(psum);
+        lrun[t] = lrun[t] * alpha + psg_rows4_sum(psum);
         mrun[t] = mnew;
 #pragma unroll
         for (int d = 0; d < 4; ++d) acc[t][d] *= alpha;
@@ -425,10 +404,10 @@ __global__ void __launch_bounds__(256) qformer_self_attn_f32_kernel(const float*
       const float inv = 1.0f / lrun[t];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        af4 o;
+        psg_f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = acc[t][e][r] * inv;
-        *reinterpret_cast<af4*>(op + 16 * g + 4 * r) = o;
+        *reinterpret_cast<psg_f32x4*>(op + 16 * g + 4 * r) = o;
       }
     }
   }
@@ -477,16 +456,16 @@ __global__ void __launch_bounds__(256) prefill_attn_f32_kernel(const float* __re
   float* orow = row < rpp ? out + ((int64_t)p * rpp + row) * hidden + h * 128 : nullptr;
   if (seen == 0) {                                                     // padding rows only: defined output, never consumed
     if (orow) {
-      const af4 zero = {0.f, 0.f, 0.f, 0.f};
+      const psg_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
       const int g = lane >> 4;
-      *reinterpret_cast<af4*>(orow + 16 * g) = zero;
-      *reinterpret_cast<af4*>(orow + 16 * g + 4) = zero;
-      *reinterpret_cast<af4*>(orow + 16 * g + 8) = zero;
-      *reinterpret_cast<af4*>(orow + 16 * g + 12) = zero;
-      *reinterpret_cast<af4*>(orow + 64 + 16 * g) = zero;
-      *reinterpret_cast<af4*>(orow + 64 + 16 * g + 4) = zero;
-      *reinterpret_cast<af4*>(orow + 64 + 16 * g + 8) = zero;
-      *reinterpret_cast<af4*>(orow + 64 + 16 * g + 12) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 16 * g) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 16 * g + 4) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 16 * g + 8) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 16 * g + 12) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 64 + 16 * g) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 64 + 16 * g + 4) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 64 + 16 * g + 8) = zero;
+      *reinterpret_cast<psg_f32x4*>(orow + 64 + 16 * g + 12) = zero;
     }
     return;
   }
@@ -498,12 +477,12 @@ __global__ void __launch_bounds__(256) prefill_attn_f32_kernel(const float* __re
   const AfCausal mk{pos >= 0 ? pos : 1 << 30};                         // a padding row of a mixed tile: any finite result
   af_tiles<128, 1>(q1, keys, nk, kc + cbase, vc + cbase, 128, 0.08838834764831845f, mk, o1);
   if (pos < 0 && orow) {                                               // padding rows of a mixed tile: zeros, as the scalar kernel
-    const af4 zero = {0.f, 0.f, 0.f, 0.f};
+    const psg_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int g = lane >> 4;
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) *reinterpret_cast<af4*>(orow + 64 * hh + 16 * g + 4 * r) = zero;
+      for (int r = 0; r < 4; ++r) *reinterpret_cast<psg_f32x4*>(orow + 64 * hh + 16 * g + 4 * r) = zero;
   }
 }
 

@@ -26,6 +26,7 @@
 // only - not on the other rows - so a pair's tokens do not depend on its batch neighbours as long as the row count's
 // plan is the same (tests: against the fp32 reference and against psg_skinny_gemm on <= 32 of the rows).
 #include "psg_common.h"
+#include "psg_wave.h"
 
 #define BG_BK 64
 #define BG_WAVES 8
@@ -33,23 +34,6 @@
 // ring depth.  Deeper rings where the LDS would hold them (4-6 units for the 128-row slabs / <= 96 rows of x) were measured
 // SLOWER (down projection at 160 rows: 35.0 -> 38.1 us, q|k|v at 40 rows: 26.3 -> 30.1): three units everywhere
 constexpr int bg_nst(int) { return 3; }
-
-template <int N_>
-__device__ __forceinline__ void bg_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-template <int N_>
-__device__ __forceinline__ void bg_lgkmwait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N_) : "memory");
-}
-__device__ __forceinline__ void bg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-typedef uint32_t bg_u32x4 __attribute__((ext_vector_type(4)));
-// (inline asm: beside a pending LDS-DMA hipcc puts s_waitcnt vmcnt(0) before every ds_read it emits itself)
-__device__ __forceinline__ bg_u32x4 bg_lds_read128(uint32_t a) {
-  bg_u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
-}
 
 // first workgroup whose unit range [i T / G, (i + 1) T / G) holds unit u
 __host__ __device__ static inline int bg_owner(int64_t u, int64_t T, int G) { return (int)(((u + 1) * G - 1) / T); }
@@ -137,7 +121,7 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
   }
 
   union Frag {
-    bg_u32x4 u;
+    psg_u32x4 u;
     v8 v;
   };
   psg_f32x16 acc[TI][TJ];
@@ -168,20 +152,20 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
   for (int64_t u = g0; u < g1; ++u) {
     // unit u landed?  loads complete in order: the younger unit's loads may stay outstanding
     const int ahead = issued - 1;                            // younger units in flight (<= NST - 2)
-    if (after_flush || ahead <= 0) bg_vmwait<0>();           // (stores of a flush may complete out of order with loads)
+    if (after_flush || ahead <= 0) psg_vmwait<0>();           // (stores of a flush may complete out of order with loads)
     else if (wid < REM) {
-      if (ahead == 1) bg_vmwait<PER + 1>();
-      else if (ahead == 2) bg_vmwait<2 * (PER + 1)>();
-      else if (ahead == 3) bg_vmwait<3 * (PER + 1)>();
-      else bg_vmwait<4 * (PER + 1)>();
+      if (ahead == 1) psg_vmwait<PER + 1>();
+      else if (ahead == 2) psg_vmwait<2 * (PER + 1)>();
+      else if (ahead == 3) psg_vmwait<3 * (PER + 1)>();
+      else psg_vmwait<4 * (PER + 1)>();
     } else {
-      if (ahead == 1) bg_vmwait<PER>();
-      else if (ahead == 2) bg_vmwait<2 * PER>();
-      else if (ahead == 3) bg_vmwait<3 * PER>();
-      else bg_vmwait<4 * PER>();
+      if (ahead == 1) psg_vmwait<PER>();
+      else if (ahead == 2) psg_vmwait<2 * PER>();
+      else if (ahead == 3) psg_vmwait<3 * PER>();
+      else psg_vmwait<4 * PER>();
     }
     after_flush = false;
-    bg_lds_barrier();                                        // unit u is in LDS; nobody reads the buffer of unit u - 1 any more
+    psg_lds_barrier();                                        // unit u is in LDS; nobody reads the buffer of unit u - 1 any more
     --issued;
     const bool pf = u + (NST - 1) < g1;
     int nb_ = buf + (NST - 1);
@@ -191,9 +175,9 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
     auto read_frags = [&](int sub, Frag (&a_)[TI], Frag (&b_)[TJ]) {
       const uint32_t piece = (uint32_t)(2 * sub + hi);
 #pragma unroll
-      for (int j = 0; j < TJ; ++j) b_[j].u = bg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
+      for (int j = 0; j < TJ; ++j) b_[j].u = psg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
 #pragma unroll
-      for (int i = 0; i < TI; ++i) a_[i].u = bg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
+      for (int i = 0; i < TI; ++i) a_[i].u = psg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
     };
     auto mma = [&](Frag (&a_)[TI], Frag (&b_)[TJ]) {
       if (var == 2) return;
@@ -207,22 +191,22 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
     read_frags(0, af[0], bf[0]);
     read_frags(1, af[1], bf[1]);
     if (pf) stage(pslab, pkt, nb_, 0, QH);
-    bg_lgkmwait<TI + TJ>();
+    psg_lgkmwait<TI + TJ>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
     mma(af[0], bf[0]);
     __builtin_amdgcn_sched_barrier(0);
     read_frags(2, af[0], bf[0]);
     if (pf) stage(pslab, pkt, nb_, QH, PER + 1);
-    bg_lgkmwait<TI + TJ>();
+    psg_lgkmwait<TI + TJ>();
     __builtin_amdgcn_sched_barrier(0);
     mma(af[1], bf[1]);
     __builtin_amdgcn_sched_barrier(0);
     read_frags(3, af[1], bf[1]);
-    bg_lgkmwait<TI + TJ>();
+    psg_lgkmwait<TI + TJ>();
     __builtin_amdgcn_sched_barrier(0);
     mma(af[0], bf[0]);
-    bg_lgkmwait<0>();
+    psg_lgkmwait<0>();
     __builtin_amdgcn_sched_barrier(0);
     mma(af[1], bf[1]);
     __builtin_amdgcn_s_setprio(0);

@@ -187,6 +187,8 @@ struct Act<f16_t> {
 typedef float psg_f32x16 __attribute__((ext_vector_type(16)));
 typedef float psg_f32x4 __attribute__((ext_vector_type(4)));
 typedef float psg_f32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t psg_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t psg_u32x2 __attribute__((ext_vector_type(2)));
 struct EBf16 {
   using act = bf16_t;
   typedef __bf16 v8 __attribute__((ext_vector_type(8)));
@@ -257,7 +259,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += psg_dpp<0x143, 0xc>(0.f, v);   // row_bcast:31 into rows 2 and 3 -> lane 63 = the wave's sum
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
-__device__ __forceinline__ float wave_sum_dpp(float v) { return wave_sum(v); }
 __device__ __forceinline__ float wave_max(float v) {               // lanes without a source keep their own value
   v = fmaxf(v, psg_dpp<0x111, 0xf>(v, v));
   v = fmaxf(v, psg_dpp<0x112, 0xf>(v, v));
@@ -351,8 +352,7 @@ __device__ __forceinline__ void ldn_splits(const void* __restrict__ in, int S, i
 // 16-byte store written through the L2 (agent scope: sc1) - a kernel whose outputs are all stored this way leaves no dirty
 // line behind for the release at its end
 __device__ __forceinline__ void psg_st4_wt(float* p, float a, float b, float c, float d) {
-  typedef float psg_wt_f4 __attribute__((ext_vector_type(4)));
-  const psg_wt_f4 v = {a, b, c, d};
+  const psg_f32x4 v = {a, b, c, d};
   asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 

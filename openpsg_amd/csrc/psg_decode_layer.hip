@@ -36,6 +36,7 @@
 
 #include "psg_common.h"
 #include "psg_decode_math.h"
+#include "psg_wave.h"
 
 #define PSG_DL_WG 256
 #define PSG_DL_WAVES 12      // waves per workgroup; a projection streams with W <= 12 of them (its slab = 16 W rows)
@@ -54,8 +55,6 @@
 #define PSG_DL_SLOT 64         // words per slot
 #define PSG_DL_NCNT (256 * PSG_DL_SLOT)
 
-typedef float df32x4_t __attribute__((ext_vector_type(4)));
-typedef float df32x16_t __attribute__((ext_vector_type(16)));
 typedef unsigned long long du64;
 
 struct psg_dl_layer {          // one decoder layer's tensors (psg_decode_layers: an array of these in device memory)
@@ -122,12 +121,10 @@ __device__ __forceinline__ float2 dl_ld2(const float* p) {
 __device__ __forceinline__ float dl_ld1(const float* p) {
   return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
-__device__ __forceinline__ void dl_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void dl_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-// publish: every wave has drained its stores (dl_drain) BEFORE it comes here; ONE lane counts the workgroup in
+// publish: every wave has drained its stores (psg_vmwait<0>) BEFORE it comes here; ONE lane counts the workgroup in
 __device__ __forceinline__ void dl_publish(unsigned* cnt, int slot, unsigned n = 1u) {
-  dl_barrier();
+  psg_lds_barrier();
   if (dl_tid() == 0) __hip_atomic_fetch_add(cnt + slot * PSG_DL_SLOT, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ bool dl_poll(unsigned* cnt, int slot, unsigned want) {
@@ -152,13 +149,13 @@ __device__ __forceinline__ void dl_wait(unsigned* cnt, int first, int nw, unsign
       }
     }
   }
-  dl_barrier();
+  psg_lds_barrier();
 }
 // All-to-all edge (every workgroup waits for every workgroup): XCD-hierarchical (MI355X_MICROARCH.md barrier-xcd) - the
 // workgroups of a b % 8 class count into their own slot, the last of a class counts into the top slot, the last of those
 // raises the eight go flags, and a workgroup polls the flag of ITS class only (32 pollers per line instead of 256).
 __device__ __forceinline__ void dl_arrive_all(unsigned* cnt, int base) {       // stores drained by the caller
-  dl_barrier();
+  psg_lds_barrier();
   if (dl_tid() == 0) {
     const int cls = dl_bid() & 7;
     if (__hip_atomic_fetch_add(cnt + (base + cls) * PSG_DL_SLOT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == PSG_DL_WG / 8 - 1)
@@ -168,39 +165,6 @@ __device__ __forceinline__ void dl_arrive_all(unsigned* cnt, int base) {       /
   }
 }
 __device__ __forceinline__ void dl_wait_all(unsigned* cnt, int base) { dl_wait(cnt, base + 9 + (dl_bid() & 7), 1, 1u); }
-
-// sum over the four 16-lane rows (psg_gemm_f32.hip: sgf_sum_kq)
-__device__ __forceinline__ float dl_sum_kq(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 7\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  const float s = a + b;
-  float c = s, d = s;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-  return c + d;
-}
-__device__ __forceinline__ void dl_ds_write128(uint32_t lds_addr, df32x4_t v) {
-  asm volatile("s_nop 15\n\tds_write_b128 %0, %1" ::"v"(lds_addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ df32x4_t dl_ds_read128(uint32_t lds_addr) {
-  df32x4_t v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-template <int N_>
-__device__ __forceinline__ void dl_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-template <int MAXN>
-struct DlWait {
-  static __device__ __forceinline__ void go(int newer) {
-    if (newer >= MAXN) dl_vmwait<(MAXN * 2 < 63 ? MAXN * 2 : 63)>();
-    else DlWait<MAXN - 1>::go(newer);
-  }
-};
-template <>
-struct DlWait<0> {
-  static __device__ __forceinline__ void go(int) { dl_vmwait<0>(); }
-};
 
 #define DL_XPAD 16
 #define DL_BLOCK 2048                                                   // 16 rows x 128 B of one wave's ring slot
@@ -301,10 +265,10 @@ struct DlGemm {
     for (int q = 0; q < G4; ++q) x4[q] = xs + min(16 * G16 + 4 * q + (lane & 3), M - 1) * xstride + kq * 32;
     const int arow = (n >> 3) * 1024 + (n & 7) * 128;
     const int a0off = arow + (((2 * kq) ^ (n & 7)) * 16), a1off = arow + (((2 * kq + 1) ^ (n & 7)) * 16);
-    const df32x4_t zero4 = {0, 0, 0, 0};
-    const df32x16_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    df32x16_t acc16[NG16];
-    df32x4_t acc4[NG4];
+    const psg_f32x4 zero4 = {0, 0, 0, 0};
+    const psg_f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    psg_f32x16 acc16[NG16];
+    psg_f32x4 acc4[NG4];
 #pragma unroll
     for (int g = 0; g < G16; ++g) acc16[g] = zero16;
 #pragma unroll
@@ -316,32 +280,32 @@ struct DlGemm {
 #pragma unroll
         for (int q = 0; q < G4; ++q)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc4[q][r] = dl_sum_kq(acc4[q][r]);
+          for (int r = 0; r < 4; ++r) acc4[q][r] = psg_rows4_sum_mfma(acc4[q][r]);
       }
-      dl_barrier();                                                   // previous slab's tile fully read
+      psg_lds_barrier();                                                   // previous slab's tile fully read
       if (streams) {
         const uint32_t tp16 = otile_lds + (uint32_t)(n * OT_PITCH + wid * 16 + 4 * kq) * 4u;
 #pragma unroll
         for (int g = 0; g < G16; ++g) {
-          df32x4_t v;
+          psg_f32x4 v;
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = (acc16[g][r] + acc16[g][4 + r]) + (acc16[g][8 + r] + acc16[g][12 + r]);
-          dl_ds_write128(tp16 + (uint32_t)(16 * g * OT_PITCH) * 4u, v);
+          psg_lds_write128_mfma(tp16 + (uint32_t)(16 * g * OT_PITCH) * 4u, v);
         }
         const int g4 = (lane >> 2) & 3, j = lane & 3;
         const uint32_t tp4 = otile_lds + (uint32_t)((16 * G16 + j) * OT_PITCH + wid * 16 + 4 * g4) * 4u;
 #pragma unroll
         for (int q = 0; q < G4; ++q)
-          if (kq == (q & 3)) dl_ds_write128(tp4 + (uint32_t)(4 * q * OT_PITCH) * 4u, acc4[q]);
+          if (kq == (q & 3)) psg_lds_write128_mfma(tp4 + (uint32_t)(4 * q * OT_PITCH) * 4u, acc4[q]);
       }
-      dl_barrier();
+      psg_lds_barrier();
       {
         const int nblk = (gx + ct * G) * ROWS;
         constexpr int C4 = ROWS / 4;
         for (int e = tid; e < M * C4; e += PSG_DL_WAVES * 64) {
           const int m = e / C4, c4 = e - m * C4;
           if (nblk + c4 * 4 + 4 <= N) {
-            const df32x4_t v = dl_ds_read128(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
+            const psg_f32x4 v = psg_lds_read128_wait(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
             float* dst = part + ((int64_t)by * M + m) * N + nblk + c4 * 4;
             dl_st2(dst, v[0], v[1]);
             dl_st2(dst + 2, v[2], v[3]);
@@ -365,18 +329,18 @@ struct DlGemm {
     }
     for (int j = 0; j < total; ++j) {
       if (j + SLOTS - 1 < total) issue();
-      DlWait<SLOTS - 1>::go(total - 1 - j);
+      PsgDmaWait<2, SLOTS - 1>::go(total - 1 - j);
       const unsigned char* slot = ring + cs * DL_BLOCK;
       if (++cs == SLOTS) cs = 0;
       const int o = cb * 128;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const df32x4_t a = *reinterpret_cast<const df32x4_t*>(slot + (h ? a1off : a0off));
-        df32x4_t b16[NG16], b4[NG4];
+        const psg_f32x4 a = *reinterpret_cast<const psg_f32x4*>(slot + (h ? a1off : a0off));
+        psg_f32x4 b16[NG16], b4[NG4];
 #pragma unroll
-        for (int g = 0; g < G16; ++g) b16[g] = *reinterpret_cast<const df32x4_t*>(x16[g] + o + 16 * h);
+        for (int g = 0; g < G16; ++g) b16[g] = *reinterpret_cast<const psg_f32x4*>(x16[g] + o + 16 * h);
 #pragma unroll
-        for (int q = 0; q < G4; ++q) b4[q] = *reinterpret_cast<const df32x4_t*>(x4[q] + o + 16 * h);
+        for (int q = 0; q < G4; ++q) b4[q] = *reinterpret_cast<const psg_f32x4*>(x4[q] + o + 16 * h);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -385,7 +349,7 @@ struct DlGemm {
           for (int q = 0; q < G4; ++q) acc4[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(a[i], b4[q][i], acc4[q], 0, 0, 0);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      psg_lgkmwait<0>();
       if (++cb == nkb) finish_slab();
     }
   }
@@ -465,7 +429,7 @@ __device__ __forceinline__ void dl_norm_stage(const psg_dl_args& a, const float*
     for (int w = 0; w < 16; ++w) tot += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r), 4 * w + 3));
     if (lane == 0) s_inv[m] = 1.0f / sqrtf(tot / (float)a.D + a.eps);
   }
-  dl_barrier();
+  psg_lds_barrier();
 #pragma unroll
   for (int k = 0; k < MAXE; ++k)
     if (off[k] >= 0) {
@@ -586,7 +550,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
     dl_wait(cnt - PSG_DL_NCNT, PSG_DL_CNT_DGRP + ((b >> 3) & 15), 1, 16u);
   }
   dl_norm_owner(a, delta, dsplits, a.ssq, b);
-  dl_drain();
+  psg_vmwait<0>();
   dl_arrive_all(cnt, PSG_DL_CNT_X1);
   DL_STAMP(1);
   dl_wait_all(cnt, PSG_DL_CNT_X1);
@@ -596,7 +560,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
     g.setup(T->wqkv, 3 * D, D, 8, b & 7, b >> 3, M, smem);
     g.skip_prefetched();
     dl_norm_stage(a, a.ssq, T->ln1, g.kbA, g.nkb, g.xstride, xs, s_inv);
-    dl_barrier();
+    psg_lds_barrier();
     DL_STAMP(3);
     g.run(a.qkv_part, smem, xs);
   }
@@ -605,7 +569,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
   {
     GemmO go;
     go.setup(T->wo, D, D, 8, b & 7, b >> 3, M, smem);
-    dl_drain();                                                     // this wave's partial-tile stores are out
+    psg_vmwait<0>();                                                // this wave's partial-tile stores are out
     go.prefetch();                                                  // its own ring is free: the next stream starts now
   }
   dl_publish(cnt, PSG_DL_CNT_HEAD + (b >> 3));
@@ -619,8 +583,8 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
       const int u = u0 + (wid >> 2);
       const DlAttnArgs aa = {a.qkv_part, a.att, T->kc, T->vc, a.tok_pair, a.tok_pos, a.cos_tab, a.sin_tab, cnt, a.M, a.D, a.heads, a.ctx};
       dl_attn_round(aa, u < nunit ? u : -1, sc);
-      dl_drain();
-      dl_barrier();
+      psg_vmwait<0>();
+      psg_lds_barrier();
       if ((tid & 255) == 0 && u < nunit)
         __hip_atomic_fetch_add(cnt + (PSG_DL_CNT_ATT + ((u % a.heads) >> 2)) * PSG_DL_SLOT, 1u, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
@@ -636,8 +600,8 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
     go.setup(T->wo, D, D, 8, b & 7, b >> 3, M, smem);
     go.skip_prefetched();
     go.stage_x_dma(a.att, D, xs);
-    dl_drain();
-    dl_barrier();
+    psg_vmwait<0>();
+    psg_lds_barrier();
     DL_STAMP(8);
     go.run(a.o_part, smem, xs);
   }
@@ -645,7 +609,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
   {
     GemmG gg;
     gg.setup(T->wgu, 2 * I, D, 8, b & 7, b >> 3, M, smem);
-    dl_drain();
+    psg_vmwait<0>();
     gg.prefetch();
   }
   dl_publish(cnt, PSG_DL_CNT_OSLAB + (b >> 3));
@@ -654,7 +618,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
   dl_wait(cnt, PSG_DL_CNT_OSLAB + (b >> 3), 1, 8u);
   DL_STAMP(10);
   dl_norm_owner(a, a.o_part, 8, a.ssq + PSG_DL_WG * 32, b);
-  dl_drain();
+  psg_vmwait<0>();
   dl_arrive_all(cnt, PSG_DL_CNT_X2);
   DL_STAMP(11);
   dl_wait_all(cnt, PSG_DL_CNT_X2);
@@ -664,7 +628,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
     gg.setup(T->wgu, 2 * I, D, 8, b & 7, b >> 3, M, smem);
     gg.skip_prefetched();
     dl_norm_stage(a, a.ssq + PSG_DL_WG * 32, T->ln2, gg.kbA, gg.nkb, gg.xstride, xs, s_inv);
-    dl_barrier();
+    psg_lds_barrier();
     DL_STAMP(13);
     gg.run(a.gu_part, smem, xs);
   }
@@ -672,7 +636,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
   {
     GemmO gd;
     gd.setup(T->wdown, D, I, 16, b & 15, b >> 4, M, smem);
-    dl_drain();
+    psg_vmwait<0>();
     gd.prefetch();
   }
   dl_publish(cnt, PSG_DL_CNT_GU + (b >> 3));
@@ -705,7 +669,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
           }
         }
       }
-      dl_barrier();
+      psg_lds_barrier();
       if (liv) {
         const int c = j * 128 + 2 * lane;
         const int64_t ig = (int64_t)m * 2 * I + c, iu = ig + I;
@@ -720,7 +684,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
         for (int s = 1; s < 8; ++s) { gsum.x += tg[s].x; gsum.y += tg[s].y; usum.x += tu[s].x; usum.y += tu[s].y; }
         const float s0 = gsum.x / (1.0f + expf(-gsum.x)), s1 = gsum.y / (1.0f + expf(-gsum.y));
         dl_st2(a.h + (int64_t)m * I + c, s0 * usum.x, s1 * usum.y);
-        dl_drain();
+        psg_vmwait<0>();
         if (lane == 0)
           __hip_atomic_fetch_add(cnt + (PSG_DL_CNT_H + j) * PSG_DL_SLOT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
@@ -737,8 +701,8 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
     dl_wait(cnt, PSG_DL_CNT_H + j0, j1 - j0, (unsigned)M);
     DL_STAMP(16);
     gd.stage_x_dma(a.h, I, xs);
-    dl_drain();
-    dl_barrier();
+    psg_vmwait<0>();
+    psg_lds_barrier();
     DL_STAMP(17);
     gd.run(down_part, smem, xs);
   }
@@ -746,7 +710,7 @@ __global__ void __launch_bounds__(PSG_DL_WAVES * 64) decode_layer_f32_kernel(con
   if (l + 1 < nl) {                                                 // chain: next layer's first q|k|v blocks, then count in
     GemmQ g;
     g.setup(T[1].wqkv, 3 * D, D, 8, b & 7, b >> 3, M, smem);
-    dl_drain();
+    psg_vmwait<0>();
     g.prefetch();
     dl_publish(cnt, PSG_DL_CNT_DGRP + (b >> 4));
   }

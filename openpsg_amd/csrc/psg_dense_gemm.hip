@@ -26,6 +26,7 @@
 // tile's 128 FLOP/B), the matrix phase alone 1.24 PFLOP/s; walking K from a tile-dependent offset (to de-phase
 // workgroups that share a panel) was measured slower: the shared bursts are L2 hits.
 #include "psg_common.h"
+#include "psg_wave.h"
 
 #define DG_BK 64
 
@@ -42,24 +43,6 @@ __device__ __forceinline__ float dg_gelu(float v) {
   const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
   const float erf_abs = fmaf(-poly * t, e, 1.0f);
   return 0.5f * v * (1.0f + copysignf(erf_abs, x));
-}
-
-template <int N_>
-__device__ __forceinline__ void dg_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-template <int N_>
-__device__ __forceinline__ void dg_lgkmwait() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N_) : "memory");
-}
-__device__ __forceinline__ void dg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// Fragment reads are inline asm: next to a pending LDS-DMA hipcc makes every ds_read it generates itself wait
-// vmcnt(0) first (the DMA is an LDS write that may alias), which would serialise the prefetch behind the reads.
-typedef uint32_t dg_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dg_u32x4 dg_lds_read128(uint32_t a) {
-  dg_u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
 }
 
 // VAR (ablation builds): 0 normal, 1 no MFMA, 2 no staging after the first K tile.  OUT32: fp32 output
@@ -181,7 +164,7 @@ dense_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
     bswz[j] = (uint32_t)((r >> 1) & 7);
   }
   union Frag {
-    dg_u32x4 u;
+    psg_u32x4 u;
     v8 v;
   };
   for (;;) {
@@ -206,8 +189,8 @@ dense_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
       const bool more_k = kt + 1 < nk;
       const bool pf = VAR != 2 && (more_k || has_next);
       const int pm0 = more_k ? m0 : mbn * BM, pn0 = more_k ? n0 : nbn * BN, pkt = more_k ? kt + 1 : 0;
-      dg_vmwait<0>();                                       // tile kt landed (requested during the previous K step)
-      dg_lds_barrier();                                     // every wave's part of tile kt is in LDS; nobody reads buf ^ 1 any more
+      psg_vmwait<0>();                                       // tile kt landed (requested during the previous K step)
+      psg_lds_barrier();                                     // every wave's part of tile kt is in LDS; nobody reads buf ^ 1 any more
       const uint32_t base = smem_lds + (uint32_t)(buf * BUF_BYTES);
       // four sub-steps of 16 in k, TI x TJ MFMAs (32 x 32 x 16) each; the TI + TJ fragment reads of sub-step s+1 are
       // issued before the MFMAs of sub-step s; the DMAs of the next K tile are issued beside sub-steps 0 and 1
@@ -215,9 +198,9 @@ dense_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
       auto read_frags = [&](int sub, Frag (&a_)[TI], Frag (&b_)[TJ]) {
         const uint32_t piece = (uint32_t)(2 * sub + hi);    // 16-byte piece (8 elements) of the 128-byte row
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) b_[j].u = dg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
+        for (int j = 0; j < TJ; ++j) b_[j].u = psg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
 #pragma unroll
-        for (int i = 0; i < TI; ++i) a_[i].u = dg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
+        for (int i = 0; i < TI; ++i) a_[i].u = psg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
       };
 #define DG_MMA(AF, BF)                                                                            \
   _Pragma("unroll") for (int i = 0; i < TI; ++i) _Pragma("unroll") for (int j = 0; j < TJ; ++j) {  \
@@ -233,42 +216,42 @@ dense_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
         auto read_a = [&](int sub, Frag (&a_)[TI]) {
           const uint32_t piece = (uint32_t)(2 * sub + hi);
 #pragma unroll
-          for (int i = 0; i < TI; ++i) a_[i].u = dg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
+          for (int i = 0; i < TI; ++i) a_[i].u = psg_lds_read128(base + arow[i] + ((piece ^ aswz[i]) << 4));
         };
         auto read_b = [&](int sub, Frag (&b_)[TJ]) {
           const uint32_t piece = (uint32_t)(2 * sub + hi);
 #pragma unroll
-          for (int j = 0; j < TJ; ++j) b_[j].u = dg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
+          for (int j = 0; j < TJ; ++j) b_[j].u = psg_lds_read128(base + brow[j] + ((piece ^ bswz[j]) << 4));
         };
         read_frags(0, af[0], bf[0]);
         read_frags(1, af[1], bf[1]);
         if (pf) stage_x(pm0, pkt, buf ^ 1);
-        dg_lgkmwait<TI + TJ>();
+        psg_lgkmwait<TI + TJ>();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         DG_MMA(af[0], bf[0])                                  // xh . wh, k 0..15
         __builtin_amdgcn_sched_barrier(0);
         read_b(2, bl[0]);
         if (pf) stage_w(pn0, pkt, buf ^ 1);
-        dg_lgkmwait<TJ>();
+        psg_lgkmwait<TJ>();
         __builtin_amdgcn_sched_barrier(0);
         DG_MMA(af[1], bf[1])                                  // xh . wh, k 16..31
         __builtin_amdgcn_sched_barrier(0);
         read_b(3, bl[1]);
-        dg_lgkmwait<TJ>();
+        psg_lgkmwait<TJ>();
         __builtin_amdgcn_sched_barrier(0);
         DG_MMA(af[0], bl[0])                                  // xh . wl, k 0..15
         __builtin_amdgcn_sched_barrier(0);
         read_a(2, af[0]);
-        dg_lgkmwait<TI>();
+        psg_lgkmwait<TI>();
         __builtin_amdgcn_sched_barrier(0);
         DG_MMA(af[1], bl[1])                                  // xh . wl, k 16..31
         __builtin_amdgcn_sched_barrier(0);
         read_a(3, af[1]);
-        dg_lgkmwait<TI>();
+        psg_lgkmwait<TI>();
         __builtin_amdgcn_sched_barrier(0);
         DG_MMA(af[0], bf[0])                                  // xl . wh, k 0..15
-        dg_lgkmwait<0>();
+        psg_lgkmwait<0>();
         __builtin_amdgcn_sched_barrier(0);
         DG_MMA(af[1], bf[1])                                  // xl . wh, k 16..31
         __builtin_amdgcn_s_setprio(0);
@@ -276,22 +259,22 @@ dense_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
       read_frags(0, af[0], bf[0]);
       read_frags(1, af[1], bf[1]);
       if (pf) stage_x(pm0, pkt, buf ^ 1);
-      dg_lgkmwait<TI + TJ>();
+      psg_lgkmwait<TI + TJ>();
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
       DG_MMA(af[0], bf[0])
       __builtin_amdgcn_sched_barrier(0);
       read_frags(2, af[0], bf[0]);
       if (pf) stage_w(pn0, pkt, buf ^ 1);
-      dg_lgkmwait<TI + TJ>();
+      psg_lgkmwait<TI + TJ>();
       __builtin_amdgcn_sched_barrier(0);
       DG_MMA(af[1], bf[1])
       __builtin_amdgcn_sched_barrier(0);
       read_frags(3, af[1], bf[1]);
-      dg_lgkmwait<TI + TJ>();
+      psg_lgkmwait<TI + TJ>();
       __builtin_amdgcn_sched_barrier(0);
       DG_MMA(af[0], bf[0])
-      dg_lgkmwait<0>();
+      psg_lgkmwait<0>();
       __builtin_amdgcn_sched_barrier(0);
       DG_MMA(af[1], bf[1])
       __builtin_amdgcn_s_setprio(0);

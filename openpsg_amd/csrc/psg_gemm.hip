@@ -41,8 +41,7 @@
 #include <vector>
 
 #include "psg_common.h"
-
-typedef float gf32x4_t __attribute__((ext_vector_type(4)));
+#include "psg_wave.h"
 
 #define SG_ROWS 64      // weight rows per workgroup (4 waves x 16)
 #define SG_U 4          // K blocks per register set
@@ -64,7 +63,7 @@ __device__ __forceinline__ void sg_load(SgFrag<E>& f, const uint16_t* __restrict
 
 template <typename E>
 __device__ __forceinline__ void sg_mma(const SgFrag<E>& f, const unsigned char* xs0, const unsigned char* xs1, int kbl,
-                                       gf32x4_t& acc0, gf32x4_t& acc1) {
+                                       psg_f32x4& acc0, psg_f32x4& acc1) {
   using gbf16x8_t = typename E::v8;
 #pragma unroll
   for (int u = 0; u < SG_U; ++u) {
@@ -122,7 +121,7 @@ __global__ void __launch_bounds__(256) skinny_gemm_kernel(const uint16_t* __rest
   // x rows >= M are clamped: they only feed output columns >= M, which are never stored
   const unsigned char* xs0 = xs + min(n, M - 1) * xstride + kq * 32;
   const unsigned char* xs1 = xs + min(16 + n, M - 1) * xstride + kq * 32;
-  gf32x4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  psg_f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
   int ct = 0, cb = 0;                                               // compute cursor
   auto finish_slab = [&]() {
     const uint16_t* wp = wrow(ct);
@@ -143,8 +142,8 @@ __global__ void __launch_bounds__(256) skinny_gemm_kernel(const uint16_t* __rest
       if (16 + n < M)
         *reinterpret_cast<float4*>(pp + (int64_t)(16 + n) * N) = make_float4(acc1[0], acc1[1], acc1[2], acc1[3]);
     }
-    acc0 = (gf32x4_t){0, 0, 0, 0};
-    acc1 = (gf32x4_t){0, 0, 0, 0};
+    acc0 = (psg_f32x4){0, 0, 0, 0};
+    acc1 = (psg_f32x4){0, 0, 0, 0};
     cb = 0;
     ++ct;
   };
@@ -172,37 +171,9 @@ __global__ void __launch_bounds__(256) skinny_gemm_kernel(const uint16_t* __rest
 // (row n, piece c) looks at slot c ^ (n & 7).  Each wave owns a private 3-slot ring of
 // UD-K-block batches; the only synchronisation is the issuing wave's own counted vmcnt.
 // ---------------------------------------------------------------------------------------------
-// Workgroup barrier for LDS traffic only.  __syncthreads() would also drain the vector-memory counter whenever an
-// LDS-DMA is in flight (the DMA is a pending LDS write to the compiler): at every slab end the whole prefetch ring
-// would be waited for and the weight stream would stall.  Ordering of the partial tile needs lgkmcnt only.
-__device__ __forceinline__ void sgd_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void sgd_ds_write128(uint32_t lds_addr, gf32x4_t v) {
-  // v holds MFMA results: the matrix-core -> LDS-store wait states are not inserted for an asm consumer
-  asm volatile("s_nop 15\n\tds_write_b128 %0, %1" ::"v"(lds_addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ gf32x4_t sgd_ds_read128(uint32_t lds_addr) {
-  gf32x4_t v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-
-template <int N_>
-__device__ __forceinline__ void sgd_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-// wait until at most `newer` batches (2*UD DMA instructions each) issued after the wanted one are outstanding
-template <int UD, int MAXN>
-struct SgdWait {
-  static __device__ __forceinline__ void go(int newer) {
-    if (newer >= MAXN) sgd_wait<(MAXN * 2 * UD < 63 ? MAXN * 2 * UD : 63)>();
-    else SgdWait<UD, MAXN - 1>::go(newer);
-  }
-};
-template <int UD>
-struct SgdWait<UD, 0> {
-  static __device__ __forceinline__ void go(int) { sgd_wait<0>(); }
-};
+// The partial tile's barriers and LDS traffic are psg_lds_barrier / psg_lds_*128_* (psg_wave.h): nothing the compiler
+// could order against the pending DMAs; the ring is waited for through PsgDmaWait<2 * UD, slots - 1> (2 * UD DMA
+// instructions per batch).
 
 // ---- row-operation prologues of the fused decode projections (psg_skinny_gemm_fused) ------------------------------
 // Outputs that other workgroups of the same launch read (the x operand) are stored WRITE-THROUGH: 8-byte relaxed
@@ -386,7 +357,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
     }
     if (tr && lane == 0) tr[6] = __builtin_readcyclecounter();      // row operation computed (or nothing to do)
     // publish: every storing wave drains its write-through stores, then ONE lane counts the workgroup's units in
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    psg_vmwait<0>();
     __syncthreads();
     if (tid == 0 && units) __hip_atomic_fetch_add(pro.sync, units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // consume: one wave polls the ONE counter (relaxed, agent scope), bounded; x is then read with sc1 loads
@@ -432,7 +403,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
         if (off[u] >= 0) *reinterpret_cast<uint4*>(xs + off[u]) = v[u];
     }
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's x rows (and first weight batches) landed
+    psg_vmwait<0>();                                                 // this wave's x rows (and first weight batches) landed
   }
   __syncthreads();
   if (tr && lane == 0) tr[2] = __builtin_readcyclecounter();
@@ -442,7 +413,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
   // fragment (row n, piece c = 2 kq + j) sits at slot c ^ (n & 7) of row n
   const int arow = (n >> 3) * 1024 + (n & 7) * 128;
   const int a0off = arow + (((2 * kq) ^ (n & 7)) * 16), a1off = arow + (((2 * kq + 1) ^ (n & 7)) * 16);
-  gf32x4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  psg_f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
   int ct = 0, cb = 0;
   auto finish_slab = [&]() {
     int r = (gx + ct * G) * ROWS + wid * 16 + n;
@@ -462,26 +433,26 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
     // The tile's LDS traffic is written as inline asm: to hipcc a pending LDS-DMA is a pending LDS write that may
     // alias ANY ds access it generates itself, so a compiler-visible ds_write / ds_read here waits vmcnt(0) first
     // and the prefetched weight batches of the next slab drain at every slab end.
-    sgd_lds_barrier();                                              // previous slab's tile fully read
+    psg_lds_barrier();                                              // previous slab's tile fully read
     {
       const uint32_t tp = otile_lds + (uint32_t)(wid * 16 + 4 * kq) * 4u;
-      if (n < M) sgd_ds_write128(tp + (uint32_t)(n * OT_PITCH) * 4u, acc0);
-      if (16 + n < M) sgd_ds_write128(tp + (uint32_t)((16 + n) * OT_PITCH) * 4u, acc1);
+      if (n < M) psg_lds_write128_mfma(tp + (uint32_t)(n * OT_PITCH) * 4u, acc0);
+      if (16 + n < M) psg_lds_write128_mfma(tp + (uint32_t)((16 + n) * OT_PITCH) * 4u, acc1);
     }
-    sgd_lds_barrier();
+    psg_lds_barrier();
     {
       const int nblk = (gx + ct * G) * ROWS;
       constexpr int C4 = ROWS / 4;                                  // float4 columns per row
       for (int e = tid; e < M * C4; e += WAVES * 64) {
         const int m = e / C4, c4 = e - m * C4;
         if (nblk + c4 * 4 + 4 <= N) {
-          const gf32x4_t v = sgd_ds_read128(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
+          const psg_f32x4 v = psg_lds_read128_wait(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
           *reinterpret_cast<float4*>(part + ((int64_t)by * M + m) * N + nblk + c4 * 4) = make_float4(v[0], v[1], v[2], v[3]);
         }
       }
     }
-    acc0 = (gf32x4_t){0, 0, 0, 0};
-    acc1 = (gf32x4_t){0, 0, 0, 0};
+    acc0 = (psg_f32x4){0, 0, 0, 0};
+    acc1 = (psg_f32x4){0, 0, 0, 0};
     cb = 0;
     ++ct;
   };
@@ -491,7 +462,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
   }
   for (int j = 0; j < total; ++j) {
     if (j + SGD_SLOTS - 1 < total) issue();                         // refills the slot consumed at j - 1
-    SgdWait<UD, SGD_SLOTS - 1>::go(total - 1 - j);                  // batches issued after batch j may stay in flight
+    PsgDmaWait<2 * UD, SGD_SLOTS - 1>::go(total - 1 - j);           // batches issued after batch j may stay in flight
     if (tr && lane == 0 && j == 0) tr[3] = __builtin_readcyclecounter();
     const unsigned char* slot = ring + (j % SGD_SLOTS) * BATCH_BYTES;
 #pragma unroll
@@ -508,14 +479,14 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_dma_kernel(const uint1
       acc0 = E::mfma16(a1, b01, acc0);
       acc1 = E::mfma16(a1, b11, acc1);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // ring reads retired before the slot is refilled
+    psg_lgkmwait<0>();                                               // ring reads retired before the slot is refilled
     if (++cb == nb) {
       if (tr && lane == 0 && ct == nslab - 1) tr[4] = __builtin_readcyclecounter();
       finish_slab();
     }
   }
   if (tr && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    psg_vmwait<0>();
     tr[5] = __builtin_readcyclecounter();
     if constexpr (PRO == 0) {
       tr[6] = nslab;

@@ -48,53 +48,7 @@
 #include <type_traits>
 
 #include "psg_common.h"
-
-typedef float sf32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void sgf_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// The partial tile's LDS traffic is inline asm for the reason given in psg_gemm.hip: to hipcc a pending LDS-DMA may
-// alias any ds access it generates itself, and it would drain the prefetch ring at every slab end.
-__device__ __forceinline__ void sgf_ds_write128(uint32_t lds_addr, sf32x4_t v) {
-  asm volatile("s_nop 15\n\tds_write_b128 %0, %1" ::"v"(lds_addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ sf32x4_t sgf_ds_read128(uint32_t lds_addr) {
-  sf32x4_t v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-template <int N_>
-__device__ __forceinline__ void sgf_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-// wait until at most `newer` blocks (2 DMA instructions each) issued after the wanted one are outstanding
-template <int MAXN, int PER = 2>
-struct SgfWait {
-  static __device__ __forceinline__ void go(int newer) {
-    if (newer >= MAXN) sgf_wait<(MAXN * PER < 63 ? MAXN * PER : 63)>();
-    else SgfWait<MAXN - 1, PER>::go(newer);
-  }
-};
-template <int PER>
-struct SgfWait<0, PER> {
-  static __device__ __forceinline__ void go(int) { sgf_wait<0>(); }
-};
-
-// sum over the four 16-lane rows of a wave (= the four kq partials of an output), in every lane: (kq0 + kq1) + (kq2 + kq3).
-// v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second, v_permlane32_swap
-// the upper half of the first with the lower half of the second; fed two copies of a value they leave "this row pair's
-// first" / "second" in the two registers.  Inline asm: ROCm 7.2's __builtin_amdgcn_permlane16_swap returns its FIRST
-// result in both vector elements (v_add_f32 v1, v1, v1 in the ISA), and an asm operand gets no hazard padding from
-// hipcc - the s_nop covers matrix-core result -> VALU read (2-pass MFMA: 5 wait states) and VALU write -> permlane read.
-__device__ __forceinline__ float sgf_sum_kq(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 7\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));      // [r0 r0 r2 r2], [r1 r1 r3 r3]
-  const float s = a + b;
-  float c = s, d = s;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));      // [lo lo], [hi hi]
-  return c + d;
-}
-
-typedef float sf32x16_t __attribute__((ext_vector_type(16)));
+#include "psg_wave.h"
 
 // G16 sixteen-row groups (x rows 16 G .. 16 G + 15) followed by G4 four-row groups (x rows 16 G16 + 4 q ..)
 template <int WAVES, int SLOTS, int G16, int G4, bool W16 = false>
@@ -169,7 +123,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
   }
   for (int i = 0; i < SLOTS - 1; ++i)
     if (i < total) issue();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this wave's x rows (and first weight blocks) landed
+  psg_vmwait<0>();                                                   // this wave's x rows (and first weight blocks) landed
   __syncthreads();
 
   // B operands, the k's of this lane's kq: 16-row group -> x row 16 G + (lane & 15); 4-row group -> x row
@@ -185,10 +139,10 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
   const int arow = W16 ? n * 64 : (n >> 3) * 1024 + (n & 7) * 128;
   const int a0off = W16 ? arow + ((kq ^ ((n >> 1) & 3)) * 16) : arow + (((2 * kq) ^ (n & 7)) * 16);
   const int a1off = W16 ? a0off : arow + (((2 * kq + 1) ^ (n & 7)) * 16);
-  const sf32x4_t zero4 = {0, 0, 0, 0};
-  const sf32x16_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  sf32x16_t acc16[NG16];
-  sf32x4_t acc4[NG4];
+  const psg_f32x4 zero4 = {0, 0, 0, 0};
+  const psg_f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  psg_f32x16 acc16[NG16];
+  psg_f32x4 acc4[NG4];
 #pragma unroll
   for (int g = 0; g < G16; ++g) acc16[g] = zero16;
 #pragma unroll
@@ -200,34 +154,34 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
 #pragma unroll
     for (int q = 0; q < G4; ++q)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc4[q][r] = sgf_sum_kq(acc4[q][r]);
-    sgf_lds_barrier();                                              // previous slab's tile fully read
+      for (int r = 0; r < 4; ++r) acc4[q][r] = psg_rows4_sum_mfma(acc4[q][r]);
+    psg_lds_barrier();                                              // previous slab's tile fully read
     {
       // 16-row groups: register 4 b + r of lane (j = lane & 15, ig = lane >> 4) = block b = kq's partial of
       // w[4 ig + r][.] x[row 16 G + j][.]; the partials are summed register-wise in the same (0 + 1) + (2 + 3) tree
       const uint32_t tp16 = otile_lds + (uint32_t)(n * OT_PITCH + wid * 16 + 4 * kq) * 4u;
 #pragma unroll
       for (int g = 0; g < G16; ++g) {
-        sf32x4_t v;
+        psg_f32x4 v;
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = (acc16[g][r] + acc16[g][4 + r]) + (acc16[g][8 + r] + acc16[g][12 + r]);
-        sgf_ds_write128(tp16 + (uint32_t)(16 * g * OT_PITCH) * 4u, v);
+        psg_lds_write128_mfma(tp16 + (uint32_t)(16 * g * OT_PITCH) * 4u, v);
       }
       // 4-row groups: every lane holds the total; row kq = q & 3 stores group q: tile[row 4 q + j][4 g + r]
       const int g4 = (lane >> 2) & 3, j = lane & 3;
       const uint32_t tp4 = otile_lds + (uint32_t)((16 * G16 + j) * OT_PITCH + wid * 16 + 4 * g4) * 4u;
 #pragma unroll
       for (int q = 0; q < G4; ++q)
-        if (kq == (q & 3)) sgf_ds_write128(tp4 + (uint32_t)(4 * q * OT_PITCH) * 4u, acc4[q]);
+        if (kq == (q & 3)) psg_lds_write128_mfma(tp4 + (uint32_t)(4 * q * OT_PITCH) * 4u, acc4[q]);
     }
-    sgf_lds_barrier();
+    psg_lds_barrier();
     {
       const int nblk = (gx + ct * G) * ROWS;
       constexpr int C4 = ROWS / 4;                                  // float4 columns per row
       for (int e = tid; e < M * C4; e += WAVES * 64) {
         const int m = e / C4, c4 = e - m * C4;
         if (nblk + c4 * 4 + 4 <= N) {
-          const sf32x4_t v = sgf_ds_read128(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
+          const psg_f32x4 v = psg_lds_read128_wait(otile_lds + (uint32_t)(m * OT_PITCH + c4 * 4) * 4u);
           float* dst = part + ((int64_t)by * M + m) * N + nblk + c4 * 4;
           if (wt) psg_st4_wt(dst, v[0], v[1], v[2], v[3]);         // option wt_stores: the slices leave the L2 as they are written
           else *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -247,7 +201,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
   }
   for (int j = 0; j < total; ++j) {
     if (j + SLOTS - 1 < total) issue();                             // refills the slot consumed at j - 1
-    SgfWait<SLOTS - 1, W16 ? 1 : 2>::go(total - 1 - j);             // blocks issued after block j may stay in flight
+    PsgDmaWait<W16 ? 1 : 2, SLOTS - 1>::go(total - 1 - j);          // blocks issued after block j may stay in flight
     const unsigned char* slot = ring + cs * BLOCK_BYTES;
     if (++cs == SLOTS) cs = 0;
     const int o = cb * 128;
@@ -257,17 +211,17 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
     if (W16) a16 = *reinterpret_cast<const sf16x8_t*>(slot + a0off);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      sf32x4_t a;
+      psg_f32x4 a;
       if (W16) {                                                    // exact widening: the operands of the fp32-weight stream
         a[0] = (float)a16[4 * h]; a[1] = (float)a16[4 * h + 1]; a[2] = (float)a16[4 * h + 2]; a[3] = (float)a16[4 * h + 3];
       } else {
-        a = *reinterpret_cast<const sf32x4_t*>(slot + (h ? a1off : a0off));
+        a = *reinterpret_cast<const psg_f32x4*>(slot + (h ? a1off : a0off));
       }
-      sf32x4_t b16[NG16], b4[NG4];
+      psg_f32x4 b16[NG16], b4[NG4];
 #pragma unroll
-      for (int g = 0; g < G16; ++g) b16[g] = *reinterpret_cast<const sf32x4_t*>(x16[g] + o + 16 * h);
+      for (int g = 0; g < G16; ++g) b16[g] = *reinterpret_cast<const psg_f32x4*>(x16[g] + o + 16 * h);
 #pragma unroll
-      for (int q = 0; q < G4; ++q) b4[q] = *reinterpret_cast<const sf32x4_t*>(x4[q] + o + 16 * h);
+      for (int q = 0; q < G4; ++q) b4[q] = *reinterpret_cast<const psg_f32x4*>(x4[q] + o + 16 * h);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -276,7 +230,7 @@ __global__ void __launch_bounds__(WAVES * 64) skinny_gemm_f32_kernel(const float
         for (int q = 0; q < G4; ++q) acc4[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(a[i], b4[q][i], acc4[q], 0, 0, 0);
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // ring reads retired before the slot is refilled
+    psg_lgkmwait<0>();                                               // ring reads retired before the slot is refilled
     if (++cb == nkb) finish_slab();
   }
 }

@@ -19,8 +19,6 @@
 //     and adds the bias (deterministic; the 2 x 16 MB of partial traffic stays in the MALL).
 #include "psg_common.h"
 
-typedef float pe_f32x16 __attribute__((ext_vector_type(16)));
-
 #define PE_KC 32
 #define PE_PITCH 33
 
@@ -72,11 +70,11 @@ patch_embed_kernel(const float* __restrict__ feat, const float* __restrict__ w, 
       pb[0] = rb[r].x; pb[1] = rb[r].y; pb[2] = rb[r].z; pb[3] = rb[r].w;
     }
   };
-  pe_f32x16 acc[2][2];
+  psg_f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (pe_f32x16){0};
+    for (int j = 0; j < 2; ++j) acc[i][j] = (psg_f32x16){0};
 
   if (nchunk > 0) load_chunk(0);
   const int l31 = lane & 31, hi = lane >> 5;

@@ -249,7 +249,6 @@ extern "C" int psg_masked_split_mean_pool(psg_ctx* ctx, const float* feat, int C
 // (v_mfma_f32_32x32x2_f32: bitwise an fmaf chain over c), one wave per 32 x 32 output tile, operands staged
 // through LDS in 32-column chunks so that global reads are 128-byte row pieces.
 // ---------------------------------------------------------------------------------------------
-typedef float bl_f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ void __launch_bounds__(64) bilinear_scores_kernel(const float* __restrict__ sub,
                                                              const float* __restrict__ obj, int B, int N, int R,
@@ -265,7 +264,7 @@ __global__ void __launch_bounds__(64) bilinear_scores_kernel(const float* __rest
   const int64_t ld = (int64_t)R * C;                                // row stride of the [B][N][R*C] inputs
   const float* sp = sub + ((int64_t)b * N) * ld + (int64_t)r * C;
   const float* op = obj + ((int64_t)b * N) * ld + (int64_t)r * C;
-  bl_f32x16 acc = {0};
+  psg_f32x16 acc = {0};
   const int i = lane & 31, kh = lane >> 5;
   for (int c0 = 0; c0 < C; c0 += 32) {
     // stage [32 rows][32 c] of both operands: lane -> (row = lane>>3 + 8 j, 4 floats at c0 + 4 (lane&7))

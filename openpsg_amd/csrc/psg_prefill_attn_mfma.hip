@@ -16,9 +16,6 @@
 // for prompts longer than 64 rows.
 #include "psg_common.h"
 
-typedef float pa_f32x16 __attribute__((ext_vector_type(16)));
-typedef float pa_f32x2 __attribute__((ext_vector_type(2)));
-
 
 
 template <typename E>
@@ -41,11 +38,11 @@ prefill_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restr
   const int nreal = __popcll(valid64);
   auto kclamp = [&](int j) { return j < nreal ? j : (nreal > 0 ? nreal - 1 : 0); };
 
-  pa_f32x16 sc[2][2];                                           // [key tile][query tile]
+  psg_f32x16 sc[2][2];                                           // [key tile][query tile]
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = (pa_f32x16){0};
+    for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = (psg_f32x16){0};
   // fragments: lane (idx = lane&31, hi) holds row (32 tile + idx), head dims 16 s + 8 hi .. +7
   const uint16_t* qp[2];
   const uint16_t* kp[2];
@@ -102,11 +99,11 @@ prefill_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restr
     inv_l[qt] = (qvalid && sum > 0.f) ? 1.0f / sum : 0.f;
   }
   // O^T[d][q] += V^T[d][keys] . P^T[keys][q]; key slice (kt, g): slot (hi, m) <-> key 32 kt + 16 g + (m&3) + 8 (m>>2) + 4 hi
-  pa_f32x16 o[4][2];                                            // [d tile][query tile]
+  psg_f32x16 o[4][2];                                            // [d tile][query tile]
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (pa_f32x16){0};
+    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (psg_f32x16){0};
   const uint16_t* vbase = vc + cbase + l31;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
@@ -206,11 +203,11 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
     }
   }
 
-  pa_f32x16 sc[2][2];
+  psg_f32x16 sc[2][2];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = (pa_f32x16){0};
+    for (int qt = 0; qt < 2; ++qt) sc[kt][qt] = (psg_f32x16){0};
   int rr[2];
   bool rreal[2];
 #pragma unroll
@@ -327,11 +324,11 @@ prefill_attn_rope_mfma_kernel(const uint16_t* __restrict__ qkv, const int32_t* _
     const bool qvalid = qi < 64 && ((valid64 >> qi) & 1ull);
     inv_l[qt] = (qvalid && sum > 0.f) ? 1.0f / sum : 0.f;
   }
-  pa_f32x16 o[4][2];
+  psg_f32x16 o[4][2];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (pa_f32x16){0};
+    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (psg_f32x16){0};
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll

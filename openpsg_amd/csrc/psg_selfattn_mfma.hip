@@ -12,8 +12,6 @@
 // The scalar kernel in psg_attn.hip (1.4 ms per layer at N = 50) stays as the fp32 verification path.
 #include "psg_common.h"
 
-typedef float sa_f32x16 __attribute__((ext_vector_type(16)));
-typedef float sa_f32x2 __attribute__((ext_vector_type(2)));
 
 
 
@@ -58,12 +56,12 @@ self_attn_mfma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restri
       kf[t][s] = *reinterpret_cast<const typename E::v8*>(rp + hidden + s * 16);
     }
   }
-  sa_f32x16 sc[2][2];                                           // [key tile][query tile]
+  psg_f32x16 sc[2][2];                                           // [key tile][query tile]
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-      sc[kt][qt] = (sa_f32x16){0};
+      sc[kt][qt] = (psg_f32x16){0};
 #pragma unroll
       for (int s = 0; s < 4; ++s)
         sc[kt][qt] = E::mfma32(kf[kt][s], qf[qt][s], sc[kt][qt]);
@@ -100,11 +98,11 @@ self_attn_mfma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restri
     inv_l[qt] = 1.0f / sum;
   }
   // O^T[d][q] += V^T[d][keys] . P^T[keys][q]; key slice (kt, g): slot (hi, m) <-> key 32 kt + 16 g + (m&3) + 8 (m>>2) + 4 hi
-  sa_f32x16 o[2][2];                                            // [d tile][query tile]
+  psg_f32x16 o[2][2];                                            // [d tile][query tile]
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (sa_f32x16){0};
+    for (int qt = 0; qt < 2; ++qt) o[dt][qt] = (psg_f32x16){0};
   const int voff = 2 * hidden + h * 64 + l31;
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt)

@@ -21,47 +21,14 @@
 #include <type_traits>
 
 #include "psg_common.h"
-
-typedef float xd_f32x16 __attribute__((ext_vector_type(16)));
-typedef float xd_f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t xd_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t xd_u32x2 __attribute__((ext_vector_type(2)));
+#include "psg_wave.h"
 
 #define XD_KSTRIDE 144   // bytes per K row in LDS: 64 bf16 + 16 B pad
 #define XD_SLOT 4352     // 4096 B tile + 256 B pair ids
 #define XD_CLS_COST 3     // a cls tile costs about this many pair tiles (static schedule)
 
-__device__ __forceinline__ float xd_xchg_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xd_xchg_sum(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// LDS traffic of the per-wave slots is inline asm: a compiler-visible ds access next to a pending LDS-DMA makes
-// hipcc wait vmcnt(0) (it treats the DMA as an LDS write that may alias), which would serialise DMA and compute.
-__device__ __forceinline__ xd_u32x4 xd_lds_read128(uint32_t a) {
-  xd_u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
-}
-__device__ __forceinline__ uint32_t xd_lds_read32(uint32_t a) {
-  uint32_t v;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(a) : "memory");
-  return v;
-}
-__device__ __forceinline__ void xd_lds_write64(uint32_t a, xd_u32x2 v) {
-  asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(v) : "memory");
-}
-__device__ __forceinline__ void xd_lds_write32(uint32_t a, uint32_t v) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory");
-}
-template <int N_>
-__device__ __forceinline__ void xd_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
+// LDS traffic of the per-wave slots goes through psg_lds_* (psg_wave.h): invisible to the compiler, so the pending DMAs
+// are waited for by the counted psg_vmwait only.
 
 template <typename E, int NC, int XD_WAVES>   // NC = key chunks of 128 (L <= 128 NC); XD_WAVES waves per workgroup (1 per CU)
 __global__ void __launch_bounds__(XD_WAVES * 64, (XD_WAVES + 3) / 4)
@@ -139,8 +106,8 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
   auto issue = [&](int64_t tile, int s) {
     unsigned char* dst = my_slots + s * XD_SLOT;
     if (poll) {
-      xd_lds_write32(slot_lds0 + (uint32_t)(s * XD_SLOT) + 4096u + (uint32_t)(lane * 4), 0xffffffffu);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the sentinel is in LDS before a DMA can overwrite it
+      psg_lds_write32(slot_lds0 + (uint32_t)(s * XD_SLOT) + 4096u + (uint32_t)(lane * 4), 0xffffffffu);
+      psg_lgkmwait<0>();  // the sentinel is in LDS before a DMA can overwrite it
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -307,14 +274,14 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     const uint32_t sl = slot_lds0 + (uint32_t)(s * XD_SLOT);
     // fragment (row l31, piece c = 2 s4 + hi) sits at slot position c ^ (l31 & 7) of its row
     union {
-      xd_u32x4 u;
+      psg_u32x4 u;
       typename E::v8 b;
     } qf[4];
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4)
-      qf[s4].u = xd_lds_read128(sl + (uint32_t)(l31 * 128 + (((2 * s4 + hi) ^ (l31 & 7)) * 16)));
-    const int pidx = (int)xd_lds_read32(sl + 4096u + (uint32_t)(l31 * 4));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      qf[s4].u = psg_lds_read128(sl + (uint32_t)(l31 * 128 + (((2 * s4 + hi) ^ (l31 & 7)) * 16)));
+    const int pidx = (int)psg_lds_read32(sl + 4096u + (uint32_t)(l31 * 4));
+    psg_lgkmwait<0>();
     __builtin_amdgcn_sched_barrier(0);
 
     int oi, oj;
@@ -351,16 +318,16 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
       if (__any(row_empty)) needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
     }
 
-    xd_f32x16 o0 = {0}, o1 = {0};
+    psg_f32x16 o0 = {0}, o1 = {0};
     float m_run = -INFINITY, l_run = 0.f;
-    if (use_mean) {                                       // (asm reads: see xd_lds_read128)
-      xd_u32x4 m0[4], m1[4];
+    if (use_mean) {                                       // (asm reads: see psg_lds_read128)
+      psg_u32x4 m0[4], m1[4];
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        m0[rr] = xd_lds_read128(mean_lds_addr + (uint32_t)(8 * rr + 4 * hi) * 4u);
-        m1[rr] = xd_lds_read128(mean_lds_addr + (uint32_t)(32 + 8 * rr + 4 * hi) * 4u);
+        m0[rr] = psg_lds_read128(mean_lds_addr + (uint32_t)(8 * rr + 4 * hi) * 4u);
+        m1[rr] = psg_lds_read128(mean_lds_addr + (uint32_t)(32 + 8 * rr + 4 * hi) * 4u);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      psg_lgkmwait<0>();
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr)
@@ -376,7 +343,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
       needmask &= needmask - 1u;
       uint32_t word = wi[t] | wj[t];
       const int left = L - 32 * t;                       // real keys in this tile (>= 1)
-      xd_f32x16 acc;
+      psg_f32x16 acc;
       const unsigned char* kp = kfrag_base + t * 32 * XD_KSTRIDE;
       if constexpr (AL) {
         if (force_all) word = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
@@ -386,7 +353,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
         } a_bias;
         a_bias.u[0] = (((word >> l31) & 1u) | (uint32_t)hi) ? 0u : E::NEG_2_15;   // 0 / -2^15 in bf16
         a_bias.u[1] = a_bias.u[2] = a_bias.u[3] = 0u;
-        acc = E::mfma32(a_bias.v, b_one.v, (xd_f32x16){0});
+        acc = E::mfma32(a_bias.v, b_one.v, (psg_f32x16){0});
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
           const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s4 * 32);
@@ -395,7 +362,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
       } else {
         {
           const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp);
-          acc = E::mfma32(a, qf[0].b, (xd_f32x16){0});
+          acc = E::mfma32(a, qf[0].b, (psg_f32x16){0});
         }
 #pragma unroll
         for (int s4 = 1; s4 < 4; ++s4) {
@@ -416,7 +383,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
       float cmax = acc[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) cmax = fmaxf(cmax, acc[r]);
-      cmax = xd_xchg_max(cmax);
+      cmax = psg_xchg32_max(cmax);
       const float m_new = fmaxf(m_run, cmax);
       float alpha, csum = 0.f;
       if constexpr (AL) {
@@ -437,7 +404,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
           csum += pv;
         }
       }
-      csum = xd_xchg_sum(csum);
+      csum = psg_xchg32_sum(csum);
       l_run = l_run * alpha + csum;
       m_run = m_new;
 #pragma unroll
@@ -467,19 +434,19 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     asm volatile("s_nop 15" ::: "memory");
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
-      xd_u32x2 w0, w1;
+      psg_u32x2 w0, w1;
       w0[0] = E::pack(o0[4 * rr] * inv_l, o0[4 * rr + 1] * inv_l);
       w0[1] = E::pack(o0[4 * rr + 2] * inv_l, o0[4 * rr + 3] * inv_l);
       w1[0] = E::pack(o1[4 * rr] * inv_l, o1[4 * rr + 1] * inv_l);
       w1[1] = E::pack(o1[4 * rr + 2] * inv_l, o1[4 * rr + 3] * inv_l);
-      xd_lds_write64(sl + (uint32_t)(l31 * 128 + ((rr ^ (l31 & 7)) * 16) + hi * 8), w0);
-      xd_lds_write64(sl + (uint32_t)(l31 * 128 + (((4 + rr) ^ (l31 & 7)) * 16) + hi * 8), w1);
+      psg_lds_write64(sl + (uint32_t)(l31 * 128 + ((rr ^ (l31 & 7)) * 16) + hi * 8), w0);
+      psg_lds_write64(sl + (uint32_t)(l31 * 128 + (((4 + rr) ^ (l31 & 7)) * 16) + hi * 8), w1);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // wave-private slot: the wave's own writes have landed
-    xd_u32x4 orow[4];
+    psg_lgkmwait<0>();  // wave-private slot: the wave's own writes have landed
+    psg_u32x4 orow[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) orow[i] = xd_lds_read128(sl + (uint32_t)((8 * i + r8) * 128 + ((pc ^ r8) * 16)));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (int i = 0; i < 4; ++i) orow[i] = psg_lds_read128(sl + (uint32_t)((8 * i + r8) * 128 + ((pc ^ r8) * 16)));
+    psg_lgkmwait<0>();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -502,15 +469,15 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     if (poll) {
       const uint32_t pa = slot_lds0 + (uint32_t)((u & 1) * XD_SLOT) + 4096u + (uint32_t)(lane * 4);
       for (int spin = 0; spin < (1 << 22); ++spin) {          // bounded: a lost DMA must not hang the GPU
-        const uint32_t got = xd_lds_read32(pa);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const uint32_t got = psg_lds_read32(pa);
+        psg_lgkmwait<0>();
         if (__all(got != 0xffffffffu)) break;
         __builtin_amdgcn_s_sleep(1);
       }
     } else if (t1 >= 0) {
-      xd_vmwait<5>();
+      psg_vmwait<5>();
     } else {
-      xd_vmwait<0>();
+      psg_vmwait<0>();
     }
     if (aligned && t >= NCLS) run_unit(t, u & 1, std::true_type{});
     else run_unit(t, u & 1, std::false_type{});

@@ -35,23 +35,9 @@
 #include <vector>
 
 #include "psg_common.h"
-
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#include "psg_wave.h"
 
 #define XA_KSTRIDE 144  // bytes per K row in LDS: 64 bf16 + 16 B pad
-
-// value of the partner lane (lane ^ 32) via v_permlane32_swap (VALU, no LDS round trip)
-__device__ __forceinline__ float xchg32_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xchg32_sum(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-
 
 template <typename E, int NC>   // NC = key chunks of 128 (L <= 128 NC): unrolled so the prefetched mask words index statically
 __global__ void __launch_bounds__(256, 2)
@@ -225,7 +211,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       if (any_empty) needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
     }
 
-    f32x16_t o0 = {0}, o1 = {0};
+    psg_f32x16 o0 = {0}, o1 = {0};
     float m_run = -INFINITY, l_run = 0.f;
 
     while (needmask != 0u) {
@@ -233,7 +219,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       needmask &= needmask - 1u;
       uint32_t word = wi[t] | wj[t];
       const int left = L - 32 * t;                       // real keys in this tile (>= 1)
-      f32x16_t acc;
+      psg_f32x16 acc;
       const unsigned char* kp = kfrag_base + t * 32 * XA_KSTRIDE;
       if constexpr (AL) {
         if (force_all) word = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
@@ -244,7 +230,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
         } a_bias;
         a_bias.u[0] = (((word >> l31) & 1u) | (uint32_t)hi) ? 0u : E::NEG_2_15;
         a_bias.u[1] = a_bias.u[2] = a_bias.u[3] = 0u;
-        acc = E::mfma32(a_bias.v, b_one.v, (f32x16_t){0});
+        acc = E::mfma32(a_bias.v, b_one.v, (psg_f32x16){0});
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s * 32);
@@ -253,7 +239,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       } else {
         {
           const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp);
-          acc = E::mfma32(a, qf[0], (f32x16_t){0});
+          acc = E::mfma32(a, qf[0], (psg_f32x16){0});
         }
 #pragma unroll
         for (int s = 1; s < 4; ++s) {
@@ -276,7 +262,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
       float cmax = acc[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) cmax = fmaxf(cmax, acc[r]);
-      cmax = xchg32_max(cmax);
+      cmax = psg_xchg32_max(cmax);
       const float m_new = fmaxf(m_run, cmax);
       float alpha, csum = 0.f;
       if constexpr (AL) {
@@ -297,7 +283,7 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
           csum += pv;
         }
       }
-      csum = xchg32_sum(csum);
+      csum = psg_xchg32_sum(csum);
       l_run = l_run * alpha + csum;
       m_run = m_new;
 #pragma unroll

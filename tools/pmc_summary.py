@@ -63,7 +63,7 @@ def main(fetch_db, write_db, out=None, esz=2):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     files = (["openpsg_amd/csrc/psg_batch_gemm.hip"] if PREFIX[0] != "skinny_gemm" else
              ["openpsg_amd/csrc/psg_gemm.hip"] if esz == 2 else ["openpsg_amd/csrc/psg_gemm_f32.hip"]) + \
-        ["openpsg_amd/csrc/psg_common.h"]
+        ["openpsg_amd/csrc/psg_common.h", "openpsg_amd/csrc/psg_wave.h"]
     res["kernel_sources"] = {f: hashlib.sha256(open(os.path.join(repo, f), "rb").read()).hexdigest()[:16] for f in files}
     text = json.dumps(res, indent=1)
     if out:
