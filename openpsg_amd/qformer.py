@@ -14,6 +14,9 @@ relation_transformer_head_v4.py:146-237 (prepare_inference :408-435, HF Instruct
     text-row attention output;
   * nothing synchronises with the host: selection stays on the device.
 
+One Q-Former layer is three blocks (`_self_block`, `_query_tail`, `_text_ffn`); the full pass, the selection phase and the
+last layer of the selected pairs compose them.
+
 Dense projections go through torch (`F.linear` -> hipBLASLt); everything else is libpsg_hip.so.
 """
 from __future__ import annotations
@@ -130,8 +133,13 @@ class RelationQueryEngine:
         return [(self._lin(pa, L["wk_x"], L["bk_x"]), self._lin(pa, L["wv_x"], L["bv_x"])) for L in self.layers]
 
     # ---- A6 + A7: Q-Former over a list of pairs ---------------------------------------------------
+    # One layer (HF-IB:446-596) = `_self_block` (all rows), then `_query_tail` (query rows: cross-attention, query FFN) and
+    # `_text_ffn` (text rows).  `_layer` composes them over P pairs; `_forward_pairs_cls_dedup` runs the first and the
+    # last per distinct prompt and lets the pair enter at `_query_tail`; `_cls_phase` puts `_query_tail` behind the last
+    # layer's one-row attention.
     # Activations travel as (X, X32): X in the activation dtype (the projections' operand), X32 its fp32 twin in mixed mode
     # (the residual of the next LayerNorm), else None.
+    # img = (kv, bits, num_objects, pair_index, segments): what the cross-attention and the classifiers read of the image(s).
     def _embed(self, ids):
         """HF-IB:728-757 for P pairs.  Returns (X [P*(33+T), 768], X32, shared0): with shared0 the embedded query rows are
         ONE [33, 768] block for all pairs (learned tokens through the embedding LayerNorm; 16-bit modes): layer 0
@@ -157,13 +165,14 @@ class RelationQueryEngine:
                 X.copy_(X32)
         return X, X32, shared0
 
-    def _ln(self, x, r16, r32, bias, ln, out16=None, period=0, index=None, want32=True):
+    def _ln(self, x, r16, r32, bias, ln, out16=None, out32=None, period=0, index=None, want32=True):
         """LayerNorm(x + bias + residual) -> (result in the activation dtype - in place of x unless out16 is given -,
-        fp32 twin or None).  period / index: residual rows from a periodic table / from table blocks chosen per group."""
+        fp32 twin - in out32 where the caller owns one - or None).  period / index: residual rows from a periodic table /
+        from table blocks chosen per group."""
         eps = self.cfg.qformer.ln_eps
         if self.res32:
-            return ops.add_layernorm_res32(x, r32, bias, ln[0], ln[1], eps, out16=out16, period=period, index=index,
-                                           want32=want32)
+            return ops.add_layernorm_res32(x, r32, bias, ln[0], ln[1], eps, out16=out16, out32=out32, period=period,
+                                           index=index, want32=want32)
         if index is not None:
             return ops.add_layernorm_indexed(x, r16, index, period, bias, ln[0], ln[1], eps, out=out16), None
         if period:
@@ -174,9 +183,10 @@ class RelationQueryEngine:
     def _s(t, a, b=None):
         return None if t is None else (t[a:] if b is None else t[a:b])
 
-    def _cross(self, li, qx, nq, kv, bits, num_objects, pair_index, segments):
+    def _cross(self, li, qx, nq, img):
         """Masked cross-attention of `nq` rows per pair (33, or 1 = the cls row alone) against the image's patches."""
         q = self.cfg.qformer
+        kv, bits, num_objects, pair_index, segments = img
         if segments is None:
             return ops.qformer_cross_attn(qx, kv[li][0], kv[li][1], bits, pair_index, num_objects, nq, q.heads,
                                           empty_policy=self.empty_policy, variant=self.xattn_variant)
@@ -187,8 +197,92 @@ class RelationQueryEngine:
                                    empty_policy=self.empty_policy, variant=self.xattn_variant)
         return cx
 
-    def _layer(self, li, X, X32, P, T, text_mask, pair_index, kv, bits, num_objects, segments, shared0=False,
-               hidden_out=None):
+    def _cross_prompt(self, qx_u, nq, img, inv, rows):
+        """Layer-0 cross-attention of the pairs when their projected queries exist per PROMPT: qx_u [U*nq, H], pair p asks
+        with block inv[p].  rows = inv[p] * nq + r where the caller has it cached with the prompt table, else None."""
+        q = self.cfg.qformer
+        H = q.hidden
+        kv, bits, num_objects, pair_index, _ = img
+        P = inv.numel()
+        cached = rows is not None
+        if not cached:
+            rows = (inv.to(torch.int64)[:, None] * nq + torch.arange(nq, device=self.device)[None, :]).reshape(-1).to(torch.int32)
+        cx = None
+        if (self.index_xattn and self.dtype in (torch.bfloat16, torch.float16) and nq == 33
+                and self.xattn_variant in (None, ops.PSG_XATTN_MFMA)):
+            # the LDS-DMA kernel looks the prompt's block up itself (pair tiles: one scalar load; cls tiles: the P cls
+            # rows gathered here) - no [P x 33, H] expansion of the queries (127 MB written and read again at C2)
+            if cached:                                                    # index tensors of a cached prompt table: built once
+                key = (rows.data_ptr(), inv.data_ptr(), P)               # (the entry keeps both tensors alive: the pointers
+                ent = self._xidx_cache.get(key)                          # cannot be handed out again while it exists)
+                if ent is None:
+                    if len(self._xidx_cache) > 64:
+                        self._xidx_cache.clear()
+                    ent = self._xidx_cache[key] = (rows[::nq].contiguous(), inv.to(torch.int32).contiguous(), rows, inv)
+            else:                                                         # `rows` is a temporary of this call: nothing to key on
+                ent = (rows[::nq].contiguous(), inv.to(torch.int32).contiguous())
+            q_cls = torch.empty((P, H), device=self.device, dtype=self.dtype)
+            ops.gather_rows(qx_u, ent[0], q_cls)
+            cx = ops.qformer_cross_attn_indexed(qx_u, ent[1], q_cls, kv[0][0], kv[0][1], bits, pair_index,
+                                                num_objects, q.heads, empty_policy=self.empty_policy)
+        if cx is None:
+            # the other kernels stream their Q tiles by DMA and take no index: each pair's rows gathered
+            qx = torch.empty((P * nq, H), device=self.device, dtype=self.dtype)
+            ops.gather_rows(qx_u, rows, qx)
+            cx = self._cross(0, qx, nq, img)
+        return cx
+
+    def _self_block(self, L, X, X32, G, T, mask, shared0=False, last=False):
+        """Self-attention block (HF-IB:471-530) of G groups of 33 + T rows -> (A, A32), laid out like X; `last`: the
+        query rows only.  shared0: the query rows entering the layer are ONE block for every group (`_embed`) - projected
+        once, and the periodic residual of the output LayerNorm."""
+        q = self.cfg.qformer
+        nq, H = q.q_rows, q.hidden
+        R, RQ = G * (nq + T), G * nq
+        ctx = torch.empty((R, H), device=self.device, dtype=self.dtype)
+        if shared0:
+            qkv_q = self._lin(X[:nq], L["wqkv"], L["bqkv"])
+            qkv = self._lin(X[RQ:], L["wqkv"], L["bqkv"])
+            ops.qformer_self_attn_shared(qkv_q, qkv, mask, G, T, nq, q.heads, ctx)
+        else:
+            qkv = self._lin(X, L["wqkv"], L["bqkv"])
+            ops.qformer_self_attn(qkv, mask, G, T, nq, q.heads, last, ctx)
+        del qkv
+        ra = RQ if last else R
+        A = self._lin(ctx[:ra], L["wo"])
+        A32 = torch.empty((ra, H), device=self.device, dtype=torch.float32) if self.res32 else None
+        if shared0:
+            self._ln(A[:RQ], X[:nq], self._s(X32, 0, nq), L["bo"], L["ln_a"], out32=self._s(A32, 0, RQ), period=nq)
+            self._ln(A[RQ:], X[RQ:], self._s(X32, RQ), L["bo"], L["ln_a"], out32=self._s(A32, RQ))
+        else:
+            self._ln(A, X[:ra], self._s(X32, 0, ra), L["bo"], L["ln_a"], out32=A32)
+        return A, A32
+
+    def _query_tail(self, li, A, A32, nq, img, prompt=None, out16=None, out32=None):
+        """Cross-attention block and query FFN of `nq` query rows per pair -> (rows leaving the layer, fp32 twin), into
+        out16 / out32 where given.  A [P*nq, H] (A32: fp32 twin): the pairs' rows behind `_self_block` - or, with prompt =
+        (inv, rows or None), one block per distinct PROMPT: pair p continues from block inv[p], the source of its
+        cross-attention queries (`_cross_prompt`) and the residual of that block's LayerNorm."""
+        L = self.layers[li]
+        qx = self._lin(A, L["wq_x"], L["bq_x"])
+        if prompt is None:
+            cx, period, index = self._cross(li, qx, nq, img), 0, None
+        else:
+            cx, period, index = self._cross_prompt(qx, nq, img, *prompt), nq, prompt[0]
+        Cq = self._lin(cx, L["wo_x"])
+        _, Cq32 = self._ln(Cq, A, A32, L["bo_x"], L["ln_x"], period=period, index=index)
+        del qx, cx
+        iq = self._ffn1(Cq, L["w1q"], L["b1q"])
+        hq = self._lin(iq, L["w2q"])
+        return self._ln(hq, Cq, Cq32, L["b2q"], L["ln_q"], out16=out16, out32=out32)
+
+    def _text_ffn(self, L, A, A32, out16=None, out32=None):
+        """FFN of the text rows (HF-IB:547-561; they never see the cross-attention) -> (rows leaving the layer, fp32 twin)."""
+        it = self._ffn1(A, L["w1t"], L["b1t"])
+        ht = self._lin(it, L["w2t"])
+        return self._ln(ht, A, A32, L["b2t"], L["ln_t"], out16=out16, out32=out32)
+
+    def _layer(self, li, X, X32, P, T, text_mask, img, shared0=False, hidden_out=None):
         """One Q-Former layer (HF-IB:446-596) over P pairs; the last layer computes the query rows only.
         Returns (Xn, Xn32)."""
         q = self.cfg.qformer
@@ -196,60 +290,23 @@ class RelationQueryEngine:
         R, RQ = P * (nq + T), P * nq
         L = self.layers[li]
         last = li == len(self.layers) - 1
-        ctx = torch.empty((R, H), device=self.device, dtype=self.dtype)
-        if li == 0 and shared0:
-            # the query rows entering layer 0 are identical for every pair: project the first pair's 33 rows once
-            qkv_q = self._lin(X[:nq], L["wqkv"], L["bqkv"])
-            qkv = self._lin(X[RQ:], L["wqkv"], L["bqkv"])
-            ops.qformer_self_attn_shared(qkv_q, qkv, text_mask, P, T, nq, q.heads, ctx)
-        else:
-            qkv = self._lin(X, L["wqkv"], L["bqkv"])
-            ops.qformer_self_attn(qkv, text_mask, P, T, nq, q.heads, last, ctx)
-        del qkv
-        ra = RQ if last else R
-        A = self._lin(ctx[:ra], L["wo"])
-        A32 = torch.empty((ra, H), device=self.device, dtype=torch.float32) if self.res32 else None
-        if li == 0 and shared0:
-            self._ln_into(A[:RQ], X[:nq], self._s(X32, 0, nq), L["bo"], L["ln_a"], self._s(A32, 0, RQ), period=nq)
-            self._ln_into(A[RQ:], X[RQ:], self._s(X32, RQ), L["bo"], L["ln_a"], self._s(A32, RQ))
-        else:
-            self._ln_into(A, X[:ra], self._s(X32, 0, ra), L["bo"], L["ln_a"], A32)
-        del ctx
-        qx = self._lin(A[:RQ], L["wq_x"], L["bq_x"])
-        cx = self._cross(li, qx, nq, kv, bits, num_objects, pair_index, segments)
-        Cq = self._lin(cx, L["wo_x"])
-        _, Cq32 = self._ln(Cq, A[:RQ], self._s(A32, 0, RQ), L["bo_x"], L["ln_x"])
-        del qx, cx
+        A, A32 = self._self_block(L, X, X32, P, T, text_mask, shared0 and li == 0, last)
         if last and hidden_out is not None:
             assert hidden_out.shape == (RQ, H) and hidden_out.dtype == self.dtype and hidden_out.is_contiguous()
             Xn = hidden_out
         else:
             Xn = torch.empty((RQ if last else R, H), device=self.device, dtype=self.dtype)
         Xn32 = torch.empty((Xn.shape[0], H), device=self.device, dtype=torch.float32) if self.res32 else None
-        iq = self._ffn1(Cq, L["w1q"], L["b1q"])
-        hq = self._lin(iq, L["w2q"])
-        self._ln_into(hq, Cq, Cq32, L["b2q"], L["ln_q"], self._s(Xn32, 0, RQ), out16=Xn[:RQ])
-        del iq, hq
+        self._query_tail(li, A[:RQ], self._s(A32, 0, RQ), nq, img, out16=Xn[:RQ], out32=self._s(Xn32, 0, RQ))
         if not last and T > 0:
-            it = self._ffn1(A[RQ:], L["w1t"], L["b1t"])
-            ht = self._lin(it, L["w2t"])
-            self._ln_into(ht, A[RQ:], self._s(A32, RQ), L["b2t"], L["ln_t"], self._s(Xn32, RQ), out16=Xn[RQ:])
-            del it, ht
+            self._text_ffn(L, A[RQ:], self._s(A32, RQ), out16=Xn[RQ:], out32=self._s(Xn32, RQ))
         return Xn, Xn32
 
-    def _ln_into(self, x, r16, r32, bias, ln, out32, out16=None, period=0, index=None):
-        """_ln writing its fp32 twin into a caller-owned slice (mixed mode); returns (16-bit result, out32)."""
-        eps = self.cfg.qformer.ln_eps
-        if self.res32:
-            o16, _ = ops.add_layernorm_res32(x, r32, bias, ln[0], ln[1], eps, out16=out16, out32=out32, period=period,
-                                             index=index)
-            return o16, out32
-        return self._ln(x, r16, None, bias, ln, out16=out16, period=period, index=index)
-
-    def _cls_heads(self, x, P, nq, pair_index, num_objects, segments, mc):
+    def _cls_heads(self, x, P, nq, img, mc):
         """The classifiers on the cls rows x[p*nq] (fp32 twin where one exists): existence logits / probabilities [P]
         (None, None without a binary head) and, when `mc` = (logit [P, R], prob [P, R]) fp32 buffers are given, the
         multiclass head into them (a separate launch behind the existence head's: that one is unchanged)."""
+        _, _, num_objects, pair_index, segments = img
         logit = prob = None
         if self.exist_w is not None:
             logit, prob = ops.exist_head(x, self.exist_w, self.exist_b, P, nq)
@@ -269,13 +326,22 @@ class RelationQueryEngine:
         sharding); everything but the cross-attention runs over all of them at once.
         mc: (logit [P, R], prob [P, R]) fp32 buffers for the multiclass head (see `_cls_heads`)."""
         P, T = ids.shape
+        img = (kv, bits, num_objects, pair_index, segments)
         X, X32, shared0 = self._embed(ids)
         for li in range(len(self.layers)):
-            X, X32 = self._layer(li, X, X32, P, T, text_mask, pair_index, kv, bits, num_objects, segments, shared0,
+            X, X32 = self._layer(li, X, X32, P, T, text_mask, img, shared0,
                                  hidden_out if li == len(self.layers) - 1 else None)
-        logit, prob = self._cls_heads(X32 if X32 is not None else X, P, self.cfg.qformer.q_rows, pair_index, num_objects,
-                                      segments, mc)
+        logit, prob = self._cls_heads(X32 if X32 is not None else X, P, self.cfg.qformer.q_rows, img, mc)
         return X, logit, prob
+
+    def _cls_in_space(self, T):
+        """Can the selection phase run in the input space (psg_qformer_cls_attn_input)?  The kernel is built for 12 heads
+        of 64 and keeps a pair's 33 + T input rows in LDS - 768 elements each, 16-bit rows padded by 8 - beside 64 floats
+        per head, within the 160 KB of a compute unit."""
+        q = self.cfg.qformer
+        wide = self.dtype == torch.float32
+        lds = (q.q_rows + T) * (q.hidden + (0 if wide else 8)) * (4 if wide else 2) + q.heads * 256
+        return self.cls_input_space and q.hidden == 768 and q.heads == 12 and lds <= 160 * 1024
 
     def forward_pairs_cls(self, kv, bits, num_objects, pair_index, ids, text_mask, segments=None, prompts=None, mc=None):
         """Selection phase: everything the existence logits depend on, and nothing else.
@@ -291,33 +357,41 @@ class RelationQueryEngine:
         of P.  rows (optional, cached by the caller) = inv[p] * 33 + r, the query rows of each pair's prompt block.
         mc: (logit [P, R], prob [P, R]) fp32 buffers for the multiclass head (see `_cls_heads`).
         Returns (state, exist_logit [P], exist_prob [P]); state feeds `pair_hidden`."""
-        q = self.cfg.qformer
-        nq, H = q.q_rows, q.hidden
         P, T = ids.shape
-        RQ = P * nq
+        RQ = P * self.cfg.qformer.q_rows
         nl = len(self.layers)
-        in_space = (self.cls_input_space and H == 768 and q.heads == 12
-                    and (nq + T) * (H + (8 if self.dtype != torch.float32 else 0)) * (
-                        4 if self.dtype == torch.float32 else 2) + q.heads * 256 <= 160 * 1024)
+        img = (kv, bits, num_objects, pair_index, segments)
+        in_space = self._cls_in_space(T)
         if (prompts is not None and segments is None and nl == 2 and T > 0 and in_space and self.dedup_prompts
                 and prompts[0].shape[0] <= 0.9 * P):
-            return self._forward_pairs_cls_dedup(kv, bits, num_objects, pair_index, text_mask, prompts, mc)
+            return self._forward_pairs_cls_dedup(img, text_mask, prompts, mc)
         X, X32, shared0 = self._embed(ids)
         for li in range(nl - 1):
-            X, X32 = self._layer(li, X, X32, P, T, text_mask, pair_index, kv, bits, num_objects, segments, shared0)
-        logit, prob = self._cls_phase(X[:RQ], self._s(X32, 0, RQ), X[RQ:], None, text_mask, P, T, kv, bits, num_objects,
-                                      pair_index, segments, in_space, X, mc)
-        state = dict(X=X, X32=X32, P=P, T=T, text_mask=text_mask, pair_index=pair_index, kv=kv, bits=bits,
-                     num_objects=num_objects, segments=segments)
+            X, X32 = self._layer(li, X, X32, P, T, text_mask, img, shared0)
+        state = self._state(X[:RQ], self._s(X32, 0, RQ), X[RQ:], self._s(X32, RQ), None, P, T, text_mask, img, X, X32)
+        logit, prob = self._cls_phase(state, text_mask, in_space, mc)
         return state, logit, prob
 
-    def _cls_phase(self, Xq, Xq32, Xt, text_index, mask, P, T, kv, bits, num_objects, pair_index, segments, in_space, X=None,
-                   mc=None):
-        """Last layer for the cls row of every pair.  Xq [P*33, H] query rows entering the layer (Xq32: fp32 twin); Xt:
-        text rows, block text_index[p] (None: block p) per pair, `mask` indexed the same way.  X: the two as one tensor
-        (K | V form)."""
+    @staticmethod
+    def _state(Xq, Xq32, Xt, Xt32, tix, P, T, text_mask, img, X=None, X32=None):
+        """What `pair_hidden` gets: the query and text rows entering the last layer (fp32 twins in mixed mode), pair p's
+        text block being tix[p] (None: block p); X / X32: both kinds of rows as ONE matrix, where they are views of one."""
+        kv, bits, num_objects, pair_index, segments = img
+        return dict(Xq=Xq, Xq32=Xq32, Xt=Xt, Xt32=Xt32, tix=tix, X=X, X32=X32, P=P, T=T, text_mask=text_mask,
+                    pair_index=pair_index, kv=kv, bits=bits, num_objects=num_objects, segments=segments)
+
+    @staticmethod
+    def _state_rows(state, segments=None):
+        """(Xq, Xq32, Xt, Xt32, tix, img) of a `_state`; the image side with the caller's `segments`."""
+        return (state["Xq"], state["Xq32"], state["Xt"], state["Xt32"], state["tix"],
+                (state["kv"], state["bits"], state["num_objects"], state["pair_index"], segments))
+
+    def _cls_phase(self, state, mask, in_space, mc=None):
+        """Last layer for the cls row of every pair of `state`; `mask`: the text masks, indexed like the text blocks."""
         q = self.cfg.qformer
         nq, H = q.q_rows, q.hidden
+        P, T, X = state["P"], state["T"], state["X"]
+        Xq, Xq32, Xt, _, tix, img = self._state_rows(state, state["segments"])
         li, L = len(self.layers) - 1, self.layers[-1]
         x_cls = Xq.view(P, nq, H)[:, 0].contiguous()                         # [P, H] residual of the cls rows
         x_cls32 = Xq32.view(P, nq, H)[:, 0].contiguous() if Xq32 is not None else None
@@ -333,7 +407,7 @@ class RelationQueryEngine:
             if X is not None:
                 xbar = ops.qformer_cls_attn_input(X, g, mask, P, T, nq, q.heads)
             else:
-                xbar = ops.qformer_cls_attn_input(Xq, g, mask, P, T, nq, q.heads, x_text=Xt, text_index=text_index)
+                xbar = ops.qformer_cls_attn_input(Xq, g, mask, P, T, nq, q.heads, x_text=Xt, text_index=tix)
             if self.split:
                 ctx = self._cls_values_split(xbar, L)
             else:
@@ -346,91 +420,27 @@ class RelationQueryEngine:
             del kvs
         A = self._lin(ctx, L["wo"])
         _, A32 = self._ln(A, x_cls, x_cls32, L["bo"], L["ln_a"])
-        qx = self._lin(A, L["wq_x"], L["bq_x"])
-        cx = self._cross(li, qx, 1, kv, bits, num_objects, pair_index, segments)
-        Cq = self._lin(cx, L["wo_x"])
-        _, Cq32 = self._ln(Cq, A, A32, L["bo_x"], L["ln_x"])
-        iq = self._ffn1(Cq, L["w1q"], L["b1q"])
-        hq = self._lin(iq, L["w2q"])
-        Xc, Xc32 = self._ln(hq, Cq, Cq32, L["b2q"], L["ln_q"])
-        return self._cls_heads(Xc32 if Xc32 is not None else Xc, P, 1, pair_index, num_objects, segments, mc)
+        Xc, Xc32 = self._query_tail(li, A, A32, 1, img)
+        return self._cls_heads(Xc32 if Xc32 is not None else Xc, P, 1, img, mc)
 
-    def _forward_pairs_cls_dedup(self, kv, bits, num_objects, pair_index, text_mask, prompts, mc=None):
+    def _forward_pairs_cls_dedup(self, img, text_mask, prompts, mc=None):
         """forward_pairs_cls with the prompt-only work done per DISTINCT prompt (two layers).  Layer 0's input is the
         learned query block plus the prompt's embeddings, so its whole self-attention block (HF-IB:471-530) is a
         function of the prompt; a pair enters at the cross-attention (its object masks).  The text rows never see the
         cross-attention at all: their layer-0 output - the last layer's text keys / values - is per prompt too."""
-        q = self.cfg.qformer
-        nq, H = q.q_rows, q.hidden
+        nq = self.cfg.qformer.q_rows
         ids_u, mask_u, inv = prompts[:3]
         U, T = ids_u.shape
         P = inv.numel()
         RQu = U * nq
         L = self.layers[0]
         Xu, Xu32, shared0 = self._embed(ids_u)
-        ctx = torch.empty((U * (nq + T), H), device=self.device, dtype=self.dtype)
-        if shared0:
-            qkv_q = self._lin(Xu[:nq], L["wqkv"], L["bqkv"])
-            qkv = self._lin(Xu[RQu:], L["wqkv"], L["bqkv"])
-            ops.qformer_self_attn_shared(qkv_q, qkv, mask_u, U, T, nq, q.heads, ctx)
-        else:
-            qkv = self._lin(Xu, L["wqkv"], L["bqkv"])
-            ops.qformer_self_attn(qkv, mask_u, U, T, nq, q.heads, False, ctx)
-        del qkv
-        A = self._lin(ctx, L["wo"])
-        A32 = torch.empty((A.shape[0], H), device=self.device, dtype=torch.float32) if self.res32 else None
-        if shared0:
-            self._ln_into(A[:RQu], Xu[:nq], self._s(Xu32, 0, nq), L["bo"], L["ln_a"], self._s(A32, 0, RQu), period=nq)
-            self._ln_into(A[RQu:], Xu[RQu:], self._s(Xu32, RQu), L["bo"], L["ln_a"], self._s(A32, RQu))
-        else:
-            self._ln_into(A, Xu, Xu32, L["bo"], L["ln_a"], A32)
-        del ctx
-        it = self._ffn1(A[RQu:], L["w1t"], L["b1t"])                        # text rows: straight to their layer-0 output
-        ht = self._lin(it, L["w2t"])
-        Xt_u, Xt_u32 = self._ln(ht, A[RQu:], self._s(A32, RQu), L["b2t"], L["ln_t"])
-        del it, ht
-        # the pair enters at the cross-attention: its queries are its prompt's 33 projected rows (projected per prompt,
-        # gathered per pair - the cross-attention kernel streams its Q tiles by DMA and takes no index), the residual
-        # of the output LayerNorm is read from the prompt's block through the index
-        qx_u = self._lin(A[:RQu], L["wq_x"], L["bq_x"])
-        if len(prompts) > 3:                                              # cached with the prompt table (names only)
-            rows = prompts[3]
-        else:
-            rows = (inv.to(torch.int64)[:, None] * nq + torch.arange(nq, device=self.device)[None, :]).reshape(-1).to(torch.int32)
-        cx = None
-        if (self.index_xattn and self.dtype in (torch.bfloat16, torch.float16) and nq == 33
-                and self.xattn_variant in (None, ops.PSG_XATTN_MFMA)):
-            # the LDS-DMA kernel looks the prompt's block up itself (pair tiles: one scalar load; cls tiles: the P cls
-            # rows gathered here) - no [P x 33, H] expansion of the queries (127 MB written and read again at C2)
-            if len(prompts) > 3:                                          # index tensors of a cached prompt table: built once
-                key = (rows.data_ptr(), inv.data_ptr(), P)               # (the entry keeps both tensors alive: the pointers
-                ent = self._xidx_cache.get(key)                          # cannot be handed out again while it exists)
-                if ent is None:
-                    if len(self._xidx_cache) > 64:
-                        self._xidx_cache.clear()
-                    ent = self._xidx_cache[key] = (rows[::nq].contiguous(), inv.to(torch.int32).contiguous(), rows, inv)
-            else:                                                         # `rows` is a temporary of this call: nothing to key on
-                ent = (rows[::nq].contiguous(), inv.to(torch.int32).contiguous())
-            q_cls = torch.empty((P, H), device=self.device, dtype=self.dtype)
-            ops.gather_rows(qx_u, ent[0], q_cls)
-            cx = ops.qformer_cross_attn_indexed(qx_u, ent[1], q_cls, kv[0][0], kv[0][1], bits, pair_index,
-                                                num_objects, q.heads, empty_policy=self.empty_policy)
-        if cx is None:
-            qx = torch.empty((P * nq, H), device=self.device, dtype=self.dtype)
-            ops.gather_rows(qx_u, rows, qx)
-            cx = self._cross(0, qx, nq, kv, bits, num_objects, pair_index, None)
-            del qx
-        Cq = self._lin(cx, L["wo_x"])
-        _, Cq32 = self._ln(Cq, A[:RQu], self._s(A32, 0, RQu), L["bo_x"], L["ln_x"], period=nq, index=inv)
-        del cx, qx_u
-        iq = self._ffn1(Cq, L["w1q"], L["b1q"])
-        hq = self._lin(iq, L["w2q"])
-        Xq, Xq32 = self._ln(hq, Cq, Cq32, L["b2q"], L["ln_q"])
-        del iq, hq, Cq
-        logit, prob = self._cls_phase(Xq, Xq32, Xt_u, inv, mask_u, P, T, kv, bits, num_objects, pair_index, None, True,
-                                      mc=mc)
-        state = dict(Xq=Xq, Xq32=Xq32, Xt_u=Xt_u, Xt_u32=Xt_u32, inv=inv, P=P, T=T, text_mask=text_mask,
-                     pair_index=pair_index, kv=kv, bits=bits, num_objects=num_objects, segments=None)
+        A, A32 = self._self_block(L, Xu, Xu32, U, T, mask_u, shared0)
+        Xt_u, Xt_u32 = self._text_ffn(L, A[RQu:], self._s(A32, RQu))       # text rows: straight to their layer-0 output
+        Xq, Xq32 = self._query_tail(0, A[:RQu], self._s(A32, 0, RQu), nq, img,
+                                    prompt=(inv, prompts[3] if len(prompts) > 3 else None))
+        state = self._state(Xq, Xq32, Xt_u, Xt_u32, inv, P, T, text_mask, img)
+        logit, prob = self._cls_phase(state, mask_u, True, mc)
         return state, logit, prob
 
     def pair_hidden(self, state, sel, segments=None):
@@ -438,59 +448,49 @@ class RelationQueryEngine:
         negative = no pair, computed as pair 0 and to be ignored).  Returns hidden [K*33, 768].
         segments: [(first slot, slot count, kv, bits, num_objects)] when the slots belong to several images of one
         `forward_pairs_cls(segments=...)` pass (everything but the cross-attention runs over all slots at once)."""
-        q = self.cfg.qformer
-        nq = q.q_rows
+        nq = self.cfg.qformer.q_rows
         P, T = state["P"], state["T"]
         assert segments is not None or state["segments"] is None, "pair_hidden: pass the slots' segments"
+        xq, xq32, xt, xt32, tix, img = self._state_rows(state, segments)
         s64 = sel.to(torch.int64).clamp(min=0)
         K = s64.numel()
         ar = torch.arange(nq, device=self.device)
         rows = [(s64[:, None] * nq + ar[None, :]).reshape(-1)]
         Xs32 = None
-        if "Xt_u" in state:                                                  # text rows live in the per-prompt table
-            trows = (state["inv"].to(torch.int64).index_select(0, s64)[:, None] * T
+        if tix is not None:                                                  # text rows live in the per-prompt table
+            trows = (tix.to(torch.int64).index_select(0, s64)[:, None] * T
                      + torch.arange(T, device=self.device)[None, :]).reshape(-1)
-            Xs = torch.cat([state["Xq"].index_select(0, rows[0]), state["Xt_u"].index_select(0, trows)])
-            if state.get("Xq32") is not None:
-                Xs32 = torch.cat([state["Xq32"].index_select(0, rows[0]), state["Xt_u32"].index_select(0, trows)])
-        else:
+            Xs = torch.cat([xq.index_select(0, rows[0]), xt.index_select(0, trows)])
+            if xq32 is not None:
+                Xs32 = torch.cat([xq32.index_select(0, rows[0]), xt32.index_select(0, trows)])
+        else:                                                                # both kinds of rows in ONE gather from X
             if T > 0:
                 rows.append((P * nq + s64[:, None] * T + torch.arange(T, device=self.device)[None, :]).reshape(-1))
             allrows = torch.cat(rows)
             Xs = state["X"].index_select(0, allrows)                        # [K*(33+T), 768]: query rows, then text rows
-            if state.get("X32") is not None:
+            if state["X32"] is not None:
                 Xs32 = state["X32"].index_select(0, allrows)
         tm = state["text_mask"].index_select(0, s64) if T > 0 else state["text_mask"]
-        pi = state["pair_index"].index_select(0, s64)
-        return self._layer(len(self.layers) - 1, Xs, Xs32, K, T, tm, pi, state["kv"], state["bits"], state["num_objects"],
-                           segments)[0]
+        img = img[:3] + (img[3].index_select(0, s64), segments)
+        return self._layer(len(self.layers) - 1, Xs, Xs32, K, T, tm, img)[0]
 
     def pair_hidden_sel(self, state, sel, first, count, slot_off=0):
         """`pair_hidden` for GLOBAL pair ids of a single-image pass: the rows of the selected pairs, their text masks and
         pair ids come out of ONE gather kernel (psg_gather_pair_rows) instead of ~20 index-arithmetic launches.
         sel int32 [K]; the chunk holds the pairs [first, first + count) at positions slot_off.. of the pass; slots of pairs
         outside it are computed as the chunk's first pair.  Returns (hidden [K*33, 768], mine uint8 [K])."""
-        q = self.cfg.qformer
-        nq = q.q_rows
-        P, T = state["P"], state["T"]
+        nq = self.cfg.qformer.q_rows
+        T = state["T"]
         assert state["segments"] is None
-        if "Xt_u" in state:                                                  # text rows live in the per-prompt table
-            xq, xt, tix = state["Xq"], state["Xt_u"], state["inv"]
-            xq32, xt32 = state.get("Xq32"), state.get("Xt_u32")
-        else:
-            X, X32 = state["X"], state.get("X32")
-            xq, xt, tix = X[:P * nq], X[P * nq:], None
-            xq32, xt32 = (None, None) if X32 is None else (X32[:P * nq], X32[P * nq:])
+        xq, xq32, xt, xt32, tix, img = self._state_rows(state)
         sel = sel.to(torch.int32).contiguous()
-        Xs, tm, pi, mine = ops.gather_pair_rows(xq, xt, tix, state["text_mask"], state["pair_index"], sel, first, count,
-                                                slot_off, nq, T)
+        Xs, tm, pi, mine = ops.gather_pair_rows(xq, xt, tix, state["text_mask"], img[3], sel, first, count, slot_off, nq, T)
         Xs32 = None
         if xq32 is not None:
             Xs32 = ops.gather_pair_rows(xq32, xt32, tix, None, None, sel, first, count, slot_off, nq, T, want_aux=False)[0]
         if T == 0:
             tm = state["text_mask"]
-        hk = self._layer(len(self.layers) - 1, Xs, Xs32, sel.numel(), T, tm, pi, state["kv"], state["bits"],
-                         state["num_objects"], None)[0]
+        hk = self._layer(len(self.layers) - 1, Xs, Xs32, sel.numel(), T, tm, img[:3] + (pi, None))[0]
         return hk, mine
 
     def _cls_big_weights(self, L):
@@ -520,7 +520,7 @@ class RelationQueryEngine:
         P = q_cls.shape[0]
         kb, _, _ = self._cls_big_weights(L)
         a2, inv_r = ops.split_f16i2(q_cls.contiguous())
-        g = ops.dense_gemm_split(a2, kb[0], None, inv_r, kb[1], tile="auto" if P < 16384 else "256x256")
+        g = ops.dense_gemm_split(a2, kb[0], None, inv_r, kb[1], tile=self._tile(P))
         return g.view(P, q.heads, q.hidden).permute(1, 0, 2).contiguous()
 
     def _cls_values_split(self, xbar, L):
@@ -529,7 +529,7 @@ class RelationQueryEngine:
         P = xbar.shape[1]
         _, vb, bias = self._cls_big_weights(L)
         x2, inv_r = ops.split_f16i2(xbar.permute(1, 0, 2).reshape(P, q.heads * q.hidden).contiguous())
-        return ops.dense_gemm_split(x2, vb[0], bias, inv_r, vb[1], tile="auto" if P < 16384 else "256x256")
+        return ops.dense_gemm_split(x2, vb[0], bias, inv_r, vb[1], tile=self._tile(P))
 
     def _bmm_f32(self, a, b, b32):
         """fp32 result of a batched product of activation-dtype operands (exact products, fp32 accumulation): the
@@ -545,6 +545,13 @@ class RelationQueryEngine:
         if self._bmm_out_dtype:
             return torch.bmm(a, b, out_dtype=torch.float32)
         return torch.bmm(a.float(), b32)
+
+    @staticmethod
+    def _tile(rows):
+        """Tile of a split product over `rows` rows.  A row's result does not depend on the tile: below ~30 k rows the
+        256 x 256 tile leaves most CUs idle - 2500 x 768 is 30 tiles - and the geometry that fills them in the fewest
+        rounds is taken instead."""
+        return "auto" if rows < 16384 else "256x256"
 
     def _lin(self, x, w, b=None, gelu=False):
         """Linear layer of the Q-Former (HF-IB: every `nn.Linear` on the path), optionally with the exact-erf GELU.
@@ -564,9 +571,7 @@ class RelationQueryEngine:
             ws = self._split_w.get(key)
             if ws is None:
                 ws = self._split_w[key] = ops.split_f16i2(w) if i2 else ops.split_f16x3(w, weights=True)
-            # (a row's result does not depend on the tile: below ~30 k rows the 256 x 256 tile leaves most CUs idle -
-            # 2500 x 768 is 30 tiles - and the geometry that fills them in the fewest rounds is taken instead)
-            tile = "auto" if x.shape[0] < 16384 else "256x256"
+            tile = self._tile(x.shape[0])
             if i2:
                 a2, inv_r = ops.split_f16i2(x)
                 return ops.dense_gemm_split(a2, ws[0], b, inv_r, ws[1], gelu=gelu, tile=tile)
