@@ -70,8 +70,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   601  psg_multiclass_head, psg_topk_large(_workspace), psg_train_mlcce_fwd / _bwd added
  *   602  grouped-query attention: psg_rope_kvwrite_gqa, psg_rope_kvwrite_scaled_gqa, psg_llm_attn_gqa, psg_prefill_attn_gqa,
  *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added
- *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added */
-#define PSG_ABI_VERSION 603
+ *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added
+ *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added */
+#define PSG_ABI_VERSION 604
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -349,6 +350,23 @@ int psg_rmsnorm_split2(psg_ctx*, float* resid, const float* delta, int delta_spl
 int psg_split_gemm_w16_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
 int psg_split_gemm_w16(psg_ctx*, const void* x2, const float* inv_scale, const void* w_f16, float* part, int M, int N, int K,
                        int slots, int mode, void* stream);
+/* The decode-step projections over an FP8-quantised weight: the model's weight is W'[n][k] = e4m3(w8[n][k]) *
+ * col_scale[n] (OCP e4m3fn bytes [N][K], fp32 per-row scales [N]; openpsg_amd/weights.py quantize_fp8_rows).  w8 streams
+ * from HBM ONCE per call as one byte per weight, is widened exactly to the x operand's 16-bit type in registers and
+ * multiplied on the 16-bit matrix cores with fp32 accumulation; col_scale is applied once, in fp32, at the slice store.
+ *   psg_split_gemm_w8 (fp32s): x2 / inv_scale as psg_split_gemm_w16's (psg_split_f16x2, psg_rmsnorm_split2):
+ *     part[slot][m][n] = (xh . q + xl . q)[m][n] * inv_scale[m] * col_scale[n];
+ *   psg_skinny_gemm_w8 (`dtype` = PSG_BF16 / PSG_F16): x [M][K]:  part[slot][m][n] = (x . q)[m][n] * col_scale[n].
+ * M <= 32, N % 16 == 0, K % 128 == 0 (one K step is a 128-byte fp8 row piece), else PSG_ERR_UNSUPPORTED.  fp32 slices
+ * part[slots][M][N] (slots <= 16) for the consumers of psg_skinny_gemm: k-ordered, no atomics, a row's result does not
+ * depend on the other rows or on M.  `slots` must be what the plan entry returns for the shape; mode 1 (ranges aligned
+ * to the 256-row slabs) / 2 (stream-K) pick a variant, 0 = the library's estimate. */
+int psg_split_gemm_w8_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_split_gemm_w8(psg_ctx*, const void* x2, const float* inv_scale, const void* w8, const float* col_scale, float* part,
+                      int M, int N, int K, int slots, int mode, void* stream);
+int psg_skinny_gemm_w8_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
+int psg_skinny_gemm_w8(psg_ctx*, const void* x, const void* w8, const float* col_scale, float* part, int M, int N, int K,
+                       int slots, int dtype, int mode, void* stream);
 /* psg_skinny_gemm(PSG_F32) over weights STORED as fp16: x fp32 [M][K], w fp16 [N][K], the same plan (psg_skinny_gemm_plan
  * with PSG_F32), the same f32 matrix instructions on the exactly widened weights in the same order - part is bit-identical
  * to the fp32-weight call on w.float(), at half the weight bytes.  For weights that ARE fp16 values: the reference's LLM is

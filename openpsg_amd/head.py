@@ -229,8 +229,22 @@ class RelationTransformerHeadV4(nn.Module):
                                                # the decoder's probability of emitting the relation name and stopping
                  num_llm_ranked_triples=0,     # 'likelihood': the N best remaining (pair, class) triples of the selected
                                                # pairs follow the generated ones (at most 4096)
+                 llm_weight_quant=None,        # None | 'fp8': the LLM's q/k/v/o/gate/up/down matrices as OCP e4m3fn bytes with one
+                                               # fp32 scale per output row (weights.quantize_fp8_rows): decode
+                                               # steps of <= 32 rows stream 1 byte per weight.  The model IS the quantised one
+                                               # (W' = q s) on every path; an FP8 checkpoint is taken as it is
+                 llm_quantize_lm_head=False,   # 'fp8': the lm_head as well (never the embedding, norms, language_projection)
                  **kwargs):
         super().__init__()
+        if llm_weight_quant not in (None, "fp8"):
+            raise PsgHipError(f"llm_weight_quant must be None or 'fp8', got {llm_weight_quant!r}")
+        if llm_weight_quant is not None and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_weight_quant={llm_weight_quant!r} quantises the LLM; rel_cls_type={rel_cls_type!r} has no "
+                              "LLM stage")
+        if llm_quantize_lm_head and llm_weight_quant is None:
+            raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8'")
+        self.llm_weight_quant = llm_weight_quant
+        self.llm_quantize_lm_head = bool(llm_quantize_lm_head)
         if rel_cls_type not in REL_CLS_TYPES:
             raise ValueError(f"rel_cls_type must be one of {REL_CLS_TYPES} (V4:31, 91-95), got {rel_cls_type!r}")
         if llm_rel_scores not in ("constant", "likelihood"):
@@ -433,12 +447,22 @@ class RelationTransformerHeadV4(nn.Module):
         if wrong:                                       # e.g. a grouped-query checkpoint under a multi-head config
             raise PsgHipError(f"LLM weights of the wrong shape ({len(wrong)}), e.g. {wrong[:2]} "
                               f"({self.cfg.llm.heads} query / {self.cfg.llm.n_kv_heads} key-value heads)")
-        w = dict(weights)
+        w = self.quantize_llm_weights(weights)
         w["language_projection.weight"] = self.language_projection.weight.data
         w["language_projection.bias"] = self.language_projection.bias.data
         self._llm_engine = LlamaDecodeEngine(w, self.cfg, self.device, self.act_dtype, n_layers=n_layers,
                                              resid_dtype=self.resid_dtype, prefill_split=self.prefill_split)
         return self
+
+    def quantize_llm_weights(self, weights: dict) -> dict:
+        """What `load_llm_weights` hands the decode engine: with llm_weight_quant='fp8' every q/k/v/o/gate/up/down matrix
+        of the kept layers (+ the lm_head with llm_quantize_lm_head) as (e4m3fn bytes under its name, fp32 row scales
+        under name + '_scale'); matrices that already come as such a pair are kept.  Otherwise a plain copy of the dict."""
+        if self.llm_weight_quant is None:
+            return dict(weights)
+        from .weights import quantize_llm_weights
+        n_layers = self.cfg.llm.layers if self.llm_truncate_num <= 0 else self.llm_truncate_num
+        return quantize_llm_weights(weights, n_layers, self.llm_quantize_lm_head)
 
     def _param_version(self) -> int:
         """Sum of the parameters' in-place version counters: every optimizer step (and any other in-place update of a

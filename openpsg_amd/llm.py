@@ -240,8 +240,32 @@ class LlamaDecodeEngine:
         self.n_layers = m.layers if n_layers is None else n_layers        # llm_truncate_num (V4:101-103)
         f32 = lambda k: weights[k].to(device=self.device, dtype=torch.float32).contiguous()   # noqa: E731
         act = lambda t: t.to(device=self.device, dtype=dtype).contiguous()                     # noqa: E731
+        # FP8-quantised matrices: `name` holds e4m3fn bytes q, `name + '_scale'` the fp32 per-row scales s, the
+        # model's weight is W' = float32(q) * s.  W' goes under the existing key in the engine's dtype - every path not
+        # built for the byte stream computes the same model on the kernels it has - and `_w8` keeps (q, s) for the decode
+        # steps of <= 32 rows, `_w8h` an exact fp16 copy of q for the fp32s prompt pass (its two-plane operand x fp16 matrix)
+        from .weights import SCALE_SUFFIX, dequantize_fp8_rows
+        self._w8, self._w8h = {}, {}
+
+        def matrix(*keys):
+            """The (row-concatenated) matrix of `keys` in the engine's dtype; registers its byte stream when every part
+            is quantised (per-row scales commute with the concatenation)."""
+            quant = [k + SCALE_SUFFIX in weights for k in keys]
+            if any(quant) and not all(quant):
+                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some are not")
+            if not quant[0]:
+                return act(torch.cat([weights[k] for k in keys], 0) if len(keys) > 1 else weights[keys[0]])
+            q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
+            sc = torch.cat([weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1) for k in keys], 0)
+            if sc.numel() != q.shape[0]:
+                raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
+            w = dequantize_fp8_rows(q, sc, dtype).contiguous()
+            self._w8[w.data_ptr()] = (q, sc.contiguous())
+            if prefill_split and dtype == torch.float32:
+                self._w8h[w.data_ptr()] = q.view(torch.float8_e4m3fn).to(torch.float16)
+            return w
         self.embed = act(weights["language_model.model.embed_tokens.weight"])
-        self.lm_head = act(weights["language_model.lm_head.weight"])
+        self.lm_head = matrix("language_model.lm_head.weight")
         self.final_norm = f32("language_model.model.norm.weight")
         self.proj_w = act(weights["language_projection.weight"])
         self.proj_b = act(weights["language_projection.bias"])
@@ -254,11 +278,16 @@ class LlamaDecodeEngine:
                     raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
                                       f"({m.heads} query / {m.n_kv_heads} key-value heads of 128)")
             self.layers.append(dict(
-                wqkv=act(torch.cat([weights[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], 0)),
-                wo=act(weights[p + "self_attn.o_proj.weight"]),
-                wgu=act(torch.cat([weights[p + "mlp.gate_proj.weight"], weights[p + "mlp.up_proj.weight"]], 0)),
-                wdown=act(weights[p + "mlp.down_proj.weight"]),
+                wqkv=matrix(*[p + f"self_attn.{n}_proj.weight" for n in "qkv"]),
+                wo=matrix(p + "self_attn.o_proj.weight"),
+                wgu=matrix(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
+                wdown=matrix(p + "mlp.down_proj.weight"),
                 ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
+        layer_w = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
+        n_q = sum(t.data_ptr() in self._w8 for t in layer_w)
+        if 0 < n_q < len(layer_w):
+            raise PsgHipError(f"{n_q} of the {len(layer_w)} decoder-layer matrices are FP8-quantised: all or none")
+        self._w8_layers = n_q > 0                                # every decoder-layer matrix streams as bytes
         self.use_skinny = True
         self.prefill_split = bool(prefill_split) and dtype == torch.float32
         # fp32 engines: are the projection weights fp16 VALUES?  The reference's LLM is the frozen Llama-2-7b-hf checkpoint
@@ -276,6 +305,8 @@ class LlamaDecodeEngine:
         if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
             tensors = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
             for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
+                if t.data_ptr() in self._w8:                    # (has its byte stream: never counted, `_w16_all` stays false)
+                    continue
                 h = t.half()
                 if torch.equal(h.float(), t):
                     self._w16[t.data_ptr()] = h
@@ -285,7 +316,8 @@ class LlamaDecodeEngine:
             # weight next to the fp32 copy the decode steps stream: 40 GB + 27 GB for Llama-2-7B, of 288 GB)
             for L in self.layers:
                 for k in ("wqkv", "wo", "wgu", "wdown"):
-                    L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
+                    if L[k].data_ptr() not in self._w8:         # (quantised: the two-plane prompt pass on `_w8h`, no split copy)
+                        L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
         # row_invariant (fp32s engines): the prompt pass's projections and the language projection on psg_dense_gemm - one
         # k-ordered accumulation per output element whatever the row count of the call - instead of the library GEMM, whose
         # kernel choice follows the row count: a pair decoded in a batch of 3 (decodes DEALT over the ranks of a pair-sharded
@@ -408,6 +440,15 @@ class LlamaDecodeEngine:
         the 16-bit modes and in the fp32 mode (the reference's own precision, V4:99-100) alike; the prompt pass goes
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
         psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm)."""
+        w8 = self._w8.get(w.data_ptr()) if self._w8 else None
+        if (w8 is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and w.shape[0] % 16 == 0
+                and w.shape[1] % 128 == 0 and (self.prefill_split or x.dtype != torch.float32)):
+            # FP8-quantised matrix, <= 32 rows: one byte per weight (psg_gemm_w8.hip).  The exact fp32 mode, other shapes
+            # and more rows run the paths below on W'
+            if x.dtype == torch.float32:
+                x2, inv = ops.split_f16x2(x)
+                return ops.split_gemm_w8(x2, inv, *w8)
+            return ops.skinny_gemm_w8(x, *w8)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
             if wh is not None and self.prefill_split:         # fp32s: two fp16 products of the split rows, 2 bytes per weight
@@ -450,7 +491,7 @@ class LlamaDecodeEngine:
         rows = int(rows)
         if not self.use_skinny or rows > 32:
             return True
-        if self._can_w16(rows):                                # psg_split_gemm_w16 for every projection
+        if self._can_w16(rows) or self._can_w8(rows):          # psg_split_gemm_w16 / _w8 for every projection
             return False
         L = self.layers[0] if self.layers else None
         ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
@@ -562,13 +603,16 @@ class LlamaDecodeEngine:
         m = self.cfg.llm
         rows, D = resid.shape
         plan = _plan_split_mm if self.plan_split else (lambda r, w, k3=False: None)
-        planes = 2 if self._w16_all else 3
+        planes = 2 if self._w16_all or self._w8_layers else 3
         if planes == 3:
             weight = lambda L, k: L[k + "_s"]                                               # noqa: E731
             mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
             split = ops.split_f16x3
         else:
-            weight = lambda L, k: (self._w16[L[k].data_ptr()], self._ones(L[k].shape[0]))   # noqa: E731
+            if self._w8_layers:                                 # W' = q s: the exact fp16 image of q, s as the column scale
+                weight = lambda L, k: (self._w8h[L[k].data_ptr()], self._w8[L[k].data_ptr()][1])   # noqa: E731
+            else:
+                weight = lambda L, k: (self._w16[L[k].data_ptr()], self._ones(L[k].shape[0]))   # noqa: E731
             split = ops.split_f16x2
 
             def mm(a2, w16, k3):                               # a2 [2, r, K] -> raw product slices [S, r, N]
@@ -608,7 +652,7 @@ class LlamaDecodeEngine:
 
     def _can_persist(self, rows, slot):
         m = self.cfg.llm
-        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32
+        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32 and not self._w8
                 and self.kv is None                            # the persistent decoder layer is multi-head only
                 and ops.decode_layer_supported(rows, m.hidden, m.inter, m.heads, self.dtype, self.device))
 
@@ -674,10 +718,52 @@ class LlamaDecodeEngine:
             a2, inv = ops.rmsnorm_split2(x, d, nxt, m.rms_eps)
         return ops.split_gemm_w16(a2, inv, wh[self.lm_head.data_ptr()])
 
+    def _can_w8(self, rows):
+        """fp32s decode steps over FP8-quantised decoder layers: every projection as psg_split_gemm_w8, the row kernels
+        writing its two-plane operand directly (`_decode_step_w8`)."""
+        m = self.cfg.llm
+        return (self._w8_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
+                and self.dtype == torch.float32 and m.hidden % 128 == 0 and m.inter % 128 == 0 and m.inter <= 16384
+                and m.hidden <= 8192 and m.vocab % 16 == 0)
+
+    def _decode_step_w8(self, st):
+        """`_decode_step_w16` over FP8-quantised decoder layers: 1 byte per weight from HBM, the same two fp16 products per
+        projection on the exactly widened bytes, the per-row weight scale applied in fp32 where a slice is stored.  The
+        lm_head runs on the stream ITS tensor has: bytes, fp16 values or fp32."""
+        m = self.cfg.llm
+        x, w8 = st["x"], self._w8
+        K, D = x.shape
+        att = torch.empty((K, D), device=self.device, dtype=torch.float32)
+        a2, inv = ops.rmsnorm_split2(x, None, self.layers[0]["ln1"], m.rms_eps)
+        for l, L in enumerate(self.layers):
+            qkv = ops.split_gemm_w8(a2, inv, *w8[L["wqkv"].data_ptr()])
+            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
+                            st["vc"][l], att, kv_heads=self.kv)
+            a2o, invo = ops.split_f16x2(att)
+            o = ops.split_gemm_w8(a2o, invo, *w8[L["wo"].data_ptr()])
+            a2, inv = ops.rmsnorm_split2(x, o, L["ln2"], m.rms_eps)
+            gu = ops.split_gemm_w8(a2, inv, *w8[L["wgu"].data_ptr()])
+            act = torch.empty((K, m.inter), device=self.device, dtype=torch.float32)
+            ops.silu_mul(gu, act)
+            a2a, inva = ops.split_f16x2(act)
+            d = ops.split_gemm_w8(a2a, inva, *w8[L["wdown"].data_ptr()])
+            if l + 1 < len(self.layers):
+                a2, inv = ops.rmsnorm_split2(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
+        head = self.lm_head.data_ptr()
+        if head in w8 and self.lm_head.shape[1] % 128 == 0:
+            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
+            return ops.split_gemm_w8(a2, inv, *w8[head])
+        if head in self._w16:
+            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
+            return ops.split_gemm_w16(a2, inv, self._w16[head])
+        n = torch.empty_like(x)
+        ops.rmsnorm(x, d, self.final_norm, m.rms_eps, n)
+        return self.logits(n)
+
     def _can_fuse(self, rows):
         m = self.cfg.llm
         D = m.hidden
-        return (bool(self.fuse_rowops) and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
+        return (bool(self.fuse_rowops) and not self._w8 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
                 and self.resid_dtype == self.dtype and rows <= 32 and D in (1024, 4096) and m.inter >= 1024 and m.inter % 64 == 0
                 and m.vocab >= 1024 and m.vocab % 16 == 0)
 
@@ -972,7 +1058,8 @@ class LlamaDecodeEngine:
         m = self.cfg.llm
         persist = hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
         w16 = not persist and self._can_w16(st["x"].shape[0])
-        fused = not persist and not w16 and self._can_fuse(st["x"].shape[0]) and hi > lo
+        w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])
+        fused = not persist and not w16 and not w8 and self._can_fuse(st["x"].shape[0]) and hi > lo
         if persist:                                            # one counter block per layer launch, zeroed once per call
             per_step = ops.decode_layer_counters(self.device) * len(self.layers)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
@@ -987,6 +1074,8 @@ class LlamaDecodeEngine:
                 logits = self._decode_step_persistent(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             elif w16:
                 logits = self._decode_step_w16(st)
+            elif w8:
+                logits = self._decode_step_w8(st)
             elif fused:
                 logits = self._decode_step_fused(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             else:

@@ -782,6 +782,49 @@ def split_gemm_w16(x2, inv_scale, w16, mode=0) -> Partials:
     return Partials(part)
 
 
+def _w8_args(name, w8, col_scale, K):
+    if w8.dtype not in (torch.uint8, torch.float8_e4m3fn) or w8.dim() != 2 or w8.shape[1] != K:
+        raise PsgHipError(f"{name}: w8 must be e4m3fn bytes [N, {K}] (uint8 / float8_e4m3fn), got {w8.dtype} {tuple(w8.shape)}")
+    if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (w8.shape[0],):
+        raise PsgHipError(f"{name}: col_scale must be fp32 [{w8.shape[0]}], got {col_scale.dtype} {tuple(col_scale.shape)}")
+    return w8.shape[0]
+
+
+def split_gemm_w8(x2, inv_scale, w8, col_scale, mode=0) -> Partials:
+    """`split_gemm_w16` over an FP8-quantised weight W' = e4m3(w8) * col_scale[:, None] (weights.quantize_fp8_rows): one byte
+    per weight from HBM, widened exactly to fp16 in registers; fp32 slices [S, M, N] of (xh . q + xl . q) * inv_scale *
+    col_scale (psg_split_gemm_w8).  K % 128 == 0.  mode 1 / 2: slab-aligned / stream-K ranges, 0 = the library's estimate."""
+    import ctypes
+    lib, ctx, st = _env(x2)
+    _, M, K = x2.shape
+    assert x2.shape[0] == 2 and x2.dtype == torch.float16
+    N = _w8_args("split_gemm_w8", w8, col_scale, K)
+    s = ctypes.c_int(0)
+    check(lib.psg_split_gemm_w8_plan(ctx, M, N, K, int(mode), ctypes.byref(s)), "psg_split_gemm_w8_plan")
+    part = torch.empty((s.value, M, N), device=x2.device, dtype=torch.float32)
+    check(lib.psg_split_gemm_w8(ctx, _p(x2), _p(inv_scale, torch.float32), _p(w8, name="w8"), _p(col_scale), _p(part), M, N, K,
+                                s.value, int(mode), st), "psg_split_gemm_w8")
+    return Partials(part)
+
+
+def skinny_gemm_w8(x, w8, col_scale, mode=0) -> Partials:
+    """`skinny_gemm` of <= 32 bf16 / fp16 rows over an FP8-quantised weight W' = e4m3(w8) * col_scale[:, None]: one byte per
+    weight from HBM, widened exactly to x's type in registers; fp32 slices [S, M, N] of (x . q) * col_scale
+    (psg_skinny_gemm_w8).  K % 128 == 0."""
+    import ctypes
+    lib, ctx, st = _env(x)
+    M, K = x.shape
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise PsgHipError(f"skinny_gemm_w8: x must be bf16 or fp16, got {x.dtype}")
+    N = _w8_args("skinny_gemm_w8", w8, col_scale, K)
+    s = ctypes.c_int(0)
+    check(lib.psg_skinny_gemm_w8_plan(ctx, M, N, K, _dt(x), int(mode), ctypes.byref(s)), "psg_skinny_gemm_w8_plan")
+    part = torch.empty((s.value, M, N), device=x.device, dtype=torch.float32)
+    check(lib.psg_skinny_gemm_w8(ctx, _p(x, name="x"), _p(w8, name="w8"), _p(col_scale), _p(part), M, N, K, s.value, _dt(x),
+                                 int(mode), st), "psg_skinny_gemm_w8")
+    return Partials(part)
+
+
 def batch_gemm(x, w, slab_rows=0, mode=0) -> Partials:
     """Decode-step projection for 33..160 rows (several images' pairs decoded together): fp32 split-K slices of x @ w.T
     like `skinny_gemm`'s, the weight streamed from HBM once (psg_batch_gemm; bf16 / fp16).

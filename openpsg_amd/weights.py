@@ -205,6 +205,82 @@ def make_weights_device(cfg: PSGConfig, seed: int, device, head_dtype=torch.floa
     return out
 
 
+# ---- FP8-quantised LLM matrices ---------------------------------------------------------------------------
+# ONE definition of the quantised model, used by the head's option, the checkpoint reader, the engine and the tests: a
+# matrix is (q, s) = (OCP e4m3fn bytes [N, K], fp32 per-row scales [N]) and its value is W' = float32(q) * s[:, None], one
+# fp32 rounding per element.  Per-row scales commute with the row concatenations the engine makes (q|k|v, gate|up).
+FP8_MAX = 448.0                                                    # largest finite e4m3fn value
+LLM_QUANT_MATRICES = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+                      "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+SCALE_SUFFIX = "_scale"                                            # `<name>.weight` -> `<name>.weight_scale`
+
+
+def quantize_fp8_rows(W: torch.Tensor):
+    """W [N, K] -> (q uint8 [N, K]: e4m3fn bytes, s fp32 [N]).  s[n] = max_k |W[n, k]| / 448 in fp32 (1 for an all-zero
+    row), q[n, k] = W[n, k] / s[n] clamped to +-448 and rounded to nearest even on the e4m3fn grid."""
+    if W.dim() != 2:
+        raise ValueError(f"quantize_fp8_rows takes a matrix, got shape {tuple(W.shape)}")
+    W = W.to(torch.float32)
+    amax = W.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (W / s[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), s
+
+
+def dequantize_fp8_rows(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """W' = float32(q) * s[:, None] (one fp32 rounding per element), then `dtype`."""
+    q8 = q if q.dtype == torch.float8_e4m3fn else q.view(torch.float8_e4m3fn)
+    return (q8.to(torch.float32) * s.to(torch.float32)[:, None]).to(dtype)
+
+
+def is_quantized(weights: dict, key: str) -> bool:
+    return key + SCALE_SUFFIX in weights
+
+
+def llm_quant_keys(n_layers: int, lm_head: bool = False):
+    """Names of the matrices llm_weight_quant='fp8' quantises: q/k/v/o/gate/up/down of the kept layers (+ the lm_head on
+    request); never the embedding, the norms or language_projection."""
+    keys = [f"language_model.model.layers.{l}.{n}" for l in range(n_layers) for n in LLM_QUANT_MATRICES]
+    return keys + (["language_model.lm_head.weight"] if lm_head else [])
+
+
+def quantize_llm_weights(weights: dict, n_layers: int, lm_head: bool = False) -> dict:
+    """`weights` with every matrix of `llm_quant_keys` replaced by its (q, s): the byte tensor under the matrix's own name,
+    the scales under name + '_scale'.  A matrix that already comes as (q, s) - an FP8 checkpoint - is kept as it is."""
+    out = dict(weights)
+    for k in llm_quant_keys(n_layers, lm_head):
+        if k in out and not is_quantized(out, k):
+            out[k], out[k + SCALE_SUFFIX] = quantize_fp8_rows(out[k])
+    return out
+
+
+def _take_fp8_pairs(out: dict, path):
+    """The (weight, weight_scale) pairs of an FP8 checkpoint, as stored: weight stays float8_e4m3fn, the scale becomes
+    fp32 [N] (a per-tensor scalar is expanded).  Activation scales (`input_scale`) are dropped: execution is weight-only."""
+    from ._lib import PsgHipError
+    for k in [k for k in out if k.endswith(".input_scale")]:
+        del out[k]
+    for ks in [k for k in out if k.endswith(".weight" + SCALE_SUFFIX)]:
+        kw = ks[:-len(SCALE_SUFFIX)]
+        w, s = out.get(kw), out[ks].to(torch.float32)
+        if w is None or w.dtype != torch.float8_e4m3fn or w.dim() != 2:
+            raise PsgHipError(f"{path}: {ks} has no float8_e4m3fn matrix {kw} beside it")
+        N = w.shape[0]
+        if s.numel() == 1:
+            s = s.reshape(1).expand(N)
+        elif tuple(s.shape) not in ((N,), (N, 1)):
+            raise PsgHipError(f"{path}: {ks} has shape {tuple(s.shape)}: block-scaled / group-scaled FP8 is not built (a "
+                              f"scalar, [{N}] or [{N}, 1])")
+        out[ks] = s.reshape(N).contiguous()
+    bare = sorted(k for k, v in out.items() if v.dtype == torch.float8_e4m3fn and k + SCALE_SUFFIX not in out)
+    if bare:
+        raise PsgHipError(f"{path}: float8_e4m3fn tensors without a weight_scale: {bare[:3]}")
+    other = sorted(k for k, v in out.items() if v.dtype in (torch.float8_e4m3fnuz, torch.float8_e5m2, torch.float8_e5m2fnuz))
+    if other:
+        raise PsgHipError(f"{path}: only OCP float8_e4m3fn weights are built, got {out[other[0]].dtype} for {other[:3]}")
+    return out
+
+
 # ---- the LLM of a local HuggingFace checkpoint directory (V4:99-103) --------------------------------------------------
 # The reference builds its LLM with `AutoModelForCausalLM.from_pretrained(llm_model_name, low_cpu_mem_usage=True)`
 # (V4:99-100): no dtype, so the fp16 tensors on disk are upcast to fp32; `llm_truncate_num` then keeps the first layers
@@ -278,7 +354,10 @@ def read_hf_llama_config(path, grouped_query=False):
 def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
     """{prefix + name: tensor (stored dtype, CPU)} of the LlamaForCausalLM checkpoint in directory `path`; layers at or
     past `n_layers` (llm_truncate_num, V4:101-103) are not read.  Formats: model.safetensors, model.safetensors.index.json
-    + shards, pytorch_model.bin, pytorch_model.bin.index.json + shards (in that order, as from_pretrained prefers them)."""
+    + shards, pytorch_model.bin, pytorch_model.bin.index.json + shards (in that order, as from_pretrained prefers them).
+    An FP8 checkpoint (a `*.weight` of dtype float8_e4m3fn with a sibling `*.weight_scale`: per-tensor scalar, [N] or
+    [N, 1]) is taken as it is: the matrix stays float8_e4m3fn, its scale becomes fp32 [N] under name + '_scale', nothing
+    is re-quantised; `*.input_scale` entries are ignored (weight-only execution)."""
     import json
     import os
     from ._lib import PsgHipError
@@ -312,7 +391,11 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
             with safe_open(os.path.join(path, fn), framework="pt", device="cpu") as f:
                 for name in (names if names is not None else f.keys()):
                     if wanted(name):
-                        out[prefix + name] = f.get_tensor(name)
+                        try:
+                            out[prefix + name] = f.get_tensor(name)
+                        except Exception as e:  # noqa: BLE001  (a safetensors build without float8_e4m3fn)
+                            raise PsgHipError(f"{path}: cannot read tensor {name!r} from {fn} ({e}); an FP8 checkpoint needs "
+                                              "a safetensors package that delivers float8_e4m3fn") from e
     else:
         files = shards("pytorch_model.bin.index.json", "pytorch_model.bin")
         if files is None:
@@ -328,4 +411,4 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
     bias = sorted(k for k in out if k.endswith(".bias"))
     if bias:
         raise PsgHipError(f"{path}: bias tensors are not built (Llama / Mistral projections have none): {bias[:3]}")
-    return out
+    return _take_fp8_pairs(out, path)

@@ -48,6 +48,9 @@ def parser():
     ap.add_argument("--llm-dir", help="local HuggingFace checkpoint directory of the LLM (config.json + model.safetensors / "
                     "shards / pytorch_model*.bin): read by the head's constructor as the reference's from_pretrained does "
                     "(V4:99-103); without it the LLM is seeded random weights of --llm-layers layers")
+    ap.add_argument("--llm-weight-quant", choices=["fp8"], default=None,
+                    help="fp8: the LLM's projection matrices as OCP e4m3fn bytes with per-row scales (decode steps stream one "
+                    "byte per weight); an FP8 checkpoint in --llm-dir is taken as it is either way")
     return ap
 
 
@@ -62,14 +65,16 @@ def build_head(a, dev):
         trunc = a.llm_layers if 0 < a.llm_layers < llm.layers else -1
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
                                          llm_model_name=a.llm_dir, llm_feature_size=llm.hidden, llm_truncate_num=trunc,
-                                         on_parse_error="skip", pair_selector=a.selector)
+                                         on_parse_error="skip", pair_selector=a.selector,
+                                         llm_weight_quant=getattr(a, "llm_weight_quant", None))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
     else:
         llm = LlamaConfig(layers=a.llm_layers)
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
-                                         llm_config=llm, on_parse_error="skip", pair_selector=a.selector)
+                                         llm_config=llm, on_parse_error="skip", pair_selector=a.selector,
+                                         llm_weight_quant=getattr(a, "llm_weight_quant", None))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
