@@ -71,8 +71,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   602  grouped-query attention: psg_rope_kvwrite_gqa, psg_rope_kvwrite_scaled_gqa, psg_llm_attn_gqa, psg_prefill_attn_gqa,
  *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added
  *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added
- *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added */
-#define PSG_ABI_VERSION 604
+ *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added
+ *   605  training branch in bf16: psg_train_bf16_* added */
+#define PSG_ABI_VERSION 605
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -631,6 +632,38 @@ int psg_train_bce_bwd(psg_ctx*, const float* logit, const float* label, int n, f
 int psg_train_mlcce_fwd(psg_ctx*, const float* logits, const float* labels, int rows, int R, float* loss, void* stream);
 int psg_train_mlcce_bwd(psg_ctx*, const float* logits, const float* labels, int rows, int R, const float* dloss,
                         float* dlogits, void* stream);
+
+/* ---- training branch in bf16 (train_precision='bf16'; csrc/psg_train_bf16.hip).  `void*` activations are
+ * bf16; the residual streams (x of the two norms, their dx), every statistic and dgamma / dbeta are fp32.  Row kernels
+ * take hidden / inter / n as multiples of 8 and 16-byte aligned rows (16-byte accesses), else PSG_ERR_UNSUPPORTED.
+ * psg_train_bf16_layernorm_bwd WRITES dgamma / dbeta (both or neither; summed in a fixed order, no atomics).
+ * attention (matrix cores, head_dim 64 or 128, any Sk): layouts, keep / drop masks and the masking rule of
+ * psg_train_attn_fwd; the forward saves lse fp32 [B][H][Sq] = the row's log-sum-exp of the masked scores (an all-masked
+ * row: finfo(float32).min, which the backward reads as "uniform") instead of the probabilities.  The backward recomputes
+ * P, writes dq / dk / dv (no accumulation, no atomics: bit-identical from run to run) and uses delta fp32 [B][H][Sq] as
+ * its workspace (sum_j p_j dP_j per row). */
+int psg_train_bf16_layernorm_fwd(psg_ctx*, const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
+                                 int hidden, void* y, float* mean, float* rstd, void* stream);
+int psg_train_bf16_layernorm_bwd(psg_ctx*, const float* x, const void* dy, const float* gamma, const float* mean,
+                                 const float* rstd, int64_t rows, int hidden, float* dx, float* dgamma, float* dbeta,
+                                 void* stream);
+int psg_train_bf16_rmsnorm_fwd(psg_ctx*, const float* x, const float* w, float eps, int64_t rows, int hidden, void* y,
+                               float* rstd, void* stream);
+int psg_train_bf16_rmsnorm_bwd(psg_ctx*, const float* x, const void* dy, const float* w, const float* rstd, int64_t rows,
+                               int hidden, float* dx, void* stream);
+int psg_train_bf16_gelu_fwd(psg_ctx*, const void* x, int64_t n, void* y, void* stream);
+int psg_train_bf16_gelu_bwd(psg_ctx*, const void* x, const void* dy, int64_t n, void* dx, void* stream);
+int psg_train_bf16_silu_mul_fwd(psg_ctx*, const void* gate_up, int64_t rows, int inter, void* y, void* stream);
+int psg_train_bf16_silu_mul_bwd(psg_ctx*, const void* gate_up, const void* dy, int64_t rows, int inter, void* dgate_up,
+                                void* stream);
+int psg_train_bf16_rope(psg_ctx*, const void* x, const int32_t* pos, const float* rope_cos, const float* rope_sin,
+                        int table_rows, int64_t rows, int heads, int head_dim, float sign, void* y, void* stream);
+int psg_train_bf16_attn_fwd(psg_ctx*, const void* q, const void* k, const void* v, const uint8_t* keep, int B, int Bk, int H,
+                            int Sq, int Sk, int D, int Mq, float scale, const uint8_t* drop, float drop_scale, void* out,
+                            float* lse, void* stream);
+int psg_train_bf16_attn_bwd(psg_ctx*, const void* q, const void* k, const void* v, const uint8_t* keep, const void* dout,
+                            const float* lse, int B, int Bk, int H, int Sq, int Sk, int D, int Mq, float scale,
+                            const uint8_t* drop, float drop_scale, void* dq, void* dk, void* dv, float* delta, void* stream);
 
 /* ---- 8f: bilinear relation scorer of the closed-set heads (relation_transformer_head_v2.py:204-209):
  * pred[b][r][s][o] = sum_c sub[b][s][r*C + c] * obj[b][o][r*C + c], i.e. einsum('nrsc,nroc->nrso') on the

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpsg_hip.so")
 
-PSG_ABI_VERSION = 604           # include/psg_hip.h; checked against psg_version() of the loaded library
+PSG_ABI_VERSION = 605           # include/psg_hip.h; checked against psg_version() of the loaded library
 PSG_F32, PSG_BF16, PSG_F16 = 0, 1, 2
 PSG_EMPTY_UNIFORM, PSG_EMPTY_UNMASKED = 0, 1
 PSG_XATTN_MFMA, PSG_XATTN_SIMPLE, PSG_XATTN_MFMA_V1 = 0, 1, 2
@@ -131,6 +131,18 @@ SIGNATURES = {
     "psg_train_bce_bwd": [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp],
     "psg_train_mlcce_fwd": [_vp, _vp, _vp, _i, _i, _vp, _vp],
     "psg_train_mlcce_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "psg_train_bf16_layernorm_fwd": [_vp, _vp, _vp, _vp, _f, _i64, _i, _vp, _vp, _vp, _vp],
+    "psg_train_bf16_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp],
+    "psg_train_bf16_rmsnorm_fwd": [_vp, _vp, _vp, _f, _i64, _i, _vp, _vp, _vp],
+    "psg_train_bf16_rmsnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp],
+    "psg_train_bf16_gelu_fwd": [_vp, _vp, _i64, _vp, _vp],
+    "psg_train_bf16_gelu_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "psg_train_bf16_silu_mul_fwd": [_vp, _vp, _i64, _i, _vp, _vp],
+    "psg_train_bf16_silu_mul_bwd": [_vp, _vp, _vp, _i64, _i, _vp, _vp],
+    "psg_train_bf16_rope": [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _f, _vp, _vp],
+    "psg_train_bf16_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _vp, _vp, _vp],
+    "psg_train_bf16_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _vp, _vp, _vp,
+                                _vp, _vp],
     "psg_greedy_step": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "psg_tree_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "psg_token_logprobs": [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _vp],

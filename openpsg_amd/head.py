@@ -11,7 +11,7 @@ Differences that are deliberate and documented:
   * V4:355-356 raises UnboundLocalError in the default 'binary' mode as committed; this head
     implements the intended contract: rel_pred = LLM triples, rel_score = 1 each (SURVEY 0.3);
   * the training branch computes the reference's two losses (`forward_train`: values through the inference kernels;
-    `forward_train_grad`: fp32, with the gradient graph - openpsg_amd/train_graph.py; SURVEY 8f rank 3);
+    `forward_train_grad`: with the gradient graph, fp32 or train_precision='bf16' - openpsg_amd/train_graph.py; SURVEY 8f rank 3);
   * rel_cls_type 'binary+multiclass' / 'multiclass' (V4:31, 91-95): the multiclass triples follow the LLM triples with
     the diagonal zeroed and the flat index decoded as p*R + r (V4:239-250 as intended), and 'multiclass' alone runs no
     pair selector or decode (DESIGN 9);
@@ -234,8 +234,16 @@ class RelationTransformerHeadV4(nn.Module):
                                                # steps of <= 32 rows stream 1 byte per weight.  The model IS the quantised one
                                                # (W' = q s) on every path; an FP8 checkpoint is taken as it is
                  llm_quantize_lm_head=False,   # 'fp8': the lm_head as well (never the embedding, norms, language_projection)
+                 train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
+                                               # reference - bf16 activations and products on fp32 masters, with
+                                               # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
                  **kwargs):
         super().__init__()
+        if train_precision not in (None, "bf16"):
+            raise PsgHipError(f"train_precision must be None or 'bf16', got {train_precision!r} (fp16 training is not "
+                              "offered: 'If use fp16, the loss will be nan', V4)")
+        self.train_precision = train_precision
+        self._train_llm_copy = None
         if llm_weight_quant not in (None, "fp8"):
             raise PsgHipError(f"llm_weight_quant must be None or 'fp8', got {llm_weight_quant!r}")
         if llm_weight_quant is not None and "binary" not in rel_cls_type:
@@ -341,8 +349,9 @@ class RelationTransformerHeadV4(nn.Module):
         # mmdet-style flow wraps the model in DistributedDataParallel BEFORE runner.train() calls model.train(), and DDP
         # registers its reducer hooks for the parameters that require a gradient at that moment.  A caller's own
         # freezes (requires_grad_(False) on part of the head) are never touched again.
+        # train_precision='bf16' trains the fp32 masters of a head of any dtype: the same argument applies.
         for p_ in self.parameters():
-            p_.requires_grad_(self.act_dtype == torch.float32)
+            p_.requires_grad_(self.act_dtype == torch.float32 or self.train_precision is not None)
         self._engine_version = None
         self._llm_weights = None
         self._rq_engine = None
@@ -570,7 +579,7 @@ class RelationTransformerHeadV4(nn.Module):
 
     def forward(self, inputs, is_generation=None):
         if self.training:
-            if self.act_dtype == torch.float32 and torch.is_grad_enabled():
+            if (self.act_dtype == torch.float32 or self.train_precision is not None) and torch.is_grad_enabled():
                 return self.forward_train_grad(inputs)            # the losses with their gradient graph (V4:345-351)
             if not self.train_losses_without_grad:
                 raise NotImplementedError(
@@ -870,12 +879,16 @@ class RelationTransformerHeadV4(nn.Module):
         sum of the two losses): the same arithmetic through `openpsg_amd/train_graph.py` - torch.autograd nodes whose
         forward / backward are the fp32 kernels of csrc/psg_train_bwd.hip, library GEMMs for the projections.  Gradients
         reach patch_embed, the Q-Former, relation_query / rel_cls_query, binary_rel_cls_pred and language_projection;
-        the LLM is frozen (CFG:65) and only passes the gradient through.  fp32 heads only.
+        the LLM is frozen (CFG:65) and only passes the gradient through.  fp32 heads - or, with train_precision='bf16', a
+        head of any dtype: the graph then runs on csrc/psg_train_bf16.hip in the bf16 model of DESIGN 13 (bf16 activations
+        and products, fp32 residual streams / statistics / losses, fp32 gradients on the fp32 masters).
         dropout: None = `train_dropout` (on by default: the reference trains its Q-Former with HF's default dropouts
         active, V4:78-84); False = off (what the oracle and the goldens are captured with); or a train_graph.Dropout."""
         from . import train_graph as G
-        if self.act_dtype != torch.float32:
-            raise PsgHipError("forward_train_grad: the gradient path runs in fp32 (construct the head with dtype='fp32')")
+        prec = self.train_precision
+        if prec is None and self.act_dtype != torch.float32:
+            raise PsgHipError("forward_train_grad: the gradient path runs in fp32 (construct the head with dtype='fp32', or "
+                              "with train_precision='bf16')")
         dev = self.device
         q = self.cfg.qformer
         with torch.enable_grad():
@@ -896,15 +909,17 @@ class RelationTransformerHeadV4(nn.Module):
                 dropout = self.train_dropout
             if dropout is True:
                 dropout = G.Dropout(q.hidden_dropout, q.attn_dropout)
-            h = G.qformer_pairs(P, self.cfg, patches, t["ids"].to(torch.int64), t["msk"], keep, dropout or None)
+            h = G.qformer_pairs(P, self.cfg, patches, t["ids"].to(torch.int64), t["msk"], keep, dropout or None, prec)
             out_s = h[:, :q.q_rows]                                                          # V4:185
             losses, logit, mc_logit = {}, None, None
             if self.has_binary:
-                logit = F.linear(out_s[:, 0], P["binary_rel_cls_pred.weight"], P["binary_rel_cls_pred.bias"]).squeeze(1)
+                logit = G.linear(out_s[:, 0], P["binary_rel_cls_pred.weight"], P["binary_rel_cls_pred.bias"], prec)
+                logit = logit.squeeze(1).float()                                         # the losses take fp32 logits
                 losses["binary_rel_cls_loss"] = G.BceFn.apply(logit, t["binary"][t["sampled"]].to(dev),
                                                               self.rel_cls_loss_weight)
             if self.has_multiclass:                                                          # V4:196-204, 473-477
-                mc_logit = F.linear(out_s[:, 0], P["multiclass_rel_cls_pred.weight"], P["multiclass_rel_cls_pred.bias"])
+                mc_logit = G.linear(out_s[:, 0], P["multiclass_rel_cls_pred.weight"], P["multiclass_rel_cls_pred.bias"],
+                                    prec).float()
                 losses["multiclass_rel_cls_loss"] = G.multiclass_loss(mc_logit, t["mc_label"].to(dev),
                                                                       self.rel_cls_loss_weight)
             # pair features of the selected pairs as the reference builds them (V4:177, 186): a zero table of all N*N pairs,
@@ -915,12 +930,12 @@ class RelationTransformerHeadV4(nn.Module):
             table = out_s.new_zeros((N * N, q.q_rows, q.hidden))
             table = table.index_put((sp.to(torch.int64),), out_s)
             pf = table[torch.tensor(t["selected"], dtype=torch.int64, device=dev), 1:]
-            vis = F.linear(pf, P["language_projection.weight"], P["language_projection.bias"])               # V4:294
-            llm = self.llm_engine
+            vis = G.linear(pf, P["language_projection.weight"], P["language_projection.bias"], prec)         # V4:294
+            llm = self.llm_engine if prec is None else self._train_llm()
             cids = t["cids"].to(torch.int64)
-            tokv = llm.embed[cids.clamp(min=0)] * (cids >= 0)[..., None].to(torch.float32)  # frozen embeddings (V4:296)
+            tokv = llm.embed[cids.clamp(min=0)] * (cids >= 0)[..., None].to(vis.dtype)      # frozen embeddings (V4:296)
             X = torch.cat([vis, tokv], dim=1)
-            logits = G.llama_teacher_forcing(llm, self.cfg, X, t["seq_len"], t["rpos"], t["flat_rows"].to(torch.int64))
+            logits = G.llama_teacher_forcing(llm, self.cfg, X, t["seq_len"], t["rpos"], t["flat_rows"].to(torch.int64), prec)
             rl = G.CrossEntropyRowsFn.apply(logits, t["want_lab"])
             per_pair = self._mean_per_pair(rl, t["counts"])
             llm_loss = torch.stack(per_pair).mean()                                          # V4:350-351
@@ -938,7 +953,25 @@ class RelationTransformerHeadV4(nn.Module):
         super().train(mode)
         self._rq_engine = None
         self._proj_stale = True
+        if not mode:
+            self._train_llm_copy = None                           # the bf16 training copy of the frozen LLM, if one was made
         return self
+
+    def _train_llm(self):
+        """The frozen LLM as train_precision='bf16' reads it: the decode engine's own tensors when it holds them in bf16,
+        else a bf16 copy made at the first training step and dropped by train(False).  FP8-quantised weights
+        (llm_weight_quant='fp8') train on W' = q s rounded to bf16."""
+        eng = self.llm_engine
+        if eng.dtype == torch.bfloat16:
+            return eng
+        if self._train_llm_copy is None:
+            from types import SimpleNamespace
+            b = lambda t: t.to(torch.bfloat16)                   # noqa: E731
+            self._train_llm_copy = SimpleNamespace(
+                embed=b(eng.embed), lm_head=b(eng.lm_head), final_norm=eng.final_norm, rope=eng.rope,
+                layers=[dict(wqkv=b(L["wqkv"]), wo=b(L["wo"]), wgu=b(L["wgu"]), wdown=b(L["wdown"]), ln1=L["ln1"],
+                             ln2=L["ln2"]) for L in eng.layers])
+        return self._train_llm_copy
 
     def forward_batch(self, batch):
         """Throughput mode for several images (the reference handles one image per call, V4:112): the

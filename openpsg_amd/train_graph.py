@@ -9,7 +9,12 @@ The graph is torch.autograd's; its nodes are
     RMSNorm, the three attentions (Q-Former self / cross with the pair masks, Llama causal), GELU, the SwiGLU gate,
     rotary, cross entropy and BCE-with-logits.
 Training batches are tiny (<= 32 sampled pairs, <= 4 LLM pairs, V4:29-30, 38), so this path is written for exactness
-against autograd on the CPU oracle (tests/test_gpu_train.py), not for speed.  fp32 only; no CPU path.
+against autograd on the CPU oracle (tests/test_gpu_train.py), not for speed.  No CPU path.
+
+precision='bf16' (the head's train_precision) runs the same graph in the model torch.autocast(bfloat16) gives
+the reference: the `*Bf16Fn` nodes below are the kernels of csrc/psg_train_bf16.hip (bf16 activations, fp32 residual
+streams and statistics, the attention on the matrix cores), `LinearBf16Fn` is a bf16 library GEMM whose weight gradient
+leaves its fp32 accumulator as fp32 onto the fp32 master.  `PatchEmbedFn`, the losses and the sampler are shared.
 """
 from __future__ import annotations
 
@@ -289,6 +294,228 @@ class PatchEmbedFn(torch.autograd.Function):
         return None, dw, dp.sum(0), None
 
 
+# ---- precision='bf16'  -----------------------------------------------------------------------------------------
+BF16 = torch.bfloat16
+
+
+def _b16(t, name="tensor"):
+    if t.dtype != BF16 or not t.is_cuda:
+        raise PsgHipError(f"{name}: the bf16 gradient path takes bf16 activations on the GPU (got {t.dtype} on {t.device})")
+    return t.contiguous()
+
+
+class LinearBf16Fn(torch.autograd.Function):
+    """x bf16 . W^T (+ b) with W, b the fp32 MASTERS: both operands bf16, fp32 accumulation, bf16 output; backward:
+    dx bf16, dW = dy^T x written from the fp32 accumulator as fp32, db summed in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = _b16(x, "linear x")
+        wb = weight.to(BF16)
+        ctx.save_for_backward(x, wb)
+        ctx.has_bias = bias is not None
+        return F.linear(x, wb, None if bias is None else bias.to(BF16))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wb = ctx.saved_tensors
+        dy2 = _b16(dy).reshape(-1, dy.shape[-1])
+        dx = (dy2 @ wb).view(x.shape) if ctx.needs_input_grad[0] else None
+        dw = torch.mm(dy2.t(), x.reshape(-1, x.shape[-1]), out_dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        db = dy2.sum(0, dtype=torch.float32) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db
+
+
+class LayerNormBf16Fn(torch.autograd.Function):
+    """x fp32 (the residual stream) -> y bf16; gamma / beta fp32 masters; dx, dgamma, dbeta fp32."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x, gamma, beta = _f32(x, "layernorm x"), _f32(gamma), _f32(beta)
+        hidden = x.shape[-1]
+        rows = x.numel() // hidden
+        y = torch.empty(x.shape, device=x.device, dtype=BF16)
+        mean = torch.empty(rows, device=x.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_layernorm_fwd(c, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), rows, hidden,
+                                               y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), st),
+              "psg_train_bf16_layernorm_fwd")
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        dy = _b16(dy)
+        hidden = x.shape[-1]
+        dx = torch.empty_like(x)
+        dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_layernorm_bwd(c, x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                               rstd.data_ptr(), x.numel() // hidden, hidden, dx.data_ptr(), dg.data_ptr(),
+                                               db.data_ptr(), st), "psg_train_bf16_layernorm_bwd")
+        return dx, dg, db, None
+
+
+class RMSNormBf16Fn(torch.autograd.Function):
+    """x fp32 (the Llama residual stream) -> y bf16, FROZEN fp32 weight; dx fp32."""
+
+    @staticmethod
+    def forward(ctx, x, w, eps):
+        x, w = _f32(x, "rmsnorm x"), _f32(w)
+        hidden = x.shape[-1]
+        rows = x.numel() // hidden
+        y = torch.empty(x.shape, device=x.device, dtype=BF16)
+        rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_rmsnorm_fwd(c, x.data_ptr(), w.data_ptr(), float(eps), rows, hidden, y.data_ptr(),
+                                             rstd.data_ptr(), st), "psg_train_bf16_rmsnorm_fwd")
+        ctx.save_for_backward(x, w, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, rstd = ctx.saved_tensors
+        dy = _b16(dy)
+        hidden = x.shape[-1]
+        dx = torch.empty_like(x)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_rmsnorm_bwd(c, x.data_ptr(), dy.data_ptr(), w.data_ptr(), rstd.data_ptr(),
+                                             x.numel() // hidden, hidden, dx.data_ptr(), st), "psg_train_bf16_rmsnorm_bwd")
+        return dx, None, None
+
+
+class AttnBf16Fn(torch.autograd.Function):
+    """AttnFn's arguments and masking rule on bf16 q / k / v, on the matrix cores; saves the row log-sum-exp, not the
+    probabilities; dq / dk / dv bf16, each element written once (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, keep, heads, scale, drop=None):
+        q, k, v = _b16(q, "attention q"), _b16(k), _b16(v)
+        keep = keep.to(torch.uint8).contiguous()
+        B, Sq, hid = q.shape
+        Bk, Sk, _ = k.shape
+        Mq = keep.shape[1]
+        assert keep.shape == (B, Mq, Sk) and v.shape == k.shape and Bk in (B, 1)
+        dmask, dscale = (None, 1.0) if drop is None else (drop[0].to(torch.uint8).contiguous(), float(drop[1]))
+        assert dmask is None or dmask.shape == (B, heads, Sq, Sk)
+        lse = torch.empty((B, heads, Sq), device=q.device, dtype=torch.float32)
+        out = torch.empty_like(q)
+        lib, c, st = _env(q)
+        check(lib.psg_train_bf16_attn_fwd(c, q.data_ptr(), k.data_ptr(), v.data_ptr(), keep.data_ptr(), B, Bk, heads, Sq, Sk,
+                                          hid // heads, Mq, float(scale), None if dmask is None else dmask.data_ptr(), dscale,
+                                          out.data_ptr(), lse.data_ptr(), st), "psg_train_bf16_attn_fwd")
+        ctx.save_for_backward(q, k, v, keep, lse)
+        ctx.heads, ctx.scale, ctx.dmask, ctx.dscale = heads, float(scale), dmask, dscale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, keep, lse = ctx.saved_tensors
+        dout = _b16(dout)
+        B, Sq, hid = q.shape
+        Bk, Sk, _ = k.shape
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        delta = torch.empty_like(lse)
+        lib, c, st = _env(q)
+        check(lib.psg_train_bf16_attn_bwd(c, q.data_ptr(), k.data_ptr(), v.data_ptr(), keep.data_ptr(), dout.data_ptr(),
+                                          lse.data_ptr(), B, Bk, ctx.heads, Sq, Sk, hid // ctx.heads, keep.shape[1], ctx.scale,
+                                          None if ctx.dmask is None else ctx.dmask.data_ptr(), ctx.dscale, dq.data_ptr(),
+                                          dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), st), "psg_train_bf16_attn_bwd")
+        return dq, dk, dv, None, None, None, None
+
+
+class GeluBf16Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _b16(x, "gelu x")
+        y = torch.empty_like(x)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_gelu_fwd(c, x.data_ptr(), x.numel(), y.data_ptr(), st), "psg_train_bf16_gelu_fwd")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dy = _b16(dy)
+        dx = torch.empty_like(x)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_gelu_bwd(c, x.data_ptr(), dy.data_ptr(), x.numel(), dx.data_ptr(), st),
+              "psg_train_bf16_gelu_bwd")
+        return dx
+
+
+class SiluMulBf16Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gu):
+        gu = _b16(gu, "gate_up")
+        rows, two = gu.shape
+        y = torch.empty((rows, two // 2), device=gu.device, dtype=BF16)
+        lib, c, st = _env(gu)
+        check(lib.psg_train_bf16_silu_mul_fwd(c, gu.data_ptr(), rows, two // 2, y.data_ptr(), st),
+              "psg_train_bf16_silu_mul_fwd")
+        ctx.save_for_backward(gu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        gu, = ctx.saved_tensors
+        dy = _b16(dy)
+        d = torch.empty_like(gu)
+        lib, c, st = _env(gu)
+        check(lib.psg_train_bf16_silu_mul_bwd(c, gu.data_ptr(), dy.data_ptr(), gu.shape[0], gu.shape[1] // 2, d.data_ptr(),
+                                              st), "psg_train_bf16_silu_mul_bwd")
+        return d
+
+
+class RopeBf16Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pos, cos, sin, heads):
+        x = _b16(x, "rope x")
+        if pos.numel() and (int(pos.max()) >= cos.shape[0] or int(pos.min()) < 0):      # training only: one read-back
+            raise PsgHipError(f"rope: position {int(pos.max())} outside the {cos.shape[0]}-row rotary table")
+        ctx.save_for_backward(pos, cos, sin)
+        ctx.heads = heads
+        return RopeBf16Fn._run(x, pos, cos, sin, heads, 1.0)
+
+    @staticmethod
+    def _run(x, pos, cos, sin, heads, sign):
+        rows, hid = x.shape
+        y = torch.empty_like(x)
+        lib, c, st = _env(x)
+        check(lib.psg_train_bf16_rope(c, x.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], rows,
+                                      heads, hid // heads, float(sign), y.data_ptr(), st), "psg_train_bf16_rope")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        pos, cos, sin = ctx.saved_tensors
+        return RopeBf16Fn._run(_b16(dy), pos, cos, sin, ctx.heads, -1.0), None, None, None, None
+
+
+class _Nodes:
+    """The graph's nodes for one precision: `qformer_pairs` / `llama_teacher_forcing` are written once over them.
+    resid(a, b): the sum a LayerNorm / the Llama stream takes - fp32 in both precisions."""
+
+    def __init__(self, precision):
+        if precision not in (None, "bf16"):
+            raise PsgHipError(f"precision must be None or 'bf16', got {precision!r}")
+        b = precision == "bf16"
+        self.bf16 = b
+        self.ln, self.rms = (LayerNormBf16Fn if b else LayerNormFn).apply, (RMSNormBf16Fn if b else RMSNormFn).apply
+        self.attn, self.gelu = (AttnBf16Fn if b else AttnFn).apply, (GeluBf16Fn if b else GeluFn).apply
+        self.silu, self.rope = (SiluMulBf16Fn if b else SiluMulFn).apply, (RopeBf16Fn if b else RopeFn).apply
+        self.linear = LinearBf16Fn.apply if b else F.linear
+        self.act = (lambda t: t.to(BF16)) if b else (lambda t: t)
+        self.resid = (lambda a, r: a.float() + r.float()) if b else (lambda a, r: a + r)
+
+
+def linear(x, weight, bias=None, precision=None):
+    return _Nodes(precision).linear(x, weight, bias)
+
+
 def layer_norm(x, gamma, beta, eps):
     return LayerNormFn.apply(x, gamma, beta, eps)
 
@@ -311,7 +538,8 @@ class Dropout:
     def hidden(self, x):
         if self.p_hidden <= 0:
             return x
-        return x * (self._keep(x.shape, self.p_hidden, x.device).to(x.dtype) / (1.0 - self.p_hidden))
+        keep = self._keep(x.shape, self.p_hidden, x.device).to(torch.float32) / (1.0 - self.p_hidden)
+        return x * keep if x.dtype == torch.float32 else (x.float() * keep).to(x.dtype)   # 16-bit x: one rounding
 
     def attn(self, B, heads, Sq, Sk, device):
         if self.p_attn <= 0:
@@ -319,11 +547,14 @@ class Dropout:
         return self._keep((B, heads, Sq, Sk), self.p_attn, device).to(torch.uint8), 1.0 / (1.0 - self.p_attn)
 
 
-def qformer_pairs(P, cfg, patches, ids, text_mask, pair_keep, dropout: Dropout | None = None):
+def qformer_pairs(P, cfg, patches, ids, text_mask, pair_keep, dropout: Dropout | None = None, precision=None):
     """The relation Q-Former (HF-IB:446-757 as driven by V4:179-185) over B pairs, all rows of all layers (training
     keeps the text rows of the last layer out of the loss, V4:185, but computes them like the reference).
     P: parameters by reference name; patches [L, C]; ids int64 [B, T]; text_mask [B, T]; pair_keep uint8 [B, L].
-    dropout: None = off (the oracle comparison), or a `Dropout` plan.  Returns the last hidden state [B, 33 + T, 768]."""
+    dropout: None = off (the oracle comparison), or a `Dropout` plan.  precision: None = fp32 | 'bf16' (patches may come
+    in fp32; the hidden states are then bf16).  Returns the last hidden state [B, 33 + T, 768]."""
+    n = _Nodes(precision)
+    layer_norm, patches = n.ln, n.act(patches)
     q = cfg.qformer
     nq, H, heads = q.q_rows, q.hidden, q.heads
     B, T = ids.shape
@@ -340,33 +571,37 @@ def qformer_pairs(P, cfg, patches, ids, text_mask, pair_keep, dropout: Dropout |
     self_keep = torch.cat([torch.ones((B, nq), dtype=torch.uint8, device=dev), text_mask.to(torch.uint8)], dim=1)[:, None, :]
     cross_keep = pair_keep.to(torch.uint8)[:, None, :]
     scale = (H // heads) ** -0.5
-    lin = lambda pfx, x: F.linear(x, P[pfx + ".weight"], P[pfx + ".bias"])  # noqa: E731
+    lin = lambda pfx, x: n.linear(x, P[pfx + ".weight"], P[pfx + ".bias"])  # noqa: E731
+    attn, gelu, add = n.attn, n.gelu, n.resid
     for l in range(q.layers):
         p = f"relation_qformer.encoder.layer.{l}."
-        a = AttnFn.apply(lin(p + "attention.attention.query", h), lin(p + "attention.attention.key", h),
+        a = attn(lin(p + "attention.attention.query", h), lin(p + "attention.attention.key", h),
                          lin(p + "attention.attention.value", h), self_keep, heads, scale, da(B, heads, S, S, dev))
-        a = layer_norm(dh(lin(p + "attention.output.dense", a)) + h, P[p + "attention.output.LayerNorm.weight"],
+        a = layer_norm(add(dh(lin(p + "attention.output.dense", a)), h), P[p + "attention.output.LayerNorm.weight"],
                        P[p + "attention.output.LayerNorm.bias"], q.ln_eps)
         q33 = a[:, :nq]
         kx = lin(p + "crossattention.attention.key", patches)[None]                           # shared by every pair
         vx = lin(p + "crossattention.attention.value", patches)[None]
-        c = AttnFn.apply(lin(p + "crossattention.attention.query", q33), kx, vx, cross_keep, heads, scale,
+        c = attn(lin(p + "crossattention.attention.query", q33), kx, vx, cross_keep, heads, scale,
                          da(B, heads, nq, L, dev))
-        c = layer_norm(dh(lin(p + "crossattention.output.dense", c)) + q33, P[p + "crossattention.output.LayerNorm.weight"],
+        c = layer_norm(add(dh(lin(p + "crossattention.output.dense", c)), q33), P[p + "crossattention.output.LayerNorm.weight"],
                        P[p + "crossattention.output.LayerNorm.bias"], q.ln_eps)
-        hq = layer_norm(dh(lin(p + "output_query.dense", GeluFn.apply(lin(p + "intermediate_query.dense", c)))) + c,
+        hq = layer_norm(add(dh(lin(p + "output_query.dense", gelu(lin(p + "intermediate_query.dense", c)))), c),
                         P[p + "output_query.LayerNorm.weight"], P[p + "output_query.LayerNorm.bias"], q.ln_eps)
         at = a[:, nq:]
-        ht = layer_norm(dh(lin(p + "output.dense", GeluFn.apply(lin(p + "intermediate.dense", at)))) + at,
+        ht = layer_norm(add(dh(lin(p + "output.dense", gelu(lin(p + "intermediate.dense", at)))), at),
                         P[p + "output.LayerNorm.weight"], P[p + "output.LayerNorm.bias"], q.ln_eps)
         h = torch.cat([hq, ht], dim=1)
     return h
 
 
-def llama_teacher_forcing(engine, cfg, X, seq_len, rope_pos, rows):
+def llama_teacher_forcing(engine, cfg, X, seq_len, rope_pos, rows, precision=None):
     """Plain `language_model(inputs_embeds, attention_mask)` forward (V4:327-336) through the FROZEN Llama, on compact
     sequences X [K, S, D] (valid tokens first), rope_pos int32 [K, S] = each token's position in the reference's padded
-    sequence (-1 behind a sequence's end), rows int64: flat row indices whose logits are wanted.  Returns fp32 logits."""
+    sequence (-1 behind a sequence's end), rows int64: flat row indices whose logits are wanted.  Returns fp32 logits.
+    precision='bf16': `engine` holds bf16 matrices (the head's `_train_llm`), X may be bf16; the stream x is fp32."""
+    n = _Nodes(precision)
+    rms, rope, attn, silu = n.rms, n.rope, n.attn, n.silu
     m = cfg.llm
     K, S, D = X.shape
     dev = X.device
@@ -377,26 +612,26 @@ def llama_teacher_forcing(engine, cfg, X, seq_len, rope_pos, rows):
     keep = keep.to(torch.uint8).contiguous()
     pos = rope_pos.clamp(min=0).reshape(-1).to(torch.int32).contiguous()
     cos, sin = engine.rope
-    x = X
+    x = X.float() if n.bf16 else X                                            # the residual stream: fp32
     scale = m.head_dim ** -0.5
     for L in engine.layers:
-        n1 = RMSNormFn.apply(x, L["ln1"], m.rms_eps)
+        n1 = rms(x, L["ln1"], m.rms_eps)
         qkv = F.linear(n1, L["wqkv"])
-        qh = RopeFn.apply(qkv[..., :D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
+        qh = rope(qkv[..., :D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
         if m.n_kv_heads == m.heads:
-            kh = RopeFn.apply(qkv[..., D:2 * D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
+            kh = rope(qkv[..., D:2 * D].reshape(K * S, D), pos, cos, sin, m.heads).view(K, S, D)
             vh = qkv[..., 2 * D:].contiguous()
         else:
             # grouped-query attention: rotate the kv_heads key heads, then give every query head its group's key / value
             # head (repeat_interleave; autograd sums dK / dV over each group)
             Dk, G = m.kv_dim, m.kv_group
-            kg = RopeFn.apply(qkv[..., D:D + Dk].reshape(K * S, Dk), pos, cos, sin, m.n_kv_heads)
+            kg = rope(qkv[..., D:D + Dk].reshape(K * S, Dk), pos, cos, sin, m.n_kv_heads)
             kh = kg.view(K, S, m.n_kv_heads, 1, m.head_dim).expand(-1, -1, -1, G, -1).reshape(K, S, D)
             vh = qkv[..., D + Dk:].reshape(K, S, m.n_kv_heads, 1, m.head_dim).expand(-1, -1, -1, G, -1).reshape(K, S, D)
-        att = AttnFn.apply(qh, kh, vh, keep, m.heads, scale)
-        x = x + F.linear(att, L["wo"])
-        n2 = RMSNormFn.apply(x, L["ln2"], m.rms_eps)
-        act = SiluMulFn.apply(F.linear(n2, L["wgu"]).view(K * S, -1)).view(K, S, -1)
-        x = x + F.linear(act, L["wdown"])
-    hfin = RMSNormFn.apply(x, engine.final_norm, m.rms_eps).reshape(K * S, D)
-    return F.linear(hfin.index_select(0, rows), engine.lm_head)
+        att = attn(qh, kh, vh, keep, m.heads, scale)
+        x = n.resid(x, F.linear(att, L["wo"]))
+        n2 = rms(x, L["ln2"], m.rms_eps)
+        act = silu(F.linear(n2, L["wgu"]).view(K * S, -1)).view(K, S, -1)
+        x = n.resid(x, F.linear(act, L["wdown"]))
+    hfin = rms(x, engine.final_norm, m.rms_eps).reshape(K * S, D)
+    return F.linear(hfin.index_select(0, rows), engine.lm_head).float()    # the loss takes fp32 logits
