@@ -1,4 +1,4 @@
-// Training branch in bf16 (train_precision='bf16'): the row / attention kernels of psg_train_bwd.hip for
+// Training branch in bf16 (train_precision='bf16'): the row / attention entry points of psg_train_bwd.hip for
 // activations stored as bf16, in the precision model torch.autocast(bfloat16) gives the reference:
 //   * activations that a product, an attention or a pointwise kernel reads (and saves for its backward) are bf16;
 //   * the two residual streams (the Q-Former's LayerNorm inputs, the Llama x), the LayerNorm / RMSNorm / softmax
@@ -11,7 +11,8 @@
 //   psg_train_bf16_attn_fwd / _bwd        attention on v_mfma_f32_32x32x16_bf16, keys walked in tiles of 32, the row
 //                                         log-sum-exp saved instead of the probabilities; the backward recomputes P
 //
-// Row kernels: one wave per row, 16-byte accesses (8 bf16 / 2 x 4 fp32 per lane and step), hidden % 8 == 0.
+// Row and pointwise kernels: the templates of psg_train_rows.h with the TrBf16 access policy - one wave per row, 16-byte
+// accesses (8 bf16 / 2 x 4 fp32 per lane and step), hidden % 8 == 0.  Only LayerNorm's dgamma / dbeta kernel is written here.
 //
 // Attention.  One wave per workgroup.  Every product is computed TRANSPOSED, so that a lane owns one column of the
 // 32 x 32 result tile (lane & 31) and 16 of its rows ((r & 3) + 8 (r >> 2) + 4 (lane >> 5), r = 0..15):
@@ -25,7 +26,7 @@
 // pass of the dQ kernel, handed to the dK / dV kernel in `delta`) rather than taken from the bf16-rounded output.
 // Masking as psg_train_attn_fwd: additive finfo(float32).min in fp32; an all-masked row is a uniform softmax.  Its
 // log-sum-exp is finfo.min + log(Sk) == finfo.min in fp32: the backward recognises the row by that value and uses 1 / Sk.
-#include "psg_wave.h"
+#include "psg_train_rows.h"
 
 #define TB_FMIN (-3.4028234663852886e38f)
 
@@ -35,104 +36,6 @@ union TbPack8 {                                   // 8 bf16 = one 16-byte access
   uint32_t w[4];
   tb_v8 v;
 };
-
-__device__ __forceinline__ void tb_ld8(const uint16_t* p, float (&o)[8]) {
-  TbPack8 t;
-  t.u = *reinterpret_cast<const uint4*>(p);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    o[2 * e] = __uint_as_float(t.w[e] << 16);
-    o[2 * e + 1] = __uint_as_float(t.w[e] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void tb_st8(uint16_t* p, const float (&v)[8]) {
-  TbPack8 t;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) t.w[e] = EBf16::pack(v[2 * e], v[2 * e + 1]);
-  *reinterpret_cast<uint4*>(p) = t.u;
-}
-__device__ __forceinline__ void tb_ld8f(const float* p, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-__device__ __forceinline__ void tb_st8f(float* p, const float (&v)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-
-// ---- LayerNorm: x fp32 -> y bf16 ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tb_layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float eps, int64_t rows,
-                                                               int hidden, uint16_t* __restrict__ y, float* __restrict__ mean,
-                                                               float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float* xr = x + row * hidden;
-  float a[8], s = 0.f;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    tb_ld8f(xr + c, a);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += a[e];
-  }
-  const float mu = wave_sum(s) / (float)hidden;
-  float v = 0.f;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    tb_ld8f(xr + c, a);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v += (a[e] - mu) * (a[e] - mu);
-  }
-  const float rs = 1.0f / sqrtf(wave_sum(v) / (float)hidden + eps);
-  for (int c = lane * 8; c < hidden; c += 512) {
-    float g[8], b[8], o[8];
-    tb_ld8f(xr + c, a);
-    tb_ld8f(gamma + c, g);
-    tb_ld8f(beta + c, b);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (a[e] - mu) * rs * g[e] + b[e];
-    tb_st8(y + row * hidden + c, o);
-  }
-  if (lane == 0) {
-    mean[row] = mu;
-    rstd[row] = rs;
-  }
-}
-
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma (dx fp32: the gradient of the residual stream)
-__global__ void __launch_bounds__(256) tb_layernorm_bwd_kernel(const float* __restrict__ x, const uint16_t* __restrict__ dy,
-                                                               const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, int64_t rows, int hidden,
-                                                               float* __restrict__ dx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float mu = mean[row], rs = rstd[row];
-  const float* xr = x + row * hidden;
-  const uint16_t* dr = dy + row * hidden;
-  float xa[8], d[8], g[8], a = 0.f, b = 0.f;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    tb_ld8f(xr + c, xa);
-    tb_ld8(dr + c, d);
-    tb_ld8f(gamma + c, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float t = d[e] * g[e];
-      a += t;
-      b += t * ((xa[e] - mu) * rs);
-    }
-  }
-  a = wave_sum(a) / (float)hidden;
-  b = wave_sum(b) / (float)hidden;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    float o[8];
-    tb_ld8f(xr + c, xa);
-    tb_ld8(dr + c, d);
-    tb_ld8f(gamma + c, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = rs * (d[e] * g[e] - a - (xa[e] - mu) * rs * b);
-    tb_st8f(dx + row * hidden + c, o);
-  }
-}
 
 // dgamma[c] = sum_rows dy xhat, dbeta[c] = sum_rows dy: one thread per (column, row group), the 16 row groups of a
 // column summed in a fixed order - no atomics, the same bits on every run
@@ -167,31 +70,20 @@ __global__ void __launch_bounds__(1024) tb_layernorm_dgb_kernel(const float* __r
 
 #define TB_ALIGNED16(p) ((((uintptr_t)(p)) & 15u) == 0)
 
+// ---- LayerNorm, RMSNorm: x fp32 -> y bf16; dy bf16 -> dx fp32 (psg_train_rows.h at 16-byte accesses) ---------------------
 extern "C" int psg_train_bf16_layernorm_fwd(psg_ctx* ctx, const float* x, const float* gamma, const float* beta, float eps,
                                             int64_t rows, int hidden, void* y, float* mean, float* rstd, void* stream) {
-  PSG_REQUIRE(ctx && x && gamma && beta && y && mean && rstd && hidden > 0 && rows >= 0, PSG_ERR_INVALID,
-              "psg_train_bf16_layernorm_fwd: bad argument");
-  PSG_REQUIRE(hidden % 8 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(gamma) && TB_ALIGNED16(beta) && TB_ALIGNED16(y),
-              PSG_ERR_UNSUPPORTED, "psg_train_bf16_layernorm_fwd: hidden=%d (a multiple of 8, 16-byte aligned rows)", hidden);
-  if (rows == 0) return PSG_OK;
-  tb_layernorm_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, gamma, beta, eps, rows, hidden,
-                                                                                      (uint16_t*)y, mean, rstd);
-  PSG_CHECK_LAUNCH("psg_train_bf16_layernorm_fwd");
-  return PSG_OK;
+  return tr_layernorm_fwd_launch<TrBf16>("psg_train_bf16_layernorm_fwd", ctx, x, gamma, beta, eps, rows, hidden, y, mean, rstd,
+                                         stream);
 }
 
 extern "C" int psg_train_bf16_layernorm_bwd(psg_ctx* ctx, const float* x, const void* dy, const float* gamma,
                                             const float* mean, const float* rstd, int64_t rows, int hidden, float* dx,
                                             float* dgamma, float* dbeta, void* stream) {
-  PSG_REQUIRE(ctx && x && dy && gamma && mean && rstd && dx && hidden > 0 && rows >= 0 && (!dgamma == !dbeta),
-              PSG_ERR_INVALID, "psg_train_bf16_layernorm_bwd: bad argument");
-  PSG_REQUIRE(hidden % 8 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(gamma) && TB_ALIGNED16(dy) && TB_ALIGNED16(dx),
-              PSG_ERR_UNSUPPORTED, "psg_train_bf16_layernorm_bwd: hidden=%d (a multiple of 8, 16-byte aligned rows)", hidden);
-  if (rows > 0) {
-    tb_layernorm_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, (const uint16_t*)dy, gamma, mean,
-                                                                                        rstd, rows, hidden, dx);
-    PSG_CHECK_LAUNCH("psg_train_bf16_layernorm_bwd");
-  }
+  PSG_REQUIRE(!dgamma == !dbeta, PSG_ERR_INVALID, "psg_train_bf16_layernorm_bwd: bad argument");
+  const int rc = tr_layernorm_bwd_launch<TrBf16>("psg_train_bf16_layernorm_bwd", ctx, x, dy, gamma, mean, rstd, rows, hidden, dx,
+                                                 nullptr, nullptr, stream);
+  if (rc != PSG_OK) return rc;
   if (dgamma) {                                              // written, not accumulated (zero rows: zeros)
     tb_layernorm_dgb_kernel<<<(unsigned)((hidden + 63) / 64), 1024, 0, (hipStream_t)stream>>>(x, (const uint16_t*)dy, mean,
                                                                                              rstd, rows, hidden, dgamma, dbeta);
@@ -200,218 +92,37 @@ extern "C" int psg_train_bf16_layernorm_bwd(psg_ctx* ctx, const float* x, const 
   return PSG_OK;
 }
 
-// ---- RMSNorm (weight frozen): x fp32 -> y bf16 -------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tb_rmsnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             float eps, int64_t rows, int hidden, uint16_t* __restrict__ y,
-                                                             float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float* xr = x + row * hidden;
-  float a[8], s = 0.f;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    tb_ld8f(xr + c, a);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += a[e] * a[e];
-  }
-  const float rs = 1.0f / sqrtf(wave_sum(s) / (float)hidden + eps);
-  for (int c = lane * 8; c < hidden; c += 512) {
-    float g[8], o[8];
-    tb_ld8f(xr + c, a);
-    tb_ld8f(w + c, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = g[e] * (a[e] * rs);
-    tb_st8(y + row * hidden + c, o);
-  }
-  if (lane == 0) rstd[row] = rs;
-}
-
-// y = w x r, r = (mean x^2 + eps)^-1/2:  dx = r (g - x r^2 mean(g x)), g = dy w
-__global__ void __launch_bounds__(256) tb_rmsnorm_bwd_kernel(const float* __restrict__ x, const uint16_t* __restrict__ dy,
-                                                             const float* __restrict__ w, const float* __restrict__ rstd,
-                                                             int64_t rows, int hidden, float* __restrict__ dx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float rs = rstd[row];
-  const float* xr = x + row * hidden;
-  const uint16_t* dr = dy + row * hidden;
-  float xa[8], d[8], g[8], a = 0.f;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    tb_ld8f(xr + c, xa);
-    tb_ld8(dr + c, d);
-    tb_ld8f(w + c, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a += d[e] * g[e] * xa[e];
-  }
-  a = wave_sum(a) / (float)hidden;
-  for (int c = lane * 8; c < hidden; c += 512) {
-    float o[8];
-    tb_ld8f(xr + c, xa);
-    tb_ld8(dr + c, d);
-    tb_ld8f(w + c, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = rs * (d[e] * g[e] - xa[e] * rs * rs * a);
-    tb_st8f(dx + row * hidden + c, o);
-  }
-}
-
 extern "C" int psg_train_bf16_rmsnorm_fwd(psg_ctx* ctx, const float* x, const float* w, float eps, int64_t rows, int hidden,
                                           void* y, float* rstd, void* stream) {
-  PSG_REQUIRE(ctx && x && w && y && rstd && hidden > 0 && rows >= 0, PSG_ERR_INVALID,
-              "psg_train_bf16_rmsnorm_fwd: bad argument");
-  PSG_REQUIRE(hidden % 8 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(w) && TB_ALIGNED16(y), PSG_ERR_UNSUPPORTED,
-              "psg_train_bf16_rmsnorm_fwd: hidden=%d (a multiple of 8, 16-byte aligned rows)", hidden);
-  if (rows == 0) return PSG_OK;
-  tb_rmsnorm_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, w, eps, rows, hidden, (uint16_t*)y,
-                                                                                    rstd);
-  PSG_CHECK_LAUNCH("psg_train_bf16_rmsnorm_fwd");
-  return PSG_OK;
+  return tr_rmsnorm_fwd_launch<TrBf16>("psg_train_bf16_rmsnorm_fwd", ctx, x, w, eps, rows, hidden, y, rstd, stream);
 }
 
 extern "C" int psg_train_bf16_rmsnorm_bwd(psg_ctx* ctx, const float* x, const void* dy, const float* w, const float* rstd,
                                           int64_t rows, int hidden, float* dx, void* stream) {
-  PSG_REQUIRE(ctx && x && dy && w && rstd && dx && hidden > 0 && rows >= 0, PSG_ERR_INVALID,
-              "psg_train_bf16_rmsnorm_bwd: bad argument");
-  PSG_REQUIRE(hidden % 8 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(w) && TB_ALIGNED16(dy) && TB_ALIGNED16(dx),
-              PSG_ERR_UNSUPPORTED, "psg_train_bf16_rmsnorm_bwd: hidden=%d (a multiple of 8, 16-byte aligned rows)", hidden);
-  if (rows == 0) return PSG_OK;
-  tb_rmsnorm_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, (const uint16_t*)dy, w, rstd, rows,
-                                                                                    hidden, dx);
-  PSG_CHECK_LAUNCH("psg_train_bf16_rmsnorm_bwd");
-  return PSG_OK;
+  return tr_rmsnorm_bwd_launch<TrBf16>("psg_train_bf16_rmsnorm_bwd", ctx, x, dy, w, rstd, rows, hidden, dx, stream);
 }
 
-// ---- element-wise: GELU, SwiGLU gate, rotary (8 bf16 per thread) -------------------------------------------------------
-__global__ void tb_gelu_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy, int64_t n8,
-                               uint16_t* __restrict__ o) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n8) return;
-  float v[8], d[8], r[8];
-  tb_ld8(x + i * 8, v);
-  if (dy) tb_ld8(dy + i * 8, d);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float cdf = 0.5f * (1.0f + erff(v[e] * 0.70710678118654752f));
-    r[e] = dy ? d[e] * (cdf + v[e] * 0.3989422804014327f * expf(-0.5f * v[e] * v[e])) : v[e] * cdf;
-  }
-  tb_st8(o + i * 8, r);
-}
-
-static int tb_gelu_launch(const char* name, psg_ctx* ctx, const void* x, const void* dy, bool bwd, int64_t n, void* o,
-                          void* stream) {
-  PSG_REQUIRE(ctx && x && o && (!bwd || dy) && n >= 0, PSG_ERR_INVALID, "%s: bad argument", name);
-  PSG_REQUIRE(n % 8 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(o) && TB_ALIGNED16(dy), PSG_ERR_UNSUPPORTED,
-              "%s: n=%lld (a multiple of 8, 16-byte aligned)", name, (long long)n);
-  if (n == 0) return PSG_OK;
-  tb_gelu_kernel<<<(unsigned)((n / 8 + 255) / 256), 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, (const uint16_t*)dy,
-                                                                                  n / 8, (uint16_t*)o);
-  PSG_CHECK_LAUNCH(name);
-  return PSG_OK;
-}
-
+// ---- element-wise: GELU, SwiGLU gate, rotary: bf16 in, bf16 out (psg_train_rows.h) -----------------------------------------
 extern "C" int psg_train_bf16_gelu_fwd(psg_ctx* ctx, const void* x, int64_t n, void* y, void* stream) {
-  return tb_gelu_launch("psg_train_bf16_gelu_fwd", ctx, x, nullptr, false, n, y, stream);
+  return tr_gelu_launch<TrBf16>("psg_train_bf16_gelu_fwd", ctx, x, nullptr, false, n, y, stream);
 }
 extern "C" int psg_train_bf16_gelu_bwd(psg_ctx* ctx, const void* x, const void* dy, int64_t n, void* dx, void* stream) {
-  return tb_gelu_launch("psg_train_bf16_gelu_bwd", ctx, x, dy, true, n, dx, stream);
-}
-
-// gu [rows][2 * inter] = gate | up; y = silu(gate) * up
-__global__ void tb_silu_mul_kernel(const uint16_t* __restrict__ gu, const uint16_t* __restrict__ dy, int64_t rows, int inter,
-                                   uint16_t* __restrict__ y, uint16_t* __restrict__ dgu) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int per = inter / 8;
-  if (i >= rows * per) return;
-  const int64_t r = i / per;
-  const int c = (int)(i % per) * 8;
-  float g[8], u[8], d[8], a[8], b[8];
-  tb_ld8(gu + r * 2 * inter + c, g);
-  tb_ld8(gu + r * 2 * inter + inter + c, u);
-  if (dy) tb_ld8(dy + r * inter + c, d);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float sg = 1.0f / (1.0f + expf(-g[e]));
-    if (!dy) {
-      a[e] = g[e] * sg * u[e];
-    } else {
-      a[e] = d[e] * u[e] * sg * (1.0f + g[e] * (1.0f - sg));
-      b[e] = d[e] * g[e] * sg;
-    }
-  }
-  if (!dy) {
-    tb_st8(y + r * inter + c, a);
-  } else {
-    tb_st8(dgu + r * 2 * inter + c, a);
-    tb_st8(dgu + r * 2 * inter + inter + c, b);
-  }
-}
-
-static int tb_silu_launch(const char* name, psg_ctx* ctx, const void* gu, const void* dy, bool bwd, int64_t rows, int inter,
-                          void* y, void* dgu, void* stream) {
-  PSG_REQUIRE(ctx && gu && (bwd ? (dy && dgu) : (y != nullptr)) && inter > 0 && rows >= 0, PSG_ERR_INVALID,
-              "%s: bad argument", name);
-  PSG_REQUIRE(inter % 8 == 0 && TB_ALIGNED16(gu) && TB_ALIGNED16(dy) && TB_ALIGNED16(y) && TB_ALIGNED16(dgu),
-              PSG_ERR_UNSUPPORTED, "%s: inter=%d (a multiple of 8, 16-byte aligned rows)", name, inter);
-  if (rows == 0) return PSG_OK;
-  const int64_t n = rows * (inter / 8);
-  tb_silu_mul_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>((const uint16_t*)gu, (const uint16_t*)dy,
-                                                                                  rows, inter, (uint16_t*)y, (uint16_t*)dgu);
-  PSG_CHECK_LAUNCH(name);
-  return PSG_OK;
+  return tr_gelu_launch<TrBf16>("psg_train_bf16_gelu_bwd", ctx, x, dy, true, n, dx, stream);
 }
 
 extern "C" int psg_train_bf16_silu_mul_fwd(psg_ctx* ctx, const void* gu, int64_t rows, int inter, void* y, void* stream) {
-  return tb_silu_launch("psg_train_bf16_silu_mul_fwd", ctx, gu, nullptr, false, rows, inter, y, nullptr, stream);
+  return tr_silu_mul_launch<TrBf16>("psg_train_bf16_silu_mul_fwd", ctx, gu, nullptr, false, rows, inter, y, nullptr, stream);
 }
 extern "C" int psg_train_bf16_silu_mul_bwd(psg_ctx* ctx, const void* gu, const void* dy, int64_t rows, int inter, void* dgu,
                                            void* stream) {
-  return tb_silu_launch("psg_train_bf16_silu_mul_bwd", ctx, gu, dy, true, rows, inter, nullptr, dgu, stream);
-}
-
-// x [rows][heads * head_dim] bf16, pos int32 [rows], cos / sin fp32 [table_rows][head_dim / 2]:
-// y = x cos + rotate_half(x) sin * sign (sign = -1: the adjoint).  A thread rotates 8 dims of the first half with their
-// partners in the second.
-__global__ void tb_rope_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ pos, const float* __restrict__ cs,
-                               const float* __restrict__ sn, int table_rows, int64_t rows, int heads, int head_dim,
-                               float sign, uint16_t* __restrict__ y) {
-  const int half = head_dim / 2, per = half / 8;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * heads * per) return;
-  const int d = (int)(i % per) * 8;
-  const int h = (int)((i / per) % heads);
-  const int64_t r = i / ((int64_t)per * heads);
-  const int64_t base = (r * heads + h) * head_dim;
-  int pr = pos[r];
-  pr = pr < 0 ? 0 : (pr >= table_rows ? table_rows - 1 : pr);   // never read outside the tables (RopeFn checks the range)
-  float c[8], s[8], a[8], b[8], oa[8], ob[8];
-  tb_ld8f(cs + (int64_t)pr * half + d, c);
-  tb_ld8f(sn + (int64_t)pr * half + d, s);
-  tb_ld8(x + base + d, a);
-  tb_ld8(x + base + d + half, b);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    oa[e] = a[e] * c[e] - b[e] * (s[e] * sign);                 // rotate_half(x) = [-x2, x1]
-    ob[e] = b[e] * c[e] + a[e] * (s[e] * sign);
-  }
-  tb_st8(y + base + d, oa);
-  tb_st8(y + base + d + half, ob);
+  return tr_silu_mul_launch<TrBf16>("psg_train_bf16_silu_mul_bwd", ctx, gu, dy, true, rows, inter, nullptr, dgu, stream);
 }
 
 extern "C" int psg_train_bf16_rope(psg_ctx* ctx, const void* x, const int32_t* pos, const float* rope_cos,
                                    const float* rope_sin, int table_rows, int64_t rows, int heads, int head_dim, float sign,
                                    void* y, void* stream) {
-  PSG_REQUIRE(ctx && x && pos && rope_cos && rope_sin && y && heads > 0 && head_dim > 0 && table_rows > 0 && rows >= 0,
-              PSG_ERR_INVALID, "psg_train_bf16_rope: bad argument");
-  PSG_REQUIRE(head_dim % 16 == 0 && TB_ALIGNED16(x) && TB_ALIGNED16(y) && TB_ALIGNED16(rope_cos) && TB_ALIGNED16(rope_sin),
-              PSG_ERR_UNSUPPORTED, "psg_train_bf16_rope: head_dim=%d (a multiple of 16, 16-byte aligned rows)", head_dim);
-  if (rows == 0) return PSG_OK;
-  const int64_t n = rows * heads * (head_dim / 16);
-  tb_rope_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, pos, rope_cos, rope_sin,
-                                                                              table_rows, rows, heads, head_dim, sign,
-                                                                              (uint16_t*)y);
-  PSG_CHECK_LAUNCH("psg_train_bf16_rope");
-  return PSG_OK;
+  return tr_rope_launch<TrBf16>("psg_train_bf16_rope", ctx, x, pos, rope_cos, rope_sin, table_rows, rows, heads, head_dim, sign,
+                                y, stream);
 }
 
 // ---- attention on the matrix cores ---------------------------------------------------------------------------------------

@@ -6,7 +6,9 @@
 // Training batches are tiny (<= 32 sampled pairs through the Q-Former, V4:29-30; <= 4 pairs through the LLM, V4:38),
 // so these are plain fp32 kernels - one wave per row or per (sequence, head, query row) - written for exactness against
 // autograd on the CPU oracle, not for speed; the dense projections and their weight gradients go through the library
-// GEMM.  Every kernel is the exact adjoint of the forward kernel next to it:
+// GEMM.  Every kernel is the exact adjoint of the forward kernel next to it.  The norms, GELU, the SwiGLU gate and rotary
+// are the templates of psg_train_rows.h with the TrF32 access policy (one float per access; the bf16 path of
+// psg_train_bf16.hip instantiates the same templates); the attention and the losses are written here:
 //
 //   psg_train_layernorm_fwd / _bwd     HF-IB LayerNorm (eps 1e-12): y = (x - mean) * rstd * gamma + beta
 //   psg_train_rmsnorm_fwd / _bwd       HF-LL:53-67 (weight frozen: no weight gradient)
@@ -20,133 +22,32 @@
 //   psg_train_rope                     half-split rotary (HF-LL:130-160); sign = -1 is its adjoint
 //   psg_train_ce_bwd / psg_train_bce_bwd   gradients of psg_cross_entropy_rows / psg_bce_with_logits
 //   psg_train_mlcce_fwd / _bwd         multilabel categorical cross entropy of the multiclass head (V4:484-495)
-#include "psg_common.h"
+#include "psg_train_rows.h"
 
 #define TR_FMIN (-3.4028234663852886e38f)
 
-// ---- LayerNorm ----------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tr_layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float eps, int64_t rows,
-                                                               int hidden, float* __restrict__ y, float* __restrict__ mean,
-                                                               float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float* xr = x + row * hidden;
-  float s = 0.f;
-  for (int c = lane; c < hidden; c += 64) s += xr[c];
-  const float mu = wave_sum(s) / (float)hidden;
-  float v = 0.f;
-  for (int c = lane; c < hidden; c += 64) {
-    const float d = xr[c] - mu;
-    v += d * d;
-  }
-  const float rs = 1.0f / sqrtf(wave_sum(v) / (float)hidden + eps);
-  for (int c = lane; c < hidden; c += 64) y[row * hidden + c] = (xr[c] - mu) * rs * gamma[c] + beta[c];
-  if (lane == 0) {
-    mean[row] = mu;
-    rstd[row] = rs;
-  }
-}
-
-// dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma; dgamma += dy * xhat, dbeta += dy (atomics)
-__global__ void __launch_bounds__(256) tr_layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                               const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, int64_t rows, int hidden,
-                                                               float* __restrict__ dx, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float mu = mean[row], rs = rstd[row];
-  const float* xr = x + row * hidden;
-  const float* dr = dy + row * hidden;
-  float a = 0.f, b = 0.f;
-  for (int c = lane; c < hidden; c += 64) {
-    const float g = dr[c] * gamma[c], xh = (xr[c] - mu) * rs;
-    a += g;
-    b += g * xh;
-  }
-  a = wave_sum(a) / (float)hidden;
-  b = wave_sum(b) / (float)hidden;
-  for (int c = lane; c < hidden; c += 64) {
-    const float xh = (xr[c] - mu) * rs;
-    dx[row * hidden + c] = rs * (dr[c] * gamma[c] - a - xh * b);
-    if (dgamma) atomicAdd(dgamma + c, dr[c] * xh);
-    if (dbeta) atomicAdd(dbeta + c, dr[c]);
-  }
-}
-
+// ---- LayerNorm, RMSNorm (psg_train_rows.h at one float per access) ------------------------------------------------------
+// dgamma / dbeta (each may be NULL) are accumulated by atomics: the caller hands them in zeroed
 extern "C" int psg_train_layernorm_fwd(psg_ctx* ctx, const float* x, const float* gamma, const float* beta, float eps,
                                        int64_t rows, int hidden, float* y, float* mean, float* rstd, void* stream) {
-  PSG_REQUIRE(ctx && x && gamma && beta && y && mean && rstd && hidden > 0, PSG_ERR_INVALID,
-              "psg_train_layernorm_fwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_layernorm_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, gamma, beta, eps, rows, hidden, y,
-                                                                                      mean, rstd);
-  PSG_CHECK_LAUNCH("psg_train_layernorm_fwd");
-  return PSG_OK;
+  return tr_layernorm_fwd_launch<TrF32>("psg_train_layernorm_fwd", ctx, x, gamma, beta, eps, rows, hidden, y, mean, rstd, stream);
 }
 
 extern "C" int psg_train_layernorm_bwd(psg_ctx* ctx, const float* x, const float* dy, const float* gamma, const float* mean,
                                        const float* rstd, int64_t rows, int hidden, float* dx, float* dgamma, float* dbeta,
                                        void* stream) {
-  PSG_REQUIRE(ctx && x && dy && gamma && mean && rstd && dx && hidden > 0, PSG_ERR_INVALID,
-              "psg_train_layernorm_bwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_layernorm_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, dy, gamma, mean, rstd, rows, hidden,
-                                                                                      dx, dgamma, dbeta);
-  PSG_CHECK_LAUNCH("psg_train_layernorm_bwd");
-  return PSG_OK;
-}
-
-// ---- RMSNorm (weight frozen) ----------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tr_rmsnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             float eps, int64_t rows, int hidden, float* __restrict__ y,
-                                                             float* __restrict__ rstd) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float* xr = x + row * hidden;
-  float s = 0.f;
-  for (int c = lane; c < hidden; c += 64) s += xr[c] * xr[c];
-  const float rs = 1.0f / sqrtf(wave_sum(s) / (float)hidden + eps);
-  for (int c = lane; c < hidden; c += 64) y[row * hidden + c] = w[c] * (xr[c] * rs);
-  if (lane == 0) rstd[row] = rs;
-}
-
-// y = w x r, r = (mean x^2 + eps)^-1/2:  dx = r (g - x r^2 mean(g x)), g = dy w
-__global__ void __launch_bounds__(256) tr_rmsnorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                             const float* __restrict__ w, const float* __restrict__ rstd,
-                                                             int64_t rows, int hidden, float* __restrict__ dx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= rows) return;
-  const float rs = rstd[row];
-  const float* xr = x + row * hidden;
-  const float* dr = dy + row * hidden;
-  float a = 0.f;
-  for (int c = lane; c < hidden; c += 64) a += dr[c] * w[c] * xr[c];
-  a = wave_sum(a) / (float)hidden;
-  for (int c = lane; c < hidden; c += 64) dx[row * hidden + c] = rs * (dr[c] * w[c] - xr[c] * rs * rs * a);
+  return tr_layernorm_bwd_launch<TrF32>("psg_train_layernorm_bwd", ctx, x, dy, gamma, mean, rstd, rows, hidden, dx, dgamma,
+                                        dbeta, stream);
 }
 
 extern "C" int psg_train_rmsnorm_fwd(psg_ctx* ctx, const float* x, const float* w, float eps, int64_t rows, int hidden,
                                      float* y, float* rstd, void* stream) {
-  PSG_REQUIRE(ctx && x && w && y && rstd && hidden > 0, PSG_ERR_INVALID, "psg_train_rmsnorm_fwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_rmsnorm_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, w, eps, rows, hidden, y, rstd);
-  PSG_CHECK_LAUNCH("psg_train_rmsnorm_fwd");
-  return PSG_OK;
+  return tr_rmsnorm_fwd_launch<TrF32>("psg_train_rmsnorm_fwd", ctx, x, w, eps, rows, hidden, y, rstd, stream);
 }
 
 extern "C" int psg_train_rmsnorm_bwd(psg_ctx* ctx, const float* x, const float* dy, const float* w, const float* rstd,
                                      int64_t rows, int hidden, float* dx, void* stream) {
-  PSG_REQUIRE(ctx && x && dy && w && rstd && dx && hidden > 0, PSG_ERR_INVALID, "psg_train_rmsnorm_bwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_rmsnorm_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, dy, w, rstd, rows, hidden, dx);
-  PSG_CHECK_LAUNCH("psg_train_rmsnorm_bwd");
-  return PSG_OK;
+  return tr_rmsnorm_bwd_launch<TrF32>("psg_train_rmsnorm_bwd", ctx, x, dy, w, rstd, rows, hidden, dx, stream);
 }
 
 // ---- attention -------------------------------------------------------------------------------------------------------
@@ -300,100 +201,26 @@ extern "C" int psg_train_attn_bwd(psg_ctx* ctx, const float* q, const float* k, 
   return PSG_OK;
 }
 
-// ---- element-wise: GELU, SwiGLU gate, rotary ---------------------------------------------------------------------------
-__global__ void tr_gelu_kernel(const float* __restrict__ x, const float* __restrict__ dy, int64_t n, float* __restrict__ o) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float v = x[i];
-  const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
-  if (dy) o[i] = dy[i] * (cdf + v * 0.3989422804014327f * expf(-0.5f * v * v));   // d/dx [x Phi(x)] = Phi + x phi
-  else o[i] = v * cdf;
-}
-
+// ---- element-wise: GELU, SwiGLU gate, rotary (psg_train_rows.h) ----------------------------------------------------------
 extern "C" int psg_train_gelu_fwd(psg_ctx* ctx, const float* x, int64_t n, float* y, void* stream) {
-  PSG_REQUIRE(ctx && x && y && n >= 0, PSG_ERR_INVALID, "psg_train_gelu_fwd: bad argument");
-  if (n == 0) return PSG_OK;
-  tr_gelu_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, nullptr, n, y);
-  PSG_CHECK_LAUNCH("psg_train_gelu_fwd");
-  return PSG_OK;
+  return tr_gelu_launch<TrF32>("psg_train_gelu_fwd", ctx, x, nullptr, false, n, y, stream);
 }
-
 extern "C" int psg_train_gelu_bwd(psg_ctx* ctx, const float* x, const float* dy, int64_t n, float* dx, void* stream) {
-  PSG_REQUIRE(ctx && x && dy && dx && n >= 0, PSG_ERR_INVALID, "psg_train_gelu_bwd: bad argument");
-  if (n == 0) return PSG_OK;
-  tr_gelu_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, dy, n, dx);
-  PSG_CHECK_LAUNCH("psg_train_gelu_bwd");
-  return PSG_OK;
-}
-
-// gu [rows][2 * inter] = gate | up; y = silu(gate) * up
-__global__ void tr_silu_mul_kernel(const float* __restrict__ gu, const float* __restrict__ dy, int64_t rows, int inter,
-                                   float* __restrict__ y, float* __restrict__ dgu) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * inter) return;
-  const int64_t r = i / inter;
-  const int c = (int)(i % inter);
-  const float g = gu[r * 2 * inter + c], u = gu[r * 2 * inter + inter + c];
-  const float sg = 1.0f / (1.0f + expf(-g));
-  if (!dy) {
-    y[i] = g * sg * u;
-  } else {
-    const float d = dy[i];
-    dgu[r * 2 * inter + c] = d * u * sg * (1.0f + g * (1.0f - sg));
-    dgu[r * 2 * inter + inter + c] = d * g * sg;
-  }
+  return tr_gelu_launch<TrF32>("psg_train_gelu_bwd", ctx, x, dy, true, n, dx, stream);
 }
 
 extern "C" int psg_train_silu_mul_fwd(psg_ctx* ctx, const float* gu, int64_t rows, int inter, float* y, void* stream) {
-  PSG_REQUIRE(ctx && gu && y && inter > 0, PSG_ERR_INVALID, "psg_train_silu_mul_fwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_silu_mul_kernel<<<(unsigned)((rows * inter + 255) / 256), 256, 0, (hipStream_t)stream>>>(gu, nullptr, rows, inter, y,
-                                                                                           nullptr);
-  PSG_CHECK_LAUNCH("psg_train_silu_mul_fwd");
-  return PSG_OK;
+  return tr_silu_mul_launch<TrF32>("psg_train_silu_mul_fwd", ctx, gu, nullptr, false, rows, inter, y, nullptr, stream);
 }
-
 extern "C" int psg_train_silu_mul_bwd(psg_ctx* ctx, const float* gu, const float* dy, int64_t rows, int inter, float* dgu,
                                       void* stream) {
-  PSG_REQUIRE(ctx && gu && dy && dgu && inter > 0, PSG_ERR_INVALID, "psg_train_silu_mul_bwd: bad argument");
-  if (rows == 0) return PSG_OK;
-  tr_silu_mul_kernel<<<(unsigned)((rows * inter + 255) / 256), 256, 0, (hipStream_t)stream>>>(gu, dy, rows, inter, nullptr,
-                                                                                           dgu);
-  PSG_CHECK_LAUNCH("psg_train_silu_mul_bwd");
-  return PSG_OK;
-}
-
-// x [rows][heads * head_dim], pos int32 [rows] (row of the cos / sin tables [table_rows][head_dim / 2]):
-// y = x cos + rotate_half(x) sin * sign.  sign = +1: HF-LL:130-160; sign = -1: its adjoint (the rotation by -angle).
-__global__ void tr_rope_kernel(const float* __restrict__ x, const int32_t* __restrict__ pos, const float* __restrict__ cs,
-                               const float* __restrict__ sn, int table_rows, int64_t rows, int heads, int head_dim,
-                               float sign, float* __restrict__ y) {
-  const int half = head_dim / 2;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * heads * half) return;
-  const int d = (int)(i % half);
-  const int h = (int)((i / half) % heads);
-  const int64_t r = i / ((int64_t)half * heads);
-  const int64_t base = (r * heads + h) * head_dim;
-  int pr = pos[r];
-  pr = pr < 0 ? 0 : (pr >= table_rows ? table_rows - 1 : pr);  // never read outside the tables (RopeFn checks the range)
-  const float c = cs[(int64_t)pr * half + d], s = sn[(int64_t)pr * half + d] * sign;
-  const float a = x[base + d], b = x[base + d + half];
-  y[base + d] = a * c - b * s;                               // rotate_half(x) = [-x2, x1]
-  y[base + d + half] = b * c + a * s;
+  return tr_silu_mul_launch<TrF32>("psg_train_silu_mul_bwd", ctx, gu, dy, true, rows, inter, nullptr, dgu, stream);
 }
 
 extern "C" int psg_train_rope(psg_ctx* ctx, const float* x, const int32_t* pos, const float* rope_cos, const float* rope_sin,
                               int table_rows, int64_t rows, int heads, int head_dim, float sign, float* y, void* stream) {
-  PSG_REQUIRE(ctx && x && pos && rope_cos && rope_sin && y && heads > 0 && head_dim > 0 && head_dim % 2 == 0 &&
-                  table_rows > 0,
-              PSG_ERR_INVALID, "psg_train_rope: bad argument");
-  if (rows == 0) return PSG_OK;
-  const int64_t n = rows * heads * (head_dim / 2);
-  tr_rope_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, pos, rope_cos, rope_sin, table_rows,
-                                                                             rows, heads, head_dim, sign, y);
-  PSG_CHECK_LAUNCH("psg_train_rope");
-  return PSG_OK;
+  return tr_rope_launch<TrF32>("psg_train_rope", ctx, x, pos, rope_cos, rope_sin, table_rows, rows, heads, head_dim, sign, y,
+                               stream);
 }
 
 // ---- loss gradients ---------------------------------------------------------------------------------------------------

@@ -877,10 +877,12 @@ class RelationTransformerHeadV4(nn.Module):
     def forward_train_grad(self, inputs, sampled=None, selected=None, dropout=None):
         """The training branch WITH its gradient graph (V4:327-351, 463-482; tools/train.py:239-246 back-propagates the
         sum of the two losses): the same arithmetic through `openpsg_amd/train_graph.py` - torch.autograd nodes whose
-        forward / backward are the fp32 kernels of csrc/psg_train_bwd.hip, library GEMMs for the projections.  Gradients
+        forward / backward are the fp32 kernels of csrc/psg_train_bwd.hip (its norms, GELU, gate and rotary: the templates
+        of csrc/psg_train_rows.h), library GEMMs for the projections.  Gradients
         reach patch_embed, the Q-Former, relation_query / rel_cls_query, binary_rel_cls_pred and language_projection;
         the LLM is frozen (CFG:65) and only passes the gradient through.  fp32 heads - or, with train_precision='bf16', a
-        head of any dtype: the graph then runs on csrc/psg_train_bf16.hip in the bf16 model of DESIGN 13 (bf16 activations
+        head of any dtype: the same nodes then call the bf16 entry points of csrc/psg_train_bf16.hip (the same templates
+        at 16-byte accesses, the attention on the matrix cores) in the bf16 model of DESIGN 13 (bf16 activations
         and products, fp32 residual streams / statistics / losses, fp32 gradients on the fp32 masters).
         dropout: None = `train_dropout` (on by default: the reference trains its Q-Former with HF's default dropouts
         active, V4:78-84); False = off (what the oracle and the goldens are captured with); or a train_graph.Dropout."""

@@ -7,14 +7,17 @@ The graph is torch.autograd's; its nodes are
   * the dense projections (`F.linear`, library GEMM; their weight gradients too), and
   * `torch.autograd.Function`s whose forward and backward are the fp32 kernels of csrc/psg_train_bwd.hip: LayerNorm,
     RMSNorm, the three attentions (Q-Former self / cross with the pair masks, Llama causal), GELU, the SwiGLU gate,
-    rotary, cross entropy and BCE-with-logits.
+    rotary, cross entropy and BCE-with-logits.  The norms, GELU, the gate and rotary are the kernel templates of
+    csrc/psg_train_rows.h, which both precisions instantiate.
 Training batches are tiny (<= 32 sampled pairs, <= 4 LLM pairs, V4:29-30, 38), so this path is written for exactness
 against autograd on the CPU oracle (tests/test_gpu_train.py), not for speed.  No CPU path.
 
 precision='bf16' (the head's train_precision) runs the same graph in the model torch.autocast(bfloat16) gives
-the reference: the `*Bf16Fn` nodes below are the kernels of csrc/psg_train_bf16.hip (bf16 activations, fp32 residual
-streams and statistics, the attention on the matrix cores), `LinearBf16Fn` is a bf16 library GEMM whose weight gradient
-leaves its fp32 accumulator as fp32 onto the fp32 master.  `PatchEmbedFn`, the losses and the sampler are shared.
+the reference (bf16 activations, fp32 residual streams and statistics).  `LayerNormFn`, `RMSNormFn`, `GeluFn`, `SiluMulFn`
+and `RopeFn` take the precision as their last argument and call the same templates through the psg_train_bf16_* entry
+points of csrc/psg_train_bf16.hip (`_Family`); `AttnBf16Fn` is that file's attention on the matrix cores, `LinearBf16Fn`
+a bf16 library GEMM whose weight gradient leaves its fp32 accumulator as fp32 onto the fp32 master.  `PatchEmbedFn`, the
+losses and the sampler are shared.
 """
 from __future__ import annotations
 
@@ -29,68 +32,103 @@ def _env(t):
     return ops._env(t)
 
 
+BF16 = torch.bfloat16
+
+
 def _f32(t, name="tensor"):
     if t.dtype != torch.float32 or not t.is_cuda:
         raise PsgHipError(f"{name}: the gradient path runs in fp32 on the GPU (got {t.dtype} on {t.device})")
     return t.contiguous()
 
 
+def _b16(t, name="tensor"):
+    if t.dtype != BF16 or not t.is_cuda:
+        raise PsgHipError(f"{name}: the bf16 gradient path takes bf16 activations on the GPU (got {t.dtype} on {t.device})")
+    return t.contiguous()
+
+
+class _Family:
+    """What a row / pointwise node needs to know of its precision: the entry points' prefix (csrc/psg_train_bwd.hip |
+    csrc/psg_train_bf16.hip, both instantiating csrc/psg_train_rows.h), the activations' dtype with its check, and how
+    LayerNorm's dgamma / dbeta arrive: accumulated by atomics into zeros (fp32) or written (bf16: no memset).  The
+    residual streams the norms read are fp32 in both."""
+
+    def __init__(self, prefix, dtype, act, dgb):
+        self.prefix, self.dtype, self.act, self.dgb = prefix, dtype, act, dgb
+
+    def call(self, op, t, *args):
+        lib, c, st = _env(t)
+        check(getattr(lib, self.prefix + op)(c, *args, st), self.prefix + op)
+
+
+_FAMILIES = {None: _Family("psg_train_", torch.float32, _f32, torch.zeros_like),
+             "bf16": _Family("psg_train_bf16_", BF16, _b16, torch.empty_like)}
+
+
+def _family(precision):
+    if precision not in (None, "bf16"):
+        raise PsgHipError(f"precision must be None or 'bf16', got {precision!r}")
+    return _FAMILIES[precision]
+
+
 class LayerNormFn(torch.autograd.Function):
+    """x fp32 (the residual stream under 'bf16') -> y in the precision's activation dtype; gamma / beta fp32 (masters);
+    dx, dgamma, dbeta fp32."""
+
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
+    def forward(ctx, x, gamma, beta, eps, precision=None):
+        f = _family(precision)
         x, gamma, beta = _f32(x, "layernorm x"), _f32(gamma), _f32(beta)
         hidden = x.shape[-1]
         rows = x.numel() // hidden
-        y = torch.empty_like(x)
+        y = torch.empty(x.shape, device=x.device, dtype=f.dtype)
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
-        lib, c, st = _env(x)
-        check(lib.psg_train_layernorm_fwd(c, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), rows, hidden,
-                                          y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), st), "psg_train_layernorm_fwd")
+        f.call("layernorm_fwd", x, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), rows, hidden, y.data_ptr(),
+               mean.data_ptr(), rstd.data_ptr())
         ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.family = f
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
-        dy = _f32(dy)
+        f = ctx.family
+        dy = f.act(dy)
         hidden = x.shape[-1]
-        rows = x.numel() // hidden
         dx = torch.empty_like(x)
-        dg, db = torch.zeros_like(gamma), torch.zeros_like(gamma)
-        lib, c, st = _env(x)
-        check(lib.psg_train_layernorm_bwd(c, x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                          rows, hidden, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), st),
-              "psg_train_layernorm_bwd")
-        return dx, dg, db, None
+        dg, db = f.dgb(gamma), f.dgb(gamma)
+        f.call("layernorm_bwd", x, x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+               x.numel() // hidden, hidden, dx.data_ptr(), dg.data_ptr(), db.data_ptr())
+        return dx, dg, db, None, None
 
 
 class RMSNormFn(torch.autograd.Function):
-    """HF-LL:53-67 with a FROZEN weight (no weight gradient)."""
+    """HF-LL:53-67 with a FROZEN fp32 weight (no weight gradient); x fp32 (the Llama residual stream under 'bf16') -> y in
+    the precision's activation dtype; dx fp32."""
 
     @staticmethod
-    def forward(ctx, x, w, eps):
+    def forward(ctx, x, w, eps, precision=None):
+        f = _family(precision)
         x, w = _f32(x, "rmsnorm x"), _f32(w)
         hidden = x.shape[-1]
         rows = x.numel() // hidden
-        y = torch.empty_like(x)
+        y = torch.empty(x.shape, device=x.device, dtype=f.dtype)
         rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-        lib, c, st = _env(x)
-        check(lib.psg_train_rmsnorm_fwd(c, x.data_ptr(), w.data_ptr(), float(eps), rows, hidden, y.data_ptr(),
-                                        rstd.data_ptr(), st), "psg_train_rmsnorm_fwd")
+        f.call("rmsnorm_fwd", x, x.data_ptr(), w.data_ptr(), float(eps), rows, hidden, y.data_ptr(), rstd.data_ptr())
         ctx.save_for_backward(x, w, rstd)
+        ctx.family = f
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, rstd = ctx.saved_tensors
-        dy = _f32(dy)
+        dy = ctx.family.act(dy)
         hidden = x.shape[-1]
         dx = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_rmsnorm_bwd(c, x.data_ptr(), dy.data_ptr(), w.data_ptr(), rstd.data_ptr(), x.numel() // hidden,
-                                        hidden, dx.data_ptr(), st), "psg_train_rmsnorm_bwd")
-        return dx, None, None
+        ctx.family.call("rmsnorm_bwd", x, x.data_ptr(), dy.data_ptr(), w.data_ptr(), rstd.data_ptr(), x.numel() // hidden,
+                        hidden, dx.data_ptr())
+        return dx, None, None, None
 
 
 class AttnFn(torch.autograd.Function):
@@ -137,73 +175,73 @@ class AttnFn(torch.autograd.Function):
 
 class GeluFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
-        x = _f32(x, "gelu x")
+    def forward(ctx, x, precision=None):
+        f = _family(precision)
+        x = f.act(x, "gelu x")
         y = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_gelu_fwd(c, x.data_ptr(), x.numel(), y.data_ptr(), st), "psg_train_gelu_fwd")
+        f.call("gelu_fwd", x, x.data_ptr(), x.numel(), y.data_ptr())
         ctx.save_for_backward(x)
+        ctx.family = f
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, = ctx.saved_tensors
-        dy = _f32(dy)
+        dy = ctx.family.act(dy)
         dx = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_gelu_bwd(c, x.data_ptr(), dy.data_ptr(), x.numel(), dx.data_ptr(), st), "psg_train_gelu_bwd")
-        return dx
+        ctx.family.call("gelu_bwd", x, x.data_ptr(), dy.data_ptr(), x.numel(), dx.data_ptr())
+        return dx, None
 
 
 class SiluMulFn(torch.autograd.Function):
     """gate_up [rows, 2*inter] -> silu(gate) * up [rows, inter] (HF-LL:163-177)."""
 
     @staticmethod
-    def forward(ctx, gu):
-        gu = _f32(gu, "gate_up")
+    def forward(ctx, gu, precision=None):
+        f = _family(precision)
+        gu = f.act(gu, "gate_up")
         rows, two = gu.shape
-        y = torch.empty((rows, two // 2), device=gu.device, dtype=torch.float32)
-        lib, c, st = _env(gu)
-        check(lib.psg_train_silu_mul_fwd(c, gu.data_ptr(), rows, two // 2, y.data_ptr(), st), "psg_train_silu_mul_fwd")
+        y = torch.empty((rows, two // 2), device=gu.device, dtype=f.dtype)
+        f.call("silu_mul_fwd", gu, gu.data_ptr(), rows, two // 2, y.data_ptr())
         ctx.save_for_backward(gu)
+        ctx.family = f
         return y
 
     @staticmethod
     def backward(ctx, dy):
         gu, = ctx.saved_tensors
-        dy = _f32(dy)
+        dy = ctx.family.act(dy)
         d = torch.empty_like(gu)
-        lib, c, st = _env(gu)
-        check(lib.psg_train_silu_mul_bwd(c, gu.data_ptr(), dy.data_ptr(), gu.shape[0], gu.shape[1] // 2, d.data_ptr(), st),
-              "psg_train_silu_mul_bwd")
-        return d
+        ctx.family.call("silu_mul_bwd", gu, gu.data_ptr(), dy.data_ptr(), gu.shape[0], gu.shape[1] // 2, d.data_ptr())
+        return d, None
 
 
 class RopeFn(torch.autograd.Function):
     """Half-split rotary (HF-LL:130-160) on x [rows, heads*head_dim] at table rows `pos` (int32 [rows])."""
 
     @staticmethod
-    def forward(ctx, x, pos, cos, sin, heads):
-        x = _f32(x, "rope x")
+    def forward(ctx, x, pos, cos, sin, heads, precision=None):
+        f = _family(precision)
+        x = f.act(x, "rope x")
         if pos.numel() and (int(pos.max()) >= cos.shape[0] or int(pos.min()) < 0):      # training only: one read-back
             raise PsgHipError(f"rope: position {int(pos.max())} outside the {cos.shape[0]}-row rotary table")
         ctx.save_for_backward(pos, cos, sin)
-        ctx.heads = heads
-        return RopeFn._run(x, pos, cos, sin, heads, 1.0)
+        ctx.heads, ctx.family = heads, f
+        return RopeFn._run(f, x, pos, cos, sin, heads, 1.0)
 
     @staticmethod
-    def _run(x, pos, cos, sin, heads, sign):
+    def _run(f, x, pos, cos, sin, heads, sign):
         rows, hid = x.shape
         y = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_rope(c, x.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], rows, heads,
-                                 hid // heads, float(sign), y.data_ptr(), st), "psg_train_rope")
+        f.call("rope", x, x.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], rows, heads, hid // heads,
+               float(sign), y.data_ptr())
         return y
 
     @staticmethod
     def backward(ctx, dy):
         pos, cos, sin = ctx.saved_tensors
-        return RopeFn._run(_f32(dy), pos, cos, sin, ctx.heads, -1.0), None, None, None, None
+        f = ctx.family
+        return RopeFn._run(f, f.act(dy), pos, cos, sin, ctx.heads, -1.0), None, None, None, None, None
 
 
 class CrossEntropyRowsFn(torch.autograd.Function):
@@ -295,15 +333,6 @@ class PatchEmbedFn(torch.autograd.Function):
 
 
 # ---- precision='bf16'  -----------------------------------------------------------------------------------------
-BF16 = torch.bfloat16
-
-
-def _b16(t, name="tensor"):
-    if t.dtype != BF16 or not t.is_cuda:
-        raise PsgHipError(f"{name}: the bf16 gradient path takes bf16 activations on the GPU (got {t.dtype} on {t.device})")
-    return t.contiguous()
-
-
 class LinearBf16Fn(torch.autograd.Function):
     """x bf16 . W^T (+ b) with W, b the fp32 MASTERS: both operands bf16, fp32 accumulation, bf16 output; backward:
     dx bf16, dW = dy^T x written from the fp32 accumulator as fp32, db summed in fp32."""
@@ -324,66 +353,6 @@ class LinearBf16Fn(torch.autograd.Function):
         dw = torch.mm(dy2.t(), x.reshape(-1, x.shape[-1]), out_dtype=torch.float32) if ctx.needs_input_grad[1] else None
         db = dy2.sum(0, dtype=torch.float32) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db
-
-
-class LayerNormBf16Fn(torch.autograd.Function):
-    """x fp32 (the residual stream) -> y bf16; gamma / beta fp32 masters; dx, dgamma, dbeta fp32."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        x, gamma, beta = _f32(x, "layernorm x"), _f32(gamma), _f32(beta)
-        hidden = x.shape[-1]
-        rows = x.numel() // hidden
-        y = torch.empty(x.shape, device=x.device, dtype=BF16)
-        mean = torch.empty(rows, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_layernorm_fwd(c, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), rows, hidden,
-                                               y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), st),
-              "psg_train_bf16_layernorm_fwd")
-        ctx.save_for_backward(x, gamma, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, mean, rstd = ctx.saved_tensors
-        dy = _b16(dy)
-        hidden = x.shape[-1]
-        dx = torch.empty_like(x)
-        dg, db = torch.empty_like(gamma), torch.empty_like(gamma)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_layernorm_bwd(c, x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                                               rstd.data_ptr(), x.numel() // hidden, hidden, dx.data_ptr(), dg.data_ptr(),
-                                               db.data_ptr(), st), "psg_train_bf16_layernorm_bwd")
-        return dx, dg, db, None
-
-
-class RMSNormBf16Fn(torch.autograd.Function):
-    """x fp32 (the Llama residual stream) -> y bf16, FROZEN fp32 weight; dx fp32."""
-
-    @staticmethod
-    def forward(ctx, x, w, eps):
-        x, w = _f32(x, "rmsnorm x"), _f32(w)
-        hidden = x.shape[-1]
-        rows = x.numel() // hidden
-        y = torch.empty(x.shape, device=x.device, dtype=BF16)
-        rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_rmsnorm_fwd(c, x.data_ptr(), w.data_ptr(), float(eps), rows, hidden, y.data_ptr(),
-                                             rstd.data_ptr(), st), "psg_train_bf16_rmsnorm_fwd")
-        ctx.save_for_backward(x, w, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, rstd = ctx.saved_tensors
-        dy = _b16(dy)
-        hidden = x.shape[-1]
-        dx = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_rmsnorm_bwd(c, x.data_ptr(), dy.data_ptr(), w.data_ptr(), rstd.data_ptr(),
-                                             x.numel() // hidden, hidden, dx.data_ptr(), st), "psg_train_bf16_rmsnorm_bwd")
-        return dx, None, None
 
 
 class AttnBf16Fn(torch.autograd.Function):
@@ -426,87 +395,16 @@ class AttnBf16Fn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
-class GeluBf16Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        x = _b16(x, "gelu x")
-        y = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_gelu_fwd(c, x.data_ptr(), x.numel(), y.data_ptr(), st), "psg_train_bf16_gelu_fwd")
-        ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, = ctx.saved_tensors
-        dy = _b16(dy)
-        dx = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_gelu_bwd(c, x.data_ptr(), dy.data_ptr(), x.numel(), dx.data_ptr(), st),
-              "psg_train_bf16_gelu_bwd")
-        return dx
-
-
-class SiluMulBf16Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, gu):
-        gu = _b16(gu, "gate_up")
-        rows, two = gu.shape
-        y = torch.empty((rows, two // 2), device=gu.device, dtype=BF16)
-        lib, c, st = _env(gu)
-        check(lib.psg_train_bf16_silu_mul_fwd(c, gu.data_ptr(), rows, two // 2, y.data_ptr(), st),
-              "psg_train_bf16_silu_mul_fwd")
-        ctx.save_for_backward(gu)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        gu, = ctx.saved_tensors
-        dy = _b16(dy)
-        d = torch.empty_like(gu)
-        lib, c, st = _env(gu)
-        check(lib.psg_train_bf16_silu_mul_bwd(c, gu.data_ptr(), dy.data_ptr(), gu.shape[0], gu.shape[1] // 2, d.data_ptr(),
-                                              st), "psg_train_bf16_silu_mul_bwd")
-        return d
-
-
-class RopeBf16Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, pos, cos, sin, heads):
-        x = _b16(x, "rope x")
-        if pos.numel() and (int(pos.max()) >= cos.shape[0] or int(pos.min()) < 0):      # training only: one read-back
-            raise PsgHipError(f"rope: position {int(pos.max())} outside the {cos.shape[0]}-row rotary table")
-        ctx.save_for_backward(pos, cos, sin)
-        ctx.heads = heads
-        return RopeBf16Fn._run(x, pos, cos, sin, heads, 1.0)
-
-    @staticmethod
-    def _run(x, pos, cos, sin, heads, sign):
-        rows, hid = x.shape
-        y = torch.empty_like(x)
-        lib, c, st = _env(x)
-        check(lib.psg_train_bf16_rope(c, x.data_ptr(), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), cos.shape[0], rows,
-                                      heads, hid // heads, float(sign), y.data_ptr(), st), "psg_train_bf16_rope")
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        pos, cos, sin = ctx.saved_tensors
-        return RopeBf16Fn._run(_b16(dy), pos, cos, sin, ctx.heads, -1.0), None, None, None, None
-
-
 class _Nodes:
     """The graph's nodes for one precision: `qformer_pairs` / `llama_teacher_forcing` are written once over them.
     resid(a, b): the sum a LayerNorm / the Llama stream takes - fp32 in both precisions."""
 
     def __init__(self, precision):
-        if precision not in (None, "bf16"):
-            raise PsgHipError(f"precision must be None or 'bf16', got {precision!r}")
-        b = precision == "bf16"
+        b = _family(precision).dtype == BF16
         self.bf16 = b
-        self.ln, self.rms = (LayerNormBf16Fn if b else LayerNormFn).apply, (RMSNormBf16Fn if b else RMSNormFn).apply
-        self.attn, self.gelu = (AttnBf16Fn if b else AttnFn).apply, (GeluBf16Fn if b else GeluFn).apply
-        self.silu, self.rope = (SiluMulBf16Fn if b else SiluMulFn).apply, (RopeBf16Fn if b else RopeFn).apply
+        bind = lambda fn: (lambda *a: fn.apply(*a, precision))                                   # noqa: E731
+        self.ln, self.rms, self.gelu, self.silu, self.rope = map(bind, (LayerNormFn, RMSNormFn, GeluFn, SiluMulFn, RopeFn))
+        self.attn = (AttnBf16Fn if b else AttnFn).apply
         self.linear = LinearBf16Fn.apply if b else F.linear
         self.act = (lambda t: t.to(BF16)) if b else (lambda t: t)
         self.resid = (lambda a, r: a.float() + r.float()) if b else (lambda a, r: a + r)

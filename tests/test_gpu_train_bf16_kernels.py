@@ -185,6 +185,35 @@ def test_gelu_silu_rope():
     assert lib.psg_train_bf16_gelu_fwd(c, x.data_ptr(), 12, y.data_ptr(), st) == PSG_ERR_UNSUPPORTED
 
 
+def test_pointwise_bf16_nodes_are_the_fp32_nodes_rounded_once():
+    """Both precisions instantiate one kernel template (csrc/psg_train_rows.h), so on bf16-representable inputs a bf16
+    pointwise node gives the bits of the fp32 node's result rounded once to bf16: GELU and the SwiGLU gate forward and
+    backward, rotary at both signs (sign -1 is the node's backward)."""
+    from openpsg_amd import train_graph as G
+    gen = torch.Generator().manual_seed(11)
+
+    def both(node, x, *args):
+        outs = []
+        for xx, precision in ((x, "bf16"), (x.float(), None)):
+            xx = xx.clone().requires_grad_(True)
+            y = node.apply(xx, *args, precision)
+            dy = _rand(tuple(y.shape), torch.Generator().manual_seed(13)).to(y.dtype)
+            dx, = torch.autograd.grad(y, xx, dy)
+            outs.append((y.to(BF), dx.to(BF)))
+        (y16, dx16), (y32, dx32) = outs
+        assert y16.dtype == BF and torch.equal(y16, y32), node.__name__ + " forward"
+        assert torch.equal(dx16, dx32), node.__name__ + " backward"
+
+    for n in (8, 2056):
+        both(G.GeluFn, _rand((n,), gen, 2.0))
+    both(G.SiluMulFn, _rand((3, 2 * 88), gen, 2.0))
+    for hd in (64, 128):
+        rows, heads, table = 5, 2, 9
+        pos = torch.randint(0, table, (rows,), generator=gen).to(torch.int32).cuda()
+        ang = torch.rand(table, hd // 2, generator=gen) * 6.0
+        both(G.RopeFn, _rand((rows, heads * hd), gen), pos, ang.cos().cuda().contiguous(), ang.sin().cuda().contiguous(), heads)
+
+
 # ---- attention -----------------------------------------------------------------------------------------------------------
 def _keep_mask(B, Mq, Sq, Sk, gen):
     """One fully masked row, one row with a single kept key, and (Mq == Sq == Sk) a causal keep-matrix."""

@@ -52,3 +52,23 @@ def test_graph_precision_argument_validation():
         G.linear(None, None, None, precision="fp16")
     for fn in (G.qformer_pairs, G.llama_teacher_forcing):
         assert inspect.signature(fn).parameters["precision"].default is None
+    # the five nodes both precisions share: an operand of the other precision's dtype (on the CPU: no library call can
+    # have been made) raises an error naming the precision the operand has to have.  The norms read the fp32 residual
+    # stream in both precisions; the pointwise nodes read activations of the precision's own dtype.
+    import torch
+    pos, tab = torch.zeros(2, dtype=torch.int32), torch.zeros(4, 8)
+    for precision, other, own in ((None, torch.bfloat16, "fp32"), ("bf16", torch.float32, "bf16")):
+        t = torch.zeros(2, 16, dtype=other)
+        for node, args in ((G.GeluFn, (t,)), (G.SiluMulFn, (t,)), (G.RopeFn, (t, pos, tab, tab, 1))):
+            with pytest.raises(PsgHipError, match=own):
+                node.apply(*args, precision)
+    g = torch.ones(16)
+    for precision in (None, "bf16"):
+        x = torch.zeros(2, 16, dtype=torch.bfloat16)
+        for node, args in ((G.LayerNormFn, (x, g, g, 1e-12)), (G.RMSNormFn, (x, g, 1e-5))):
+            with pytest.raises(PsgHipError, match="fp32"):
+                node.apply(*args, precision)
+    for node, args in ((G.LayerNormFn, (g, g, g, 1e-12)), (G.RMSNormFn, (g, g, 1e-5)), (G.GeluFn, (g,)), (G.SiluMulFn, (g,)),
+                       (G.RopeFn, (g, pos, tab, tab, 1))):
+        with pytest.raises(PsgHipError, match="precision"):
+            node.apply(*args, "fp16")

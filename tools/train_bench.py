@@ -5,6 +5,7 @@ two precisions of the gradient path:
 
   fp32   dtype='fp32', train_precision=None   the fp32 kernels of csrc/psg_train_bwd.hip, fp32 library GEMMs
   bf16   dtype='bf16', train_precision='bf16' csrc/psg_train_bf16.hip, bf16 library GEMMs, fp32 masters
+(the row and pointwise kernels of both are the templates of csrc/psg_train_rows.h)
 
 Shapes: the training golden T2's geometry (768 x 1024, 9 segments, its relations), synthetic weights, the LLM at
 hidden 4096 / 32 heads / inter 11008 / vocab 32000.  Each precision runs in a process of its own (peak memory is per
