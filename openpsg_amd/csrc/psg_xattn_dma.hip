@@ -1,11 +1,11 @@
 // K6, second generation: relation-query cross-attention with FULL-LINE Q / context traffic.
 //
 // Same arithmetic, mask semantics, tile order and per-unit matrix-core code as psg_xattn_mfma.hip (HF-IB:464-466,
-// 487-496 driven by V4:168-170, 179-185; see that file's header).  What changes is how a unit's 32 x 64 Q tile
-// gets in and its context tile gets out.  The first-generation kernel loaded the Q fragments straight into the
-// MFMA B-operand layout: 4 instructions per unit, each touching 32 cache lines for 32 bytes apiece, and stored
-// the context with 8 instructions of 16 bytes per line; a copy-only build of it ran as slowly as the real one
-//  - the kernel was bound by the number of line touches, not by bytes or flops.  Here
+// 487-496 driven by V4:168-170, 179-185; see that file's header): both take them from psg_xattn_tile.h.  What changes
+// is how a unit's 32 x 64 Q tile gets in and its context tile gets out.  The first-generation kernel loaded the Q
+// fragments straight into the MFMA B-operand layout: 4 instructions per unit, each touching 32 cache lines for 32 bytes
+// apiece, and stored the context with 8 instructions of 16 bytes per line; a copy-only build of it ran as slowly as the
+// real one - the kernel was bound by the number of line touches, not by bytes or flops.  Here
 //   * Q arrives by LDS-DMA (global_load_lds_dwordx4): one instruction = 8 rows x 128 B, i.e. 8 whole lines, into
 //     a per-wave ring of two 4 KiB slots; the bank-conflict swizzle is applied to the SOURCE address (the LDS
 //     image of a DMA is lane-linear), and the fragment reads undo it; the pair ids of the unit ride along as a
@@ -20,10 +20,8 @@
 // first-generation kernel.
 #include <type_traits>
 
-#include "psg_common.h"
-#include "psg_wave.h"
+#include "psg_xattn_tile.h"
 
-#define XD_KSTRIDE 144   // bytes per K row in LDS: 64 bf16 + 16 B pad
 #define XD_SLOT 4352     // 4096 B tile + 256 B pair ids
 #define XD_CLS_COST 3     // a cls tile costs about this many pair tiles (static schedule)
 
@@ -48,15 +46,11 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
   long long* tr = trace ? trace + ((int64_t)blockIdx.x * XD_WAVES + (threadIdx.x >> 6)) * 32 : nullptr;
   if (tr && (threadIdx.x & 63) == 0) tr[0] = __builtin_readcyclecounter();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int Lpad = (L + 31) & ~31;
-  const int NT = Lpad >> 5;
-  const int VS = Lpad * 2 + 16;  // bytes per V^T row in LDS
-  unsigned char* k_lds = smem;
-  unsigned char* vt_lds = smem + (size_t)Lpad * XD_KSTRIDE;
-  unsigned char* mean_lds = vt_lds + (size_t)64 * VS;   // 64 floats: mean of V_h over the L keys
-  uint64_t* bits_lds = reinterpret_cast<uint64_t*>(mean_lds + 256);
-  const int bits_bytes = (N * words * 8 + 15) & ~15;
-  unsigned char* slots = reinterpret_cast<unsigned char*>(bits_lds) + bits_bytes;
+  const XattnImage im = xattn_image(N, words, L);
+  unsigned char* vt_lds = smem + im.vt_off;
+  unsigned char* mean_lds = smem + im.mean_off;
+  uint64_t* bits_lds = reinterpret_cast<uint64_t*>(smem + im.bits_off);
+  unsigned char* slots = smem + im.bytes;
   const int h = blockIdx.x % heads;
   const int g = blockIdx.x / heads;
   const int G = gridDim.x / heads;
@@ -66,36 +60,15 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
   const int l31 = lane & 31, hi = lane >> 5;
   const int r8 = lane >> 3, pc = lane & 7;               // row-order view of a wave: 8 rows x 8 16-byte pieces
 
-  const bool aligned = nq == 33;
-  const int64_t P = R / nq;
-  const int64_t NCLS = aligned ? (P + 31) >> 5 : 0;
-  const int64_t ntile = aligned ? P + NCLS : (R + 31) >> 5;
-  const unsigned char* kfrag_base = k_lds + l31 * XD_KSTRIDE + hi * 16;
-  const unsigned char* vfrag_base = vt_lds + l31 * VS + hi * 16;
+  const XattnTiles tg = xattn_tiles(R, nq);           // cls tiles first, then one tile per pair (psg_xattn_tile.h)
+  const bool aligned = tg.aligned;
+  const int64_t NCLS = tg.NCLS, ntile = tg.ntile;
+  const unsigned char* kfrag_base = smem + l31 * XATTN_KSTRIDE + hi * 16;
+  const unsigned char* vfrag_base = vt_lds + l31 * im.VS + hi * 16;
   unsigned char* my_slots = slots + wid * (2 * XD_SLOT);
   const uint32_t slot_lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)my_slots;
   const uint32_t mean_lds_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)mean_lds;
 
-  // row rr (0..31) of a tile: global row, validity, pair
-  auto tile_row = [&](int64_t tile, int rr, int64_t& row, bool& valid, int64_t& pair) {
-    if (aligned) {
-      if (tile >= NCLS) {
-        pair = tile - NCLS;
-        row = pair * 33 + 1 + rr;
-        valid = true;
-      } else {
-        const int64_t pr = tile * 32 + rr;
-        valid = pr < P;
-        pair = valid ? pr : P - 1;
-        row = pair * 33;
-      }
-    } else {
-      row = tile * 32 + rr;
-      valid = row < R;
-      if (!valid) row = R - 1;
-      pair = row / nq;
-    }
-  };
   // DMA of one unit into slot s: 4 x (8 rows x 128 B), piece (pc ^ r8) of row 8 i + r8 lands in slot position pc
   // of that row; + the pair ids of rows 0..31 (lanes 32..63 repeat them)
   // poll mode: the unit's arrival is read off its LDS slot - the pair-id words (the LAST of the five DMAs; loads land in
@@ -113,7 +86,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     for (int i = 0; i < 4; ++i) {
       int64_t row, pair;
       bool valid;
-      tile_row(tile, 8 * i + r8, row, valid, pair);
+      xattn_tile_row(tg, tile, 8 * i + r8, row, valid, pair);
       const uint16_t* src = q + row * hidden + h * 64 + ((pc ^ r8) * 8);
       if (q_index) {
         if (tile >= NCLS) {
@@ -129,7 +102,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     {
       int64_t row, pair;
       bool valid;
-      tile_row(tile, l31, row, valid, pair);
+      xattn_tile_row(tg, tile, l31, row, valid, pair);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pair_index + pair),
                                        (__attribute__((address_space(3))) void*)(dst + 4096), 4, 0, 0);
     }
@@ -174,37 +147,13 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     const int64_t npair = ntile - NCLS;
     return idx < npair ? NCLS + idx : -1;
   };
-  union {
-    uint32_t u[4];
-    typename E::v8 v;
-  } b_one;
-  b_one.u[0] = hi ? 0u : E::ONE;
-  b_one.u[1] = b_one.u[2] = b_one.u[3] = 0u;
-  const float C8 = 0.125f * 1.4426950408889634f;
-  const float bias_raw = policy == PSG_EMPTY_UNIFORM ? -3.4028234663852886e38f : -80000.0f;
 
   // ---- prologue: every global request of the workgroup is issued before the first wait - K_h / V_h (registers),
   // the object bit table, then the Q tiles of the first two units by DMA - so the staging costs one memory round
   // trip (a load -> LDS-write loop, or the DMAs ahead of plain loads, paid one per step: 8 us of 54)
   constexpr int IT = NC;                                 // (Lpad/2 key pairs * 8 chunks) / (64 XD_WAVES) threads <= NC
   uint4 kv[IT][2], vv[IT][2];
-  {
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int e = tid + it * (XD_WAVES * 64);
-      const int m = e >> 3, c = e & 7;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int key = 2 * m + u;
-        kv[it][u] = make_uint4(0, 0, 0, 0);
-        vv[it][u] = make_uint4(0, 0, 0, 0);
-        if (key < L) {
-          kv[it][u] = *reinterpret_cast<const uint4*>(k + (int64_t)key * hidden + h * 64 + c * 8);
-          vv[it][u] = *reinterpret_cast<const uint4*>(v + (int64_t)key * hidden + h * 64 + c * 8);
-        }
-      }
-    }
-  }
+  xattn_kv_load<XD_WAVES * 64, IT>(kv, vv, k, v, tid, L, hidden, h);
   uint64_t bitreg[2] = {0, 0};
   const int nbw = N * words;
 #pragma unroll
@@ -223,36 +172,14 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     if (e < nbw) bits_lds[e] = bitreg[i];
   }
   for (int e = tid + 2 * (XD_WAVES * 64); e < nbw; e += XD_WAVES * 64) bits_lds[e] = bits[e];   // N * words > 1024
-  {
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int e = tid + it * (XD_WAVES * 64);
-      const int m = e >> 3, c = e & 7;
-      if (2 * m < Lpad) {
-        *reinterpret_cast<uint4*>(k_lds + (2 * m) * XD_KSTRIDE + c * 16) = kv[it][0];
-        *reinterpret_cast<uint4*>(k_lds + (2 * m + 1) * XD_KSTRIDE + c * 16) = kv[it][1];
-        const int o = (2 * m) & 15;
-        const int pos = (o & 3) | ((o & 8) >> 1) | ((o & 4) << 1);  // swap key bits 2 <-> 3 inside a 16-key group
-        const int kcol = (((2 * m) & ~15) | pos) * 2;
-        const uint32_t a[4] = {vv[it][0].x, vv[it][0].y, vv[it][0].z, vv[it][0].w};
-        const uint32_t bq[4] = {vv[it][1].x, vv[it][1].y, vv[it][1].z, vv[it][1].w};
-#pragma unroll
-        for (int d2 = 0; d2 < 4; ++d2) {
-          const uint32_t lo = (a[d2] & 0xffffu) | (bq[d2] << 16);
-          const uint32_t hi2 = (a[d2] >> 16) | (bq[d2] & 0xffff0000u);
-          *reinterpret_cast<uint32_t*>(vt_lds + (c * 8 + 2 * d2) * VS + kcol) = lo;
-          *reinterpret_cast<uint32_t*>(vt_lds + (c * 8 + 2 * d2 + 1) * VS + kcol) = hi2;
-        }
-      }
-    }
-  }
+  xattn_kv_store<XD_WAVES * 64, IT>(smem, im, kv, vv, tid);
   __syncthreads();
   {                                                     // mean of V_h over the keys (pad keys hold zeros): 8 lanes per
     const int d = tid >> 3, part = tid & 7;             // dim, each summing every 8th 16-byte piece of the V^T row
     if (d < 64) {
       float sum = 0.f;
-      const uint16_t* vr = reinterpret_cast<const uint16_t*>(vt_lds + d * VS);
-      for (int kk = part * 8; kk < Lpad; kk += 64) {
+      const uint16_t* vr = reinterpret_cast<const uint16_t*>(vt_lds + d * im.VS);
+      for (int kk = part * 8; kk < im.Lpad; kk += 64) {
         const uint4 x = *reinterpret_cast<const uint4*>(vr + kk);
         const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
@@ -285,42 +212,16 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     __builtin_amdgcn_sched_barrier(0);
 
     int oi, oj;
-    if (N <= 1024) {
-      oi = (int)(((float)pidx + 0.5f) * rcpN);
-      oj = pidx - oi * N;
-    } else {
-      oi = pidx / N;
-      oj = pidx % N;
-    }
+    xattn_pair_objects(pidx, N, rcpN, oi, oj);
     const uint32_t* wi = reinterpret_cast<const uint32_t*>(bits_lds + (int64_t)oi * words);
     const uint32_t* wj = reinterpret_cast<const uint32_t*>(bits_lds + (int64_t)oj * words);
-    uint32_t needmask = 0;      // wave-uniform
-    bool force_all = false;
-    bool use_mean = false;
-    if constexpr (AL) {
-      for (int t = 0; t < NT; ++t)
-        needmask |= ((__builtin_amdgcn_readfirstlane(wi[t] | wj[t]) != 0u) ? 1u : 0u) << t;
-      if (needmask == 0u) {
-        if (policy == PSG_EMPTY_UNIFORM) {
-          use_mean = true;                                // uniform softmax over the L real keys: mean_k V[k]
-        } else {
-          force_all = true;
-          needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
-        }
-      }
-    } else {
-      bool row_empty = true;
-      for (int t = 0; t < NT; ++t) {
-        const uint32_t w = wi[t] | wj[t];
-        row_empty = row_empty && (w == 0u);
-        needmask |= (__any(w != 0u) ? 1u : 0u) << t;
-      }
-      if (__any(row_empty)) needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
-    }
+    uint32_t needmask;
+    bool force_all;
+    const bool use_mean = xattn_mask_analysis<AL>(wi, wj, im.NT, policy, needmask, force_all);
 
     psg_f32x16 o0 = {0}, o1 = {0};
     float m_run = -INFINITY, l_run = 0.f;
-    if (use_mean) {                                       // (asm reads: see psg_lds_read128)
+    if (use_mean) {       // empty union, uniform softmax over the L real keys: mean_k V[k] (asm reads: psg_wave.h)
       psg_u32x4 m0[4], m1[4];
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
@@ -338,95 +239,8 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
         }
       l_run = 1.0f;
     }
-    while (needmask != 0u) {
-      const int t = __builtin_ctz(needmask);
-      needmask &= needmask - 1u;
-      uint32_t word = wi[t] | wj[t];
-      const int left = L - 32 * t;                       // real keys in this tile (>= 1)
-      psg_f32x16 acc;
-      const unsigned char* kp = kfrag_base + t * 32 * XD_KSTRIDE;
-      if constexpr (AL) {
-        if (force_all) word = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
-        union {
-          uint32_t u[4];
-          typename E::v8 v;
-        } a_bias;
-        a_bias.u[0] = (((word >> l31) & 1u) | (uint32_t)hi) ? 0u : E::NEG_2_15;   // 0 / -2^15 in bf16
-        a_bias.u[1] = a_bias.u[2] = a_bias.u[3] = 0u;
-        acc = E::mfma32(a_bias.v, b_one.v, (psg_f32x16){0});
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s4 * 32);
-          acc = E::mfma32(a, qf[s4].b, acc);
-        }
-      } else {
-        {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp);
-          acc = E::mfma32(a, qf[0].b, (psg_f32x16){0});
-        }
-#pragma unroll
-        for (int s4 = 1; s4 < 4; ++s4) {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s4 * 32);
-          acc = E::mfma32(a, qf[s4].b, acc);
-        }
-        const uint32_t inv = ~word >> (4 * hi);
-        const bool has_pad = left < 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int koff = (r & 3) + 8 * (r >> 2);
-          const int mb = __builtin_amdgcn_sbfe((int)inv, koff, 1);  // -1 if masked
-          float y = acc[r] + __uint_as_float((uint32_t)mb & __float_as_uint(bias_raw));
-          if (has_pad && (koff + 4 * hi >= left)) y = -INFINITY;
-          acc[r] = y;
-        }
-      }
-      float cmax = acc[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) cmax = fmaxf(cmax, acc[r]);
-      cmax = psg_xchg32_max(cmax);
-      const float m_new = fmaxf(m_run, cmax);
-      float alpha, csum = 0.f;
-      if constexpr (AL) {
-        const float mc = m_new * C8;
-        alpha = __builtin_amdgcn_exp2f(fmaf(m_run, C8, -mc));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(fmaf(acc[r], C8, -mc));
-          acc[r] = pv;
-          csum += pv;
-        }
-      } else {
-        alpha = __builtin_amdgcn_exp2f((m_run - m_new) * C8);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = __builtin_amdgcn_exp2f((acc[r] - m_new) * C8);
-          acc[r] = pv;
-          csum += pv;
-        }
-      }
-      csum = psg_xchg32_sum(csum);
-      l_run = l_run * alpha + csum;
-      m_run = m_new;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        o0[r] *= alpha;
-        o1[r] *= alpha;
-      }
-#pragma unroll
-      for (int gg = 0; gg < 2; ++gg) {
-        union {
-          uint32_t u[4];
-          typename E::v8 v;
-        } pf;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pf.u[e] = E::pack(acc[8 * gg + 2 * e], acc[8 * gg + 2 * e + 1]);
-        const unsigned char* vp = vfrag_base + (t * 32 + 16 * gg) * 2;
-        const typename E::v8 a0 = *reinterpret_cast<const typename E::v8*>(vp);
-        const typename E::v8 a1 = *reinterpret_cast<const typename E::v8*>(vp + 32 * VS);
-        o0 = E::mfma32(a0, pf.v, o0);
-        o1 = E::mfma32(a1, pf.v, o1);
-      }
-    }
+    xattn_key_tiles<E, AL>(qf[0].b, qf[1].b, qf[2].b, qf[3].b, wi, wj, needmask, force_all, kfrag_base, vfrag_base,
+                           im.VS, L, policy, l31, hi, o0, o1, m_run, l_run);
     // ---- context tile: lane (q = l31, hi) holds O[q][32 dt + (r&3) + 8 (r>>2) + 4 hi]; 16-byte piece index of
     // dims 8 rr + 4 hi .. + 3 is rr (first half) / 4 + rr (second half); swizzled by the row like the Q image
     const float inv_l = 1.0f / l_run;
@@ -452,7 +266,7 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
     for (int i = 0; i < 4; ++i) {
       int64_t row, pair;
       bool valid;
-      tile_row(tile, 8 * i + r8, row, valid, pair);
+      xattn_tile_row(tg, tile, 8 * i + r8, row, valid, pair);
       if (AL || valid) {
         uint16_t* dst = out + row * hidden + h * 64 + pc * 8;
         if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(orow[i]) : "memory");
@@ -492,10 +306,8 @@ cross_attn_dma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict
   }
 }
 
-static size_t xd_lds_bytes(int N, int words, int L, int waves) {
-  const int Lpad = (L + 31) & ~31;
-  return (size_t)Lpad * XD_KSTRIDE + (size_t)64 * (Lpad * 2 + 16) + 256 + (((size_t)N * words * 8 + 15) & ~(size_t)15) +
-         (size_t)waves * 2 * XD_SLOT + 16;
+static size_t xd_lds_bytes(int N, int words, int L, int waves) {    // image + slot ring + cursor
+  return xattn_image_bytes(N, words, L) + (size_t)waves * 2 * XD_SLOT + 16;
 }
 
 // smallest LDS footprint of the kernel family (8 waves); the dispatcher compares it with the 160 KiB of a CU
@@ -505,21 +317,19 @@ template <typename E>
 static int xd_launch(psg_ctx* ctx, const void* q, const void* k, const void* v, const uint64_t* bits, int words,
                      const int32_t* pair_index, int N, int P, int L, int nq, int heads, int policy, void* out,
                      hipStream_t st, const int32_t* q_index, const void* q_cls) {
-  const int Lpad = (L + 31) & ~31;
   // 8 waves per CU, ten for launches with few tiles per wave when the K/V image leaves room for ten slot pairs
   // (L <= 256): with the tiles drawn from the LDS counter, BASELINE C2 (2579 tiles per head, 15 per wave) runs 6 % faster
   // with ten (more Q streams in flight through the staging phase and the tail), C4 (61 per wave) 3 % slower.
   // Option xattn_waves: 8 = this rule, 10 = always ten, 0 = always eight.
-  const int64_t ntile0 = nq == 33 ? (int64_t)P + (P + 31) / 32 : ((int64_t)P * nq + 31) / 32;
-  const int64_t per_wave8 = ntile0 / (((int64_t)ctx->num_cu / heads > 0 ? (int64_t)ctx->num_cu / heads : 1) * 8);
+  const int64_t ntile = xattn_ntile(P, nq);
+  const int64_t per_wave8 = ntile / (((int64_t)ctx->num_cu / heads > 0 ? (int64_t)ctx->num_cu / heads : 1) * 8);
   const bool want10 = ctx->opt.xattn_waves == 10 || (ctx->opt.xattn_waves == 8 && per_wave8 < 32 && per_wave8 >= 4);
   const int waves = (want10 && xd_lds_bytes(N, words, L, 10) <= 160 * 1024) ? 10 : 8;
   const size_t lds = xd_lds_bytes(N, words, L, waves);
-  const int NC = (Lpad / 32 + 3) / 4;
+  const int NC = (xattn_image(N, words, L).NT + 3) / 4;
   PSG_REQUIRE(lds <= 160 * 1024 && NC >= 1 && NC <= 3, PSG_ERR_UNSUPPORTED,
               "psg_qformer_cross_attn(dma): L=%d needs %zu B of LDS", L, lds);
   const int64_t R = (int64_t)P * nq;
-  const int64_t ntile = nq == 33 ? (int64_t)P + (P + 31) / 32 : (R + 31) / 32;
   int64_t G = ctx->num_cu / heads;                       // one workgroup per CU
   const int64_t maxG = (ntile + waves - 1) / waves;
   if (G > maxG) G = maxG;

@@ -7,23 +7,18 @@
 // bitmask table and tests bits in registers.
 //
 // Work layout (gfx950, wave = 64):
-//   * a workgroup (4 waves, 2 per CU) owns one head h: it stages K_h [Lpad][64], V_h^T [64][Lpad] (bf16, row
-//     strides padded by 16 B => conflict-free ds_read_b128), the mean of V_h and the whole object bit table
-//     into LDS once, then its waves walk row tiles in a static round-robin order;
+//   * a workgroup (4 waves, 2 per CU) owns one head h: it stages the head's LDS image (K_h, V_h^T, the mean of V_h
+//     and the whole object bit table) once, then its waves walk row tiles in a static round-robin order;
 //   * row tiles (nq == 33): first the tiles that batch the cls rows (row 0) of 32 consecutive pairs - they
 //     carry per-row masks - then one tile per pair = its rows 1..32, which share ONE mask, so the mask words
 //     are wave-uniform, 32-key tiles nobody attends to are skipped (they contribute exactly 0), and an empty
 //     union under the "uniform" policy is just the mean of V;
-//   * S^T = K . Q^T with v_mfma_f32_32x32x16_bf16 (A = K fragment from LDS, B = Q fragment held in
-//     registers), so a lane owns ONE query row (column lane&31 of D) and 16 keys per 32-key tile; for pair
-//     tiles the additive mask is one more MFMA (A'[key][0] = 0 / -2^15, B'[0][row] = 1) instead of three
-//     VALU instructions per score; the softmax reduction is in-register plus one lane^32 exchange;
-//   * O^T = V^T . P^T the same way (A = V^T fragment from LDS, B = this lane's exponentiated scores packed to
-//     bf16), so the online-softmax rescale and the final 1/l are lane-local.  V^T is stored with key bits
-//     2<->3 swapped inside every 16-key group, which makes the accumulator registers of the S^T tile line up
-//     with the B-operand slots of the P.V MFMA without any cross-lane shuffle;
-//   * the active key tiles of a unit are a dynamic loop (per-tile online softmax, 22 KB of code instead of
-//     55 KB unrolled); the Q fragments and pair ids of the next two units are in flight while one is computed.
+//   * the image layout, the tile order, the K/V staging, the mask analysis and the loop over a unit's key tiles
+//     (S^T = K . Q^T and O^T = V^T . P^T on v_mfma_f32_32x32x16, mask bias as one more MFMA, online softmax) are
+//     shared with the second-generation kernel (psg_xattn_dma.hip) and live in psg_xattn_tile.h;
+//   * this file's own: the Q fragments go straight from global memory into the MFMA B-operand layout, the Q
+//     fragments and pair ids of the next two units are in flight while one is computed, and the context rows
+//     are stored directly from the accumulator layout.
 // The kernel moves Q in and the context out once each (PMC: 126 MB + 124 MB at N = 50) and is bound by that
 // traffic, 128 bytes per row per head; see DESIGN.md for the timeline that led here.
 //
@@ -34,12 +29,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "psg_common.h"
-#include "psg_wave.h"
+#include "psg_xattn_tile.h"
 
-#define XA_KSTRIDE 144  // bytes per K row in LDS: 64 bf16 + 16 B pad
-
-template <typename E, int NC>   // NC = key chunks of 128 (L <= 128 NC): unrolled so the prefetched mask words index statically
+template <typename E, int NC>   // NC = key chunks of 128 (L <= 128 NC): sizes the staging registers
 __global__ void __launch_bounds__(256, 2)
 cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
                        const uint64_t* __restrict__ bits, int words, const int32_t* __restrict__ pair_index, int N,
@@ -49,31 +41,22 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
   long long* tr = trace ? trace + ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 : nullptr;
   if (tr && (threadIdx.x & 63) == 0) tr[0] = __builtin_readcyclecounter();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int Lpad = (L + 31) & ~31;
-  const int NT = Lpad >> 5;
-  const int VS = Lpad * 2 + 16;  // bytes per V^T row in LDS
-  unsigned char* k_lds = smem;
-  unsigned char* vt_lds = smem + (size_t)Lpad * XA_KSTRIDE;
-  unsigned char* mean_lds = vt_lds + (size_t)64 * VS;   // 64 floats: mean of V_h over the L keys
-  uint64_t* bits_lds = reinterpret_cast<uint64_t*>(mean_lds + 256);   // object bit rows [N][words]
+  const XattnImage im = xattn_image(N, words, L);
+  unsigned char* vt_lds = smem + im.vt_off;
+  unsigned char* mean_lds = smem + im.mean_off;
+  uint64_t* bits_lds = reinterpret_cast<uint64_t*>(smem + im.bits_off);
   const int h = blockIdx.x % heads;
   const int g = blockIdx.x / heads;
   const int G = gridDim.x / heads;
   const int hidden = heads * 64;
   const int tid = threadIdx.x;
-
-
   const int lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
-  // Row tiles.  nq == 33: tile t < P = rows 1..32 of pair t (the 32 relation queries share ONE pair
-  // mask, so most 32-key tiles are masked for the whole tile and are skipped below); tiles >= P batch
-  // the cls rows (row 0) of 32 consecutive pairs.  Other nq: flat 32-row tiles.
-  const bool aligned = nq == 33;
-  const int64_t P = R / nq;
-  const int64_t NCLS = aligned ? (P + 31) >> 5 : 0;
-  const int64_t ntile = aligned ? P + NCLS : (R + 31) >> 5;
-  const unsigned char* kfrag_base = k_lds + l31 * XA_KSTRIDE + hi * 16;
-  const unsigned char* vfrag_base = vt_lds + l31 * VS + hi * 16;
+  const XattnTiles tg = xattn_tiles(R, nq);           // cls tiles first, then one tile per pair (psg_xattn_tile.h)
+  const bool aligned = tg.aligned;
+  const int64_t NCLS = tg.NCLS, ntile = tg.ntile;
+  const unsigned char* kfrag_base = smem + l31 * XATTN_KSTRIDE + hi * 16;
+  const unsigned char* vfrag_base = vt_lds + l31 * im.VS + hi * 16;
 
   // One unit of work = (row tile, head h).  Its operands sit behind a chain of dependent global loads
   // (pair_index -> object bit rows -> mask words); most key tiles are skipped, so a unit is short (~1 us)
@@ -86,33 +69,11 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
     int64_t row;
     bool rvalid;
   };
-  // Queue order (nq == 33): the NCLS tiles that batch the cls rows (row 0) of 32 consecutive pairs come
-  // FIRST - they carry per-row masks and need most key tiles, ~5x the cost of a pair tile; then tile
-  // NCLS + p = rows 1..32 of pair p.
-  auto unit_rows = [&](int64_t tile, int64_t& row, bool& rvalid, int64_t& pair) {
-    if (aligned) {
-      if (tile >= NCLS) {
-        pair = tile - NCLS;
-        row = pair * 33 + 1 + l31;
-        rvalid = true;
-      } else {
-        const int64_t pr = tile * 32 + l31;
-        rvalid = pr < P;
-        pair = rvalid ? pr : P - 1;
-        row = pair * 33;
-      }
-    } else {
-      row = tile * 32 + l31;
-      rvalid = row < R;
-      if (!rvalid) row = R - 1;
-      pair = row / nq;
-    }
-  };
   // A fetch only ISSUES loads (Q fragments and the pair id); the object bit rows live in LDS, so nothing
   // in the unit's operand chain depends on another global load.
   auto fetch = [&](int64_t tile, XUnit& u) {
     int64_t pair;
-    unit_rows(tile, u.row, u.rvalid, pair);
+    xattn_tile_row(tg, tile, l31, u.row, u.rvalid, pair);
     // Q fragments: B operand of S^T = K.Q^T; lane (q = lane&31, hi) holds Q[q][16 s + 8 hi .. +7]
     const uint16_t* qp = q + u.row * hidden + h * 64 + hi * 8;
 #pragma unroll
@@ -132,181 +93,40 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
     wnext += wstride;
     return t;
   };
-  // B operand of the mask-bias MFMA: B'[k = 0][row] = 1 for every row, all other k-slots 0
-  union {
-    uint32_t u[4];
-    typename E::v8 v;
-  } b_one;
-  b_one.u[0] = hi ? 0u : E::ONE;
-  b_one.u[1] = b_one.u[2] = b_one.u[3] = 0u;
-  const float C8 = 0.125f * 1.4426950408889634f;
-  const float bias_raw = policy == PSG_EMPTY_UNIFORM ? -3.4028234663852886e38f : -80000.0f;  // generic path, pre-scale
-
-  // One unit = (row tile, head).  Two code paths:
-  //  AL (nq == 33, tile < P): the 32 rows are rows 1..32 of ONE pair and share its mask, so the mask words
-  //     are wave-uniform (scalar tile skipping) and the additive mask is applied by the matrix core: one
-  //     extra MFMA per key tile adds A'[key][0] * B'[0][row] = bias(key) * 1 to S^T, which replaces three
-  //     VALU instructions per score.  A pair with an empty union under the "uniform" policy is the mean of
-  //     V over the L keys (precomputed per workgroup): no bias has to absorb the scores, so a moderate
-  //     bias (-2^15, exact in bf16) and the fused exp2(fma(s, C, -m C)) are safe.
-  //  generic (cls-row tiles, other nq): per-row masks in VALU, absorbing finfo.min bias as in the reference
-  //     (HF additive mask), exp2((s - m) * C) so that equal scores give exactly 2^0.
+  // One unit = (row tile, head): AL = a pair tile (nq == 33, rows 1..32 of ONE pair, wave-uniform mask words, mask
+  // bias on the matrix core), otherwise per-row masks in VALU; the arithmetic is psg_xattn_tile.h's.
   auto run_unit = [&](const XUnit& cur, auto al_tag) {
     constexpr bool AL = decltype(al_tag)::value;
     const int64_t row = cur.row;
     const bool rvalid = cur.rvalid;
-    typename E::v8 qf[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = cur.qf[s];
-
-    // i = pidx / N, j = pidx % N; exact in fp32 for pidx < 2^24 and N <= 1024
     int oi, oj;
-    if (N <= 1024) {
-      oi = (int)(((float)cur.pidx + 0.5f) * rcpN);
-      oj = cur.pidx - oi * N;
-    } else {
-      oi = cur.pidx / N;
-      oj = cur.pidx % N;
-    }
-    // object bit rows as 32-bit words: word t = keys [32 t, 32 t + 32), 1 = attend
+    xattn_pair_objects(cur.pidx, N, rcpN, oi, oj);
     const uint32_t* wi = reinterpret_cast<const uint32_t*>(bits_lds + (int64_t)oi * words);
     const uint32_t* wj = reinterpret_cast<const uint32_t*>(bits_lds + (int64_t)oj * words);
-    // which 32-key tiles does this row tile need?  A tile no row attends to contributes exactly 0: skipped.
-    uint32_t needmask = 0;      // wave-uniform
-    bool force_all = false;     // AL + "unmasked" policy + empty union: plain attention over the L real keys
-    if constexpr (AL) {
-      for (int t = 0; t < NT; ++t)
-        needmask |= ((__builtin_amdgcn_readfirstlane(wi[t] | wj[t]) != 0u) ? 1u : 0u) << t;
-      if (needmask == 0u) {
-        if (policy == PSG_EMPTY_UNIFORM) {
-          // uniform softmax over the L real keys: out = mean_k V[k]
-          const float* mean = reinterpret_cast<const float*>(mean_lds);
-          uint16_t* op = out + row * hidden + h * 64 + 4 * hi;
+    uint32_t needmask;
+    bool force_all;
+    if (xattn_mask_analysis<AL>(wi, wj, im.NT, policy, needmask, force_all)) {
+      // empty union, uniform softmax over the L real keys: out = mean_k V[k]
+      const float* mean = reinterpret_cast<const float*>(mean_lds);
+      uint16_t* op = out + row * hidden + h * 64 + 4 * hi;
 #pragma unroll
-          for (int rr = 0; rr < 4; ++rr) {
-            const float4 m0 = *reinterpret_cast<const float4*>(mean + 8 * rr + 4 * hi);
-            const float4 m1 = *reinterpret_cast<const float4*>(mean + 32 + 8 * rr + 4 * hi);
-            uint2 w0, w1;
-            w0.x = E::pack(m0.x, m0.y);
-            w0.y = E::pack(m0.z, m0.w);
-            w1.x = E::pack(m1.x, m1.y);
-            w1.y = E::pack(m1.z, m1.w);
-            *reinterpret_cast<uint2*>(op + 8 * rr) = w0;
-            *reinterpret_cast<uint2*>(op + 32 + 8 * rr) = w1;
-          }
-          return;
-        }
-        force_all = true;
-        needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
+      for (int rr = 0; rr < 4; ++rr) {
+        const float4 m0 = *reinterpret_cast<const float4*>(mean + 8 * rr + 4 * hi);
+        const float4 m1 = *reinterpret_cast<const float4*>(mean + 32 + 8 * rr + 4 * hi);
+        uint2 w0, w1;
+        w0.x = E::pack(m0.x, m0.y);
+        w0.y = E::pack(m0.z, m0.w);
+        w1.x = E::pack(m1.x, m1.y);
+        w1.y = E::pack(m1.z, m1.w);
+        *reinterpret_cast<uint2*>(op + 8 * rr) = w0;
+        *reinterpret_cast<uint2*>(op + 32 + 8 * rr) = w1;
       }
-    } else {
-      bool any_empty = false, row_empty = true;
-      for (int t = 0; t < NT; ++t) {
-        const uint32_t w = wi[t] | wj[t];
-        row_empty = row_empty && (w == 0u);
-        needmask |= (__any(w != 0u) ? 1u : 0u) << t;
-      }
-      // a row whose pair mask is empty attends to every key (uniform softmax): it needs all tiles
-      any_empty = __any(row_empty);
-      if (any_empty) needmask = NT >= 32 ? 0xffffffffu : (1u << NT) - 1u;
+      return;
     }
-
     psg_f32x16 o0 = {0}, o1 = {0};
     float m_run = -INFINITY, l_run = 0.f;
-
-    while (needmask != 0u) {
-      const int t = __builtin_ctz(needmask);
-      needmask &= needmask - 1u;
-      uint32_t word = wi[t] | wj[t];
-      const int left = L - 32 * t;                       // real keys in this tile (>= 1)
-      psg_f32x16 acc;
-      const unsigned char* kp = kfrag_base + t * 32 * XA_KSTRIDE;
-      if constexpr (AL) {
-        if (force_all) word = left >= 32 ? 0xffffffffu : (1u << left) - 1u;
-        // A'[key = lane&31][k = 0] = 0 if the pair attends to this key, else -2^15 (bf16 0xc700)
-        union {
-          uint32_t u[4];
-          typename E::v8 v;
-        } a_bias;
-        a_bias.u[0] = (((word >> l31) & 1u) | (uint32_t)hi) ? 0u : E::NEG_2_15;
-        a_bias.u[1] = a_bias.u[2] = a_bias.u[3] = 0u;
-        acc = E::mfma32(a_bias.v, b_one.v, (psg_f32x16){0});
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s * 32);
-          acc = E::mfma32(a, qf[s], acc);
-        }
-      } else {
-        {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp);
-          acc = E::mfma32(a, qf[0], (psg_f32x16){0});
-        }
-#pragma unroll
-        for (int s = 1; s < 4; ++s) {
-          const typename E::v8 a = *reinterpret_cast<const typename E::v8*>(kp + s * 32);
-          acc = E::mfma32(a, qf[s], acc);
-        }
-        // additive mask per (row, key): register r of a lane is key (r&3) + 8 (r>>2) + 4 hi of the tile
-        const uint32_t inv = ~word >> (4 * hi);
-        const bool has_pad = left < 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int koff = (r & 3) + 8 * (r >> 2);
-          const int mb = __builtin_amdgcn_sbfe((int)inv, koff, 1);  // -1 if masked
-          float y = acc[r] + __uint_as_float((uint32_t)mb & __float_as_uint(bias_raw));
-          if (has_pad && (koff + 4 * hi >= left)) y = -INFINITY;
-          acc[r] = y;
-        }
-      }
-      // online softmax over the raw scores (the scale is positive)
-      float cmax = acc[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) cmax = fmaxf(cmax, acc[r]);
-      cmax = psg_xchg32_max(cmax);
-      const float m_new = fmaxf(m_run, cmax);
-      float alpha, csum = 0.f;
-      if constexpr (AL) {
-        const float mc = m_new * C8;
-        alpha = __builtin_amdgcn_exp2f(fmaf(m_run, C8, -mc));
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(fmaf(acc[r], C8, -mc));
-          acc[r] = pv;
-          csum += pv;
-        }
-      } else {
-        alpha = __builtin_amdgcn_exp2f((m_run - m_new) * C8);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = __builtin_amdgcn_exp2f((acc[r] - m_new) * C8);
-          acc[r] = pv;
-          csum += pv;
-        }
-      }
-      csum = psg_xchg32_sum(csum);
-      l_run = l_run * alpha + csum;
-      m_run = m_new;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        o0[r] *= alpha;
-        o1[r] *= alpha;
-      }
-      // O^T += V^T . P^T : A = V^T fragment (LDS), B = this lane's P values packed to bf16
-#pragma unroll
-      for (int gg = 0; gg < 2; ++gg) {
-        union {
-          uint32_t u[4];
-          typename E::v8 v;
-        } pf;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pf.u[e] = E::pack(acc[8 * gg + 2 * e], acc[8 * gg + 2 * e + 1]);
-        const unsigned char* vp = vfrag_base + (t * 32 + 16 * gg) * 2;
-        const typename E::v8 a0 = *reinterpret_cast<const typename E::v8*>(vp);
-        const typename E::v8 a1 = *reinterpret_cast<const typename E::v8*>(vp + 32 * VS);
-        o0 = E::mfma32(a0, pf.v, o0);
-        o1 = E::mfma32(a1, pf.v, o1);
-      }
-    }
+    xattn_key_tiles<E, AL>(cur.qf[0], cur.qf[1], cur.qf[2], cur.qf[3], wi, wj, needmask, force_all, kfrag_base,
+                           vfrag_base, im.VS, L, policy, l31, hi, o0, o1, m_run, l_run);
     // epilogue: lane (q, hi) holds O[q][32 dt + (r&3) + 8 (r>>2) + 4 hi]
     if (AL || rvalid) {
       const float inv_l = 1.0f / l_run;
@@ -349,54 +169,17 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 
   for (int e = threadIdx.x; e < N * words; e += 256) bits_lds[e] = bits[e];
   // ---- stage K_h and V_h^T (once per workgroup) ----
-  // All global loads of a thread are issued before the first LDS write (a load -> write loop paid one
-  // L2 round trip per iteration: 20 us of prologue).  A thread owns the key PAIR (2m, 2m+1) of one 8-dim
-  // chunk c: the two keys are neighbours in the V^T row, so the transposed writes are 32-bit.
   {
     constexpr int IT = 2 * NC;                           // (Lpad/2 key pairs * 8 chunks) / 256 threads <= 2 NC
     uint4 kv[IT][2], vv[IT][2];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int e = tid + it * 256;
-      const int m = e >> 3, c = e & 7;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int key = 2 * m + u;
-        kv[it][u] = make_uint4(0, 0, 0, 0);
-        vv[it][u] = make_uint4(0, 0, 0, 0);
-        if (key < L) {
-          kv[it][u] = *reinterpret_cast<const uint4*>(k + (int64_t)key * hidden + h * 64 + c * 8);
-          vv[it][u] = *reinterpret_cast<const uint4*>(v + (int64_t)key * hidden + h * 64 + c * 8);
-        }
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int e = tid + it * 256;
-      const int m = e >> 3, c = e & 7;
-      if (2 * m < Lpad) {
-        *reinterpret_cast<uint4*>(k_lds + (2 * m) * XA_KSTRIDE + c * 16) = kv[it][0];
-        *reinterpret_cast<uint4*>(k_lds + (2 * m + 1) * XA_KSTRIDE + c * 16) = kv[it][1];
-        const int o = (2 * m) & 15;
-        const int pos = (o & 3) | ((o & 8) >> 1) | ((o & 4) << 1);  // swap bits 2 <-> 3 (bit 0 stays: pair adjacent)
-        const int kcol = (((2 * m) & ~15) | pos) * 2;
-        const uint32_t a[4] = {vv[it][0].x, vv[it][0].y, vv[it][0].z, vv[it][0].w};
-        const uint32_t bq[4] = {vv[it][1].x, vv[it][1].y, vv[it][1].z, vv[it][1].w};
-#pragma unroll
-        for (int d2 = 0; d2 < 4; ++d2) {
-          const uint32_t lo = (a[d2] & 0xffffu) | (bq[d2] << 16);            // dim 2 d2    of keys 2m, 2m+1
-          const uint32_t hi2 = (a[d2] >> 16) | (bq[d2] & 0xffff0000u);      // dim 2 d2 + 1
-          *reinterpret_cast<uint32_t*>(vt_lds + (c * 8 + 2 * d2) * VS + kcol) = lo;
-          *reinterpret_cast<uint32_t*>(vt_lds + (c * 8 + 2 * d2 + 1) * VS + kcol) = hi2;
-        }
-      }
-    }
+    xattn_kv_load<256, IT>(kv, vv, k, v, tid, L, hidden, h);
+    xattn_kv_store<256, IT>(smem, im, kv, vv, tid);
   }
   __syncthreads();
   if (tid < 64) {                                       // pad keys hold zeros: sum over all Lpad slots
     float sum = 0.f;
-    const uint16_t* vr = reinterpret_cast<const uint16_t*>(vt_lds + tid * VS);
-    for (int kk = 0; kk < Lpad; kk += 8) {
+    const uint16_t* vr = reinterpret_cast<const uint16_t*>(vt_lds + tid * im.VS);
+    for (int kk = 0; kk < im.Lpad; kk += 8) {
       const uint4 x = *reinterpret_cast<const uint4*>(vr + kk);
       const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
@@ -447,25 +230,14 @@ cross_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restric
 #undef XA_STEP
 }
 
-int psg_cross_attn_dma_launch(psg_ctx* ctx, const void* q, const void* k, const void* v, const uint64_t* bits,
-                              int words, const int32_t* pair_index, int N, int P, int L, int nq, int heads, int policy,
-                              void* out, int dtype, hipStream_t st, const int32_t* q_index = nullptr,
-                              const void* q_cls = nullptr);
-extern "C" int psg_cross_attn_dma_lds_bytes(int N, int words, int L);
-
-int psg_cross_attn_simple_launch(const void* q, const void* k, const void* v, const uint64_t* bits, int words,
-                                 const int32_t* pair_index, int N, int P, int L, int nq, int heads, int policy,
-                                 void* out, int dtype, hipStream_t st);
-
 template <typename E>
 static int xa_v1_launch(psg_ctx* ctx, const void* q, const void* k, const void* v, const uint64_t* bits, int words,
                         const int32_t* pair_index, int N, int P, int L, int nq, int heads, int empty_policy, void* out,
                         hipStream_t st) {
-  const int Lpad = (L + 31) & ~31;
-  const size_t lds = (size_t)Lpad * XA_KSTRIDE + (size_t)64 * (Lpad * 2 + 16) + 256 + (((size_t)N * words * 8 + 15) & ~(size_t)15);
+  const size_t lds = xattn_image_bytes(N, words, L);
   PSG_REQUIRE(lds <= 160 * 1024, PSG_ERR_UNSUPPORTED, "psg_qformer_cross_attn: L=%d needs %zu B of LDS (> 160 KiB)", L,
               lds);
-  const int NC = (Lpad / 32 + 3) / 4;                     // template parameter: staging passes / 128 keys
+  const int NC = (xattn_image(N, words, L).NT + 3) / 4;   // template parameter: staging passes / 128 keys
   PSG_REQUIRE(NC >= 1 && NC <= 4, PSG_ERR_UNSUPPORTED, "psg_qformer_cross_attn: L=%d (MFMA variant handles L <= 512)", L);
   const void* kfn = NC == 1 ? (const void*)cross_attn_mfma_kernel<E, 1>
                   : NC == 2 ? (const void*)cross_attn_mfma_kernel<E, 2>
@@ -478,7 +250,7 @@ static int xa_v1_launch(psg_ctx* ctx, const void* q, const void* k, const void* 
     }
   }
   const int64_t R = (int64_t)P * nq;
-  const int64_t ntile = nq == 33 ? (int64_t)P + (P + 31) / 32 : (R + 31) / 32;
+  const int64_t ntile = xattn_ntile(P, nq);
   // persistent grid: ~2 workgroups per CU, at least one tile per wave
   int blocks_per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
   int64_t G = ((int64_t)ctx->num_cu * blocks_per_cu + heads - 1) / heads;
@@ -499,10 +271,6 @@ static int xa_v1_launch(psg_ctx* ctx, const void* q, const void* k, const void* 
   PSG_CHECK_LAUNCH("psg_qformer_cross_attn");
   return PSG_OK;
 }
-
-int psg_cross_attn_f32_launch(const void* q, const void* k, const void* v, const uint64_t* bits, int words,
-                              const int32_t* pair_index, int N, int P, int L, int nq, int heads, int policy, void* out,
-                              hipStream_t st);
 
 extern "C" int psg_qformer_cross_attn(psg_ctx* ctx, const void* q, const void* k, const void* v, const uint64_t* bits,
                                       int words, const int32_t* pair_index, int N, int P, int L, int nq, int heads,
@@ -528,7 +296,7 @@ extern "C" int psg_qformer_cross_attn(psg_ctx* ctx, const void* q, const void* k
   if (variant == PSG_XATTN_MFMA && ctx->opt.xattn_dma && psg_cross_attn_dma_lds_bytes(N, words, L) <= 160 * 1024 &&
       L <= 384)
     return psg_cross_attn_dma_launch(ctx, q, k, v, bits, words, pair_index, N, P, L, nq, heads, empty_policy, out, dtype,
-                                     st);
+                                     st, nullptr, nullptr);
   PSG_DISPATCH_E16(dtype, "psg_qformer_cross_attn", return xa_v1_launch<E>(ctx, q, k, v, bits, words, pair_index, N, P, L, nq,
                                                                             heads, empty_policy, out, st));
 }

@@ -206,6 +206,118 @@ def test_cross_attn_mfma_matches_scalar_kernel(L, N, nq, policy):
         assert torch.isfinite(a).all() and err < 1.2e-2
 
 
+def _xattn_case(L, N, P, dtype):
+    """Inputs of test_cross_attn_mfma_vs_fp32_reference (objects 0 and 1 vanished: pair (0,0) has an empty union) in
+    `dtype`, 33 query rows per pair, 12 heads.  Returns q, k, v, bits, pair_index, pair masks [P, L]."""
+    dev = _dev()
+    g = torch.Generator(device="cpu").manual_seed(L * 1000 + N)
+    q = (torch.randn(P * 33, 768, generator=g) * 1.5).to(dev).to(dtype)
+    k = (torch.randn(L, 768, generator=g) * 1.5).to(dev).to(dtype)
+    v = torch.randn(L, 768, generator=g).to(dev).to(dtype)
+    om = torch.rand(N, L, generator=g) < 0.15
+    om[0] = False
+    if N > 2:
+        om[1] = False
+    words = (L + 63) // 64
+    bits_np = np.zeros((N, words * 64), dtype=np.uint8)
+    bits_np[:, :L] = om.numpy()
+    bits = torch.from_numpy(np.packbits(bits_np, axis=-1, bitorder="little").view(np.int64).reshape(N, words)).to(dev)
+    pair_index = torch.arange(P, dtype=torch.int32, device=dev)
+    pm = (om[:, None, :] | om[None, :, :]).reshape(N * N, L)[:P].to(dev)
+    return q, k, v, bits, pair_index, pm
+
+
+def _xattn_rel(a, b):
+    """The metric of test_cross_attn_mfma_matches_scalar_kernel: max |a - b| / (1 + |b|)."""
+    a, b = a.float(), b.float()
+    assert torch.isfinite(a).all()
+    return ((a - b).abs() / (1.0 + b.abs())).max().item()
+
+
+@pytest.mark.parametrize("L,N,P", [(288, 5, 25), (320, 3, 9)])
+def test_cross_attn_three_key_chunks_on_the_dma_kernel(L, N, P):
+    """257 <= L <= 320 (three chunks of 128 keys, eight waves) on the LDS-DMA kernel: bit-equal to the first generation,
+    close to the fp32 restatement and to the scalar kernel.  L = 320 is the last geometry whose K/V image leaves room for
+    the DMA slots; the indexed entry point, which only the LDS-DMA kernel serves, proves that it ran."""
+    from openpsg_amd import ops, _lib
+    heads = 12
+    q, k, v, bits, pair_index, pm = _xattn_case(L, N, P, torch.bfloat16)
+    import ctypes
+    lds_bytes = _lib.load().psg_cross_attn_dma_lds_bytes   # int (int N, int words, int L): the dispatcher's own formula
+    lds_bytes.argtypes, lds_bytes.restype = [ctypes.c_int] * 3, ctypes.c_int
+    lds = lds_bytes(N, bits.shape[1], L)
+    print(f"L={L} N={N}: LDS-DMA kernel needs {lds} B of LDS")
+    assert lds <= 160 * 1024
+    if L == 320:                                                   # one more 32-key tile no longer fits
+        assert lds_bytes(N, (352 + 63) // 64, 352) > 160 * 1024
+    ref = _xattn_reference(q, k, v, pm, heads)
+    for pol in (_lib.PSG_EMPTY_UNIFORM, _lib.PSG_EMPTY_UNMASKED):
+        out_m = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol, variant=_lib.PSG_XATTN_MFMA)
+        out_1 = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol,
+                                       variant=_lib.PSG_XATTN_MFMA_V1)
+        out_s = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol,
+                                       variant=_lib.PSG_XATTN_SIMPLE)
+        out_i = ops.qformer_cross_attn_indexed(q, pair_index, q[::33].contiguous(), k, v, bits, pair_index, N, heads,
+                                               empty_policy=pol)
+        torch.cuda.synchronize()
+        assert out_i is not None, "the LDS-DMA kernel does not take this geometry"
+        assert torch.equal(out_m, out_1) and torch.equal(out_i, out_m)
+        r_m, r_1 = _xattn_rel(out_m, out_s), _xattn_rel(out_1, out_s)
+        print(f"L={L} policy {pol}: LDS-DMA vs scalar {r_m:.3e}, first generation vs scalar {r_1:.3e}")
+        assert r_m < 1.2e-2 and r_1 < 1.2e-2
+        if pol == _lib.PSG_EMPTY_UNIFORM:
+            e_m, e_1 = (out_m.float() - ref).abs().max().item(), (out_1.float() - ref).abs().max().item()
+            print(f"L={L}: LDS-DMA kernel err {e_m:.3e}, first-generation kernel err {e_1:.3e}")
+            assert e_m < 3e-2 and e_1 < 3e-2
+
+
+@pytest.mark.parametrize("L,N,P", [(40, 3, 9), (192, 7, 49)])
+def test_cross_attn_fp16_both_generations(L, N, P):
+    """fp16 storage on both matrix-core kernels (L = 40: padding keys in the only key tile): bit-equal to each other and
+    within the bf16 test's bound of the scalar kernel run in fp16."""
+    from openpsg_amd import ops, _lib
+    heads = 12
+    q, k, v, bits, pair_index, _ = _xattn_case(L, N, P, torch.float16)
+    for pol in (_lib.PSG_EMPTY_UNIFORM, _lib.PSG_EMPTY_UNMASKED):
+        out_m = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol, variant=_lib.PSG_XATTN_MFMA)
+        out_1 = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol,
+                                       variant=_lib.PSG_XATTN_MFMA_V1)
+        out_s = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, empty_policy=pol,
+                                       variant=_lib.PSG_XATTN_SIMPLE)
+        torch.cuda.synchronize()
+        assert out_m.dtype == torch.float16 and torch.equal(out_m, out_1)
+        r_m, r_1 = _xattn_rel(out_m, out_s), _xattn_rel(out_1, out_s)
+        print(f"fp16 L={L} policy {pol}: LDS-DMA vs scalar {r_m:.3e}, first generation vs scalar {r_1:.3e}")
+        assert r_m < 1.2e-2 and r_1 < 1.2e-2
+
+
+def test_cross_attn_dma_schedules_compute_the_same_bits():
+    """841 pairs at L = 96: 868 row tiles per head, which the default deals dynamically to ten waves per workgroup.  The
+    static deal, eight waves, ten waves dealt statically and write-back stores change which wave computes a unit and how
+    its rows are stored, never the arithmetic: every output equals the default bit for bit."""
+    from openpsg_amd import ops, _lib
+    heads, N, L = 12, 29, 96
+    q, k, v, bits, pair_index, _ = _xattn_case(L, N, N * N, torch.bfloat16)
+    out_s = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, variant=_lib.PSG_XATTN_SIMPLE)
+    want = ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, variant=_lib.PSG_XATTN_MFMA)
+    torch.cuda.synchronize()
+    assert _xattn_rel(want, out_s) < 1.2e-2
+    names = ("xattn_dynamic", "xattn_waves", "xattn_wt")
+    saved = {n: _lib.get_option(0, n) for n in names}
+    try:
+        for setting in ({"xattn_dynamic": 0}, {"xattn_waves": 0}, {"xattn_waves": 10, "xattn_dynamic": 0}, {"xattn_wt": 0}):
+            for n in names:
+                _lib.set_option(0, n, setting.get(n, saved[n]))
+            got = torch.full_like(q, float("nan"))
+            ops.qformer_cross_attn(q, k, v, bits, pair_index, N, 33, heads, out=got, variant=_lib.PSG_XATTN_MFMA)
+            torch.cuda.synchronize()
+            assert torch.equal(got, want), setting
+            assert _xattn_rel(got, out_s) < 1.2e-2, setting
+    finally:
+        for n in names:
+            _lib.set_option(0, n, saved[n])
+
+
 @pytest.mark.parametrize("K,S,heads", [(20, 46, 32), (3, 64, 4), (5, 33, 2), (1, 7, 1)])
 def test_prefill_attn_mfma_vs_scalar_kernel_and_fp32(K, S, heads):
     """psg_prefill_attn (matrix cores) against psg_llm_attn (scalar) and an fp32 torch causal attention on a
