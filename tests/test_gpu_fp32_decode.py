@@ -303,10 +303,76 @@ def test_split_products_in_both_operand_layouts_agree_with_the_reference():
         assert [int(t) for t in new[1][i] if t >= 0] == want[want >= 0].tolist()
 
 
-def test_fused_split_kernels_equal_the_separate_kernels_bit_for_bit():
-    """psg_rmsnorm_split / psg_rope_kvwrite_scaled / psg_silu_mul_split against psg_scale_rows_cols + psg_rmsnorm /
-    psg_rope_kvwrite / psg_silu_mul + psg_split_f16x3 on the prompt pass's shapes: identical bits (no GEMM involved)."""
+# (rows, hidden, inter) of the other widths openpsg_amd/llm.py admits to the fused kernels (hidden <= 8192, inter <= 16384):
+# 13B-class 5120 / 13824 at <= 64 rows (1024 threads per row, two chunks with a tail) and above (256 threads, five chunks),
+# 8192 / 14336 (1024 threads, two full chunks), a width one float4 past a chunk, and one far below every chunk
+OTHER_WIDTHS = [(20, 5120, 13824), (200, 5120, 13824), (64, 8192, 14336), (3, 4100, 4100), (70, 100, 36)]
+
+
+def _fused_split_kernels_at(rows, D, I):
+    """psg_rmsnorm_split (three segments; two planes at <= 64 rows; no delta, a dense one, three slices) and
+    psg_silu_mul_split (three segments, two planes, two slices) against the separate kernels at one (rows, hidden, inter).
+    Equal as fp16 values, like the prompt-pass cases below: where x * scale underflows fp32 (|x * scale| < 2^-149, which
+    silu(g) * u reaches for g near -88 and a small u) psg_split_f16x3 forms hi and lo from the unrounded product (one
+    fused operation each) and the fused SwiGLU kernel from the rounded one; both parts are zero either way, but the low
+    part's zero is -0 in the first and +0 in the second."""
     from openpsg_amd import ops
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(rows + D + I)
+    pw2 = lambda n: torch.exp2(torch.randint(-20, 4, (n,), generator=g, device=dev).float())   # noqa: E731
+    resid0 = torch.randn(rows, D, generator=g, device=dev)
+    w = 1.0 + 0.1 * torch.randn(D, generator=g, device=dev)
+    for slices in (None, 1, 3):
+        y, rs, cs = torch.randn(slices or 1, rows, D, generator=g, device=dev) * 1e3, pw2(rows), pw2(D)
+        ysum = y[0].clone()
+        for s in range(1, y.shape[0]):
+            ysum = ysum + y[s]
+        ra = resid0.clone()
+        n = torch.empty_like(ra)
+        ops.rmsnorm(ra, ops.scale_rows_cols(ysum.clone(), rs, cs) if slices else None, w, 1e-5, n)
+        for planes in (3, 2) if rows <= 64 else (3,):
+            rb = resid0.clone()
+            yb = y[0].clone() if slices == 1 else y.clone()
+            a, inv = ops.split_f16x3(n) if planes == 3 else ops.split_f16x2(n)
+            b, binv = ops.rmsnorm_split(rb, ops.Scaled(yb, rs, cs) if slices else None, w, 1e-5, planes=planes)
+            assert torch.equal(ra, rb) and torch.equal(a, b) and torch.equal(inv, binv), (rows, D, slices, planes)
+    for slices in (1, 2):
+        y, rs, cs = torch.randn(slices, rows, 2 * I, generator=g, device=dev) * 1e3, pw2(rows), pw2(2 * I)
+        act = torch.empty(rows, I, device=dev)
+        ops.silu_mul(ops.scale_rows_cols(y[0] + y[1] if slices == 2 else y[0].clone(), rs, cs), act)
+        for planes in (3, 2):
+            a, inv = ops.split_f16x3(act) if planes == 3 else ops.split_f16x2(act)
+            b, binv = ops.silu_mul_split(ops.Scaled(y[0].clone() if slices == 1 else y.clone(), rs, cs), I, planes=planes)
+            assert torch.equal(a, b) and torch.equal(inv, binv), (rows, I, slices, planes)
+
+
+def test_fused_split_kernels_refuse_wider_rows():
+    """hidden 8196 (> 8192) and inter 16388 (> 16384) are outside the fused kernels' register budgets: refused with
+    PSG_ERR_UNSUPPORTED (-2), the residual stream untouched."""
+    from openpsg_amd import ops
+    from openpsg_amd._lib import PsgHipError
+    dev = "cuda:0"
+    resid = torch.full((3, 8196), -1234.5, device=dev)
+    for planes in (3, 2):
+        with pytest.raises(PsgHipError, match="status -2"):
+            ops.rmsnorm_split(resid, None, torch.ones(8196, device=dev), 1e-5, planes=planes)
+    y = torch.ones(3, 2 * 16388, device=dev)
+    for planes in (3, 2):
+        with pytest.raises(PsgHipError, match="status -2"):
+            ops.silu_mul_split(ops.Scaled(y, torch.ones(3, device=dev), torch.ones(2 * 16388, device=dev)), 16388, planes=planes)
+    torch.cuda.synchronize()
+    assert bool((resid == -1234.5).all())
+
+
+@pytest.mark.parametrize("shape", [None] + OTHER_WIDTHS, ids=lambda s: "prompt-pass" if s is None else "x".join(map(str, s)))
+def test_fused_split_kernels_equal_the_separate_kernels_bit_for_bit(shape):
+    """psg_rmsnorm_split / psg_rope_kvwrite_scaled / psg_silu_mul_split against psg_scale_rows_cols + psg_rmsnorm /
+    psg_rope_kvwrite / psg_silu_mul + psg_split_f16x3 on the prompt pass's shapes: identical bits (no GEMM involved);
+    RMSNorm and SwiGLU also at the other admitted widths (OTHER_WIDTHS)."""
+    from openpsg_amd import ops
+    if shape is not None:
+        _fused_split_kernels_at(*shape)
+        return
     dev = "cuda:0"
     g = torch.Generator(device=dev).manual_seed(11)
     rows, D, I, heads, ctx = 200, 4096, 11008, 32, 64

@@ -130,13 +130,30 @@ def test_engine_streams_fp16_valued_weights_as_fp16(dtype):
     assert np.array_equal(outs_m[0], outs_m[1])
 
 
-def test_two_plane_rmsnorm_equals_the_row_kernel_followed_by_the_split_bit_for_bit():
+# (rows, hidden, inter) of the other widths openpsg_amd/llm.py admits (tests/test_gpu_fp32_decode.py: OTHER_WIDTHS)
+OTHER_WIDTHS = [(20, 5120, 13824), (200, 5120, 13824), (64, 8192, 14336), (3, 4100, 4100), (70, 100, 36)]
+
+
+def test_two_plane_rmsnorm_refuses_hidden_8196():
+    from openpsg_amd import ops
+    from openpsg_amd._lib import PsgHipError
+    resid = torch.full((3, 8196), -1234.5, device=DEV)
+    with pytest.raises(PsgHipError, match="status -2"):
+        ops.rmsnorm_split2(resid, None, torch.ones(8196, device=DEV), 1e-5)
+    torch.cuda.synchronize()
+    assert bool((resid == -1234.5).all())
+
+
+@pytest.mark.parametrize("shapes,slices", [(((20, 4096, 11008), (32, 4096, 11008), (3, 512, 1024), (7, 1024, 2816)), (0, 1, 4, 16))]
+                         + [((s,), (0, 1, 16)) for s in OTHER_WIDTHS],
+                         ids=["decode-steps"] + ["x".join(map(str, s)) for s in OTHER_WIDTHS])
+def test_two_plane_rmsnorm_equals_the_row_kernel_followed_by_the_split_bit_for_bit(shapes, slices):
     """psg_rmsnorm_split2 (decode steps: fp32 rows, fp32 split-K slices) against psg_rmsnorm + psg_split_f16x2."""
     from openpsg_amd import ops
     g = torch.Generator(device=DEV).manual_seed(5)
-    for rows, D, I in ((20, 4096, 11008), (32, 4096, 11008), (3, 512, 1024), (7, 1024, 2816)):
+    for rows, D, I in shapes:
         w = 1.0 + 0.1 * torch.randn(D, generator=g, device=DEV)
-        for S in (0, 1, 4, 16):
+        for S in slices:
             resid = torch.randn(rows, D, generator=g, device=DEV) * 3
             delta = ops.Partials(torch.randn(S, rows, D, generator=g, device=DEV).contiguous()) if S else None
             ra, rb = resid.clone(), resid.clone()
