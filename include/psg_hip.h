@@ -72,8 +72,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *        psg_prefill_attn_rope_gqa, psg_decode_attn_gqa added
  *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added
  *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added
- *   605  training branch in bf16: psg_train_bf16_* added */
-#define PSG_ABI_VERSION 605
+ *   605  training branch in bf16: psg_train_bf16_* added
+ *   606  MXFP4-quantised LLM weights: psg_split_gemm_w4(_plan), psg_skinny_gemm_w4(_plan) added */
+#define PSG_ABI_VERSION 606
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -368,6 +369,23 @@ int psg_split_gemm_w8(psg_ctx*, const void* x2, const float* inv_scale, const vo
 int psg_skinny_gemm_w8_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
 int psg_skinny_gemm_w8(psg_ctx*, const void* x, const void* w8, const float* col_scale, float* part, int M, int N, int K,
                        int slots, int dtype, int mode, void* stream);
+/* The same projections over an MXFP4-quantised weight (OCP Microscaling: E2M1 elements, one E8M0 exponent per
+ * 32): W'[n][k] = e2m1(w4[n][k]) * 2^(e[n][k / 32] - 127) * col_scale[n] (openpsg_amd/weights.py quantize_mxfp4_rows).  w4 is
+ * uint8 [N][K / 2], the low nibble the even k (any nibble is accepted); col_scale is any finite fp32 [N].  The block
+ * exponents come RE-LAID-OUT for the kernel's K step of 256: e_img uint8 [K / 256][N][2][4], byte [h][j] = e[n][8 t + 2 j +
+ * h] of unit t (ops.mxfp4_exp_image), every byte >= 114 so that the fp16 widening never meets a subnormal.  4.25 bits per
+ * weight stream from HBM ONCE per call; two nibbles and their block scale are widened exactly to the x operand's 16-bit
+ * type by one conversion instruction, multiplied on the 16-bit matrix cores with fp32 accumulation; col_scale (and the
+ * PAIR form's inv_scale) are applied once, in fp32, at the slice store.
+ *   psg_split_gemm_w4 (fp32s): x2 / inv_scale as psg_split_gemm_w16's;  psg_skinny_gemm_w4: x [M][K] bf16 / fp16.
+ * M <= 32, N % 16 == 0, K % 256 == 0 (one K step is a 128-byte fp4 row piece), else PSG_ERR_UNSUPPORTED.  Slices, plan
+ * entries and modes as the w8 family's. */
+int psg_split_gemm_w4_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const void* w4, const void* e_img, const float* col_scale,
+                      float* part, int M, int N, int K, int slots, int mode, void* stream);
+int psg_skinny_gemm_w4_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
+int psg_skinny_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img, const float* col_scale, float* part, int M,
+                       int N, int K, int slots, int dtype, int mode, void* stream);
 /* psg_skinny_gemm(PSG_F32) over weights STORED as fp16: x fp32 [M][K], w fp16 [N][K], the same plan (psg_skinny_gemm_plan
  * with PSG_F32), the same f32 matrix instructions on the exactly widened weights in the same order - part is bit-identical
  * to the fp32-weight call on w.float(), at half the weight bytes.  For weights that ARE fp16 values: the reference's LLM is

@@ -233,7 +233,10 @@ class RelationTransformerHeadV4(nn.Module):
                                                # fp32 scale per output row (weights.quantize_fp8_rows): decode
                                                # steps of <= 32 rows stream 1 byte per weight.  The model IS the quantised one
                                                # (W' = q s) on every path; an FP8 checkpoint is taken as it is
-                 llm_quantize_lm_head=False,   # 'fp8': the lm_head as well (never the embedding, norms, language_projection)
+                                               # 'mxfp4': OCP Microscaling FP4, two E2M1 codes per byte + one exponent byte per 32 k
+                                               # + one fp32 scale per row (weights.quantize_mxfp4_rows): 4.25 bits
+                                               # per weight in those steps, W' = fp4(q) 2^(e - 127) s likewise
+                 llm_quantize_lm_head=False,   # quantised: the lm_head as well (never the embedding, norms, language_projection)
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -244,13 +247,13 @@ class RelationTransformerHeadV4(nn.Module):
                               "offered: 'If use fp16, the loss will be nan', V4)")
         self.train_precision = train_precision
         self._train_llm_copy = None
-        if llm_weight_quant not in (None, "fp8"):
-            raise PsgHipError(f"llm_weight_quant must be None or 'fp8', got {llm_weight_quant!r}")
+        if llm_weight_quant not in (None, "fp8", "mxfp4"):
+            raise PsgHipError(f"llm_weight_quant must be None, 'fp8' or 'mxfp4', got {llm_weight_quant!r}")
         if llm_weight_quant is not None and "binary" not in rel_cls_type:
             raise PsgHipError(f"llm_weight_quant={llm_weight_quant!r} quantises the LLM; rel_cls_type={rel_cls_type!r} has no "
                               "LLM stage")
         if llm_quantize_lm_head and llm_weight_quant is None:
-            raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8'")
+            raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4'")
         self.llm_weight_quant = llm_weight_quant
         self.llm_quantize_lm_head = bool(llm_quantize_lm_head)
         if rel_cls_type not in REL_CLS_TYPES:
@@ -452,7 +455,9 @@ class RelationTransformerHeadV4(nn.Module):
                    not (".layers." in k and int(k.split(".layers.")[1].split(".")[0]) >= n_layers)]
         if missing:
             raise PsgHipError(f"LLM weights missing {len(missing)} tensors, e.g. {missing[:3]}")
-        wrong = [(k, tuple(weights[k].shape), need[k]) for k in need if k in weights and tuple(weights[k].shape) != need[k]]
+        def stored(k):                                  # an MXFP4 matrix [N, K] comes as two codes per byte: [N, K / 2]
+            return (need[k][0], need[k][1] // 2) if k + "_bexp" in weights else need[k]
+        wrong = [(k, tuple(weights[k].shape), stored(k)) for k in need if k in weights and tuple(weights[k].shape) != stored(k)]
         if wrong:                                       # e.g. a grouped-query checkpoint under a multi-head config
             raise PsgHipError(f"LLM weights of the wrong shape ({len(wrong)}), e.g. {wrong[:2]} "
                               f"({self.cfg.llm.heads} query / {self.cfg.llm.n_kv_heads} key-value heads)")
@@ -466,12 +471,13 @@ class RelationTransformerHeadV4(nn.Module):
     def quantize_llm_weights(self, weights: dict) -> dict:
         """What `load_llm_weights` hands the decode engine: with llm_weight_quant='fp8' every q/k/v/o/gate/up/down matrix
         of the kept layers (+ the lm_head with llm_quantize_lm_head) as (e4m3fn bytes under its name, fp32 row scales
-        under name + '_scale'); matrices that already come as such a pair are kept.  Otherwise a plain copy of the dict."""
+        under name + '_scale'), with 'mxfp4' as (fp4 nibbles, name + '_bexp', name + '_scale'); matrices that already come
+        quantised are kept.  Otherwise a plain copy of the dict."""
         if self.llm_weight_quant is None:
             return dict(weights)
         from .weights import quantize_llm_weights
         n_layers = self.cfg.llm.layers if self.llm_truncate_num <= 0 else self.llm_truncate_num
-        return quantize_llm_weights(weights, n_layers, self.llm_quantize_lm_head)
+        return quantize_llm_weights(weights, n_layers, self.llm_quantize_lm_head, self.llm_weight_quant)
 
     def _param_version(self) -> int:
         """Sum of the parameters' in-place version counters: every optimizer step (and any other in-place update of a

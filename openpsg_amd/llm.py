@@ -82,6 +82,13 @@ def _split_mm(a3, w3, plan=None, out_dtype=torch.float32):
     return y
 
 
+# MXFP4 shapes (N, K) that stream as their exact FP8 image instead of as nibbles (acceptance rule): a shape goes
+# here when tools/w4_bench.py measured psg_gemm_w4.hip's range of times NOT wholly below psg_gemm_w8.hip's on the same W'.
+# "pair": fp32s engines (psg_split_gemm_w*), "single": 16-bit engines (psg_skinny_gemm_w*).  The image costs a byte per
+# weight and is kept for these shapes only
+W4_STREAM_AS_FP8 = {"pair": frozenset(), "single": frozenset()}
+
+
 def _plan_split_mm(rows, w3, out_dtype=torch.float32, k3=False, pool=None):
     """The form the library product of this shape runs in: a pure function of the shape (`_SPLIT_PLAN_TABLE`; 'whole' for
     every shape the table does not name), unless PSG_PLAN=measure."""
@@ -244,8 +251,15 @@ class LlamaDecodeEngine:
         # model's weight is W' = float32(q) * s.  W' goes under the existing key in the engine's dtype - every path not
         # built for the byte stream computes the same model on the kernels it has - and `_w8` keeps (q, s) for the decode
         # steps of <= 32 rows, `_w8h` an exact fp16 copy of q for the fp32s prompt pass (its two-plane operand x fp16 matrix)
-        from .weights import SCALE_SUFFIX, dequantize_fp8_rows
+        # MXFP4-quantised matrices: `name` holds two fp4 codes per byte, `name + '_bexp'` the block exponents e,
+        # `name + '_scale'` s; W' = fp4(q) 2^(e - 127) s goes under the existing key likewise, `_w4` keeps (q, the kernel's
+        # exponent image, s) for the decode steps of <= 32 rows, `_w4h` the exact fp16 image of W' / s for the fp32s prompt
+        # pass.  A shape of W4_STREAM_AS_FP8 (measured slower as nibbles than as bytes) gets its exact FP8 image in `_w8`
+        # as well and streams through the FP8 kernels: the same W' bit for bit
+        from .weights import (BEXP_SUFFIX, SCALE_SUFFIX, dequantize_fp8_rows, dequantize_mxfp4_rows, mxfp4_as_fp8_rows,
+                              quant_format, _mxfp4_unscaled)
         self._w8, self._w8h = {}, {}
+        self._w4, self._w4h = {}, {}
 
         def matrix(*keys):
             """The (row-concatenated) matrix of `keys` in the engine's dtype; registers its byte stream when every part
@@ -255,10 +269,27 @@ class LlamaDecodeEngine:
                 raise PsgHipError(f"{keys}: some parts are FP8-quantised and some are not")
             if not quant[0]:
                 return act(torch.cat([weights[k] for k in keys], 0) if len(keys) > 1 else weights[keys[0]])
+            fmts = {quant_format(weights, k) for k in keys}
+            if len(fmts) > 1:
+                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
             q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
             sc = torch.cat([weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1) for k in keys], 0)
             if sc.numel() != q.shape[0]:
                 raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
+            if fmts == {"mxfp4"}:
+                e = torch.cat([weights[k + BEXP_SUFFIX].to(self.device) for k in keys], 0).contiguous()
+                N, K = q.shape[0], 2 * q.shape[1]
+                if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
+                    raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
+                                      "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
+                sc = sc.contiguous()
+                w = dequantize_mxfp4_rows(q, e, sc, dtype).contiguous()
+                self._w4[w.data_ptr()] = (q, ops.mxfp4_exp_image(e) if K % 256 == 0 else None, sc)
+                if prefill_split and dtype == torch.float32:
+                    self._w4h[w.data_ptr()] = _mxfp4_unscaled(q, e).to(torch.float16)
+                if (N, K) in W4_STREAM_AS_FP8["pair" if dtype == torch.float32 else "single"]:
+                    self._w8[w.data_ptr()] = mxfp4_as_fp8_rows(q, e, sc)
+                return w
             w = dequantize_fp8_rows(q, sc, dtype).contiguous()
             self._w8[w.data_ptr()] = (q, sc.contiguous())
             if prefill_split and dtype == torch.float32:
@@ -274,6 +305,8 @@ class LlamaDecodeEngine:
             p = f"language_model.model.layers.{l}."
             for n, rows_ in (("q", m.hidden), ("k", m.kv_dim), ("v", m.kv_dim)):
                 shp = tuple(weights[p + f"self_attn.{n}_proj.weight"].shape)
+                if p + f"self_attn.{n}_proj.weight" + BEXP_SUFFIX in weights:      # (MXFP4: two codes per byte)
+                    shp = (shp[0], 2 * shp[1])
                 if shp != (rows_, m.hidden):
                     raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
                                       f"({m.heads} query / {m.n_kv_heads} key-value heads of 128)")
@@ -284,10 +317,16 @@ class LlamaDecodeEngine:
                 wdown=matrix(p + "mlp.down_proj.weight"),
                 ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
         layer_w = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
-        n_q = sum(t.data_ptr() in self._w8 for t in layer_w)
+        n_q4 = sum(t.data_ptr() in self._w4 for t in layer_w)
+        n_q = sum(t.data_ptr() in self._w8 and t.data_ptr() not in self._w4 for t in layer_w)
+        if n_q and n_q4:
+            raise PsgHipError(f"{n_q} decoder-layer matrices are FP8-quantised and {n_q4} MXFP4-quantised: one format")
         if 0 < n_q < len(layer_w):
             raise PsgHipError(f"{n_q} of the {len(layer_w)} decoder-layer matrices are FP8-quantised: all or none")
+        if 0 < n_q4 < len(layer_w):
+            raise PsgHipError(f"{n_q4} of the {len(layer_w)} decoder-layer matrices are MXFP4-quantised: all or none")
         self._w8_layers = n_q > 0                                # every decoder-layer matrix streams as bytes
+        self._w4_layers = n_q4 > 0                               # ... as nibbles (or, per shape, as their exact FP8 image)
         self.use_skinny = True
         self.prefill_split = bool(prefill_split) and dtype == torch.float32
         # fp32 engines: are the projection weights fp16 VALUES?  The reference's LLM is the frozen Llama-2-7b-hf checkpoint
@@ -305,7 +344,7 @@ class LlamaDecodeEngine:
         if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
             tensors = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
             for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
-                if t.data_ptr() in self._w8:                    # (has its byte stream: never counted, `_w16_all` stays false)
+                if t.data_ptr() in self._w8 or t.data_ptr() in self._w4:   # (has its byte stream: never counted, `_w16_all` stays false)
                     continue
                 h = t.half()
                 if torch.equal(h.float(), t):
@@ -316,7 +355,7 @@ class LlamaDecodeEngine:
             # weight next to the fp32 copy the decode steps stream: 40 GB + 27 GB for Llama-2-7B, of 288 GB)
             for L in self.layers:
                 for k in ("wqkv", "wo", "wgu", "wdown"):
-                    if L[k].data_ptr() not in self._w8:         # (quantised: the two-plane prompt pass on `_w8h`, no split copy)
+                    if L[k].data_ptr() not in self._w8 and L[k].data_ptr() not in self._w4:   # (quantised: the two-plane prompt pass on `_w8h` / `_w4h`, no split copy)
                         L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
         # row_invariant (fp32s engines): the prompt pass's projections and the language projection on psg_dense_gemm - one
         # k-ordered accumulation per output element whatever the row count of the call - instead of the library GEMM, whose
@@ -449,6 +488,14 @@ class LlamaDecodeEngine:
                 x2, inv = ops.split_f16x2(x)
                 return ops.split_gemm_w8(x2, inv, *w8)
             return ops.skinny_gemm_w8(x, *w8)
+        w4 = self._w4.get(w.data_ptr()) if self._w4 else None
+        if (w4 is not None and w4[1] is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
+                and w.shape[0] % 16 == 0 and (self.prefill_split or x.dtype != torch.float32)):
+            # MXFP4-quantised matrix, <= 32 rows: 4.25 bits per weight (psg_gemm_w4.hip; K % 256 == 0 or there is no image)
+            if x.dtype == torch.float32:
+                x2, inv = ops.split_f16x2(x)
+                return ops.split_gemm_w4(x2, inv, *w4)
+            return ops.skinny_gemm_w4(x, *w4)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
             if wh is not None and self.prefill_split:         # fp32s: two fp16 products of the split rows, 2 bytes per weight
@@ -491,7 +538,7 @@ class LlamaDecodeEngine:
         rows = int(rows)
         if not self.use_skinny or rows > 32:
             return True
-        if self._can_w16(rows) or self._can_w8(rows):          # psg_split_gemm_w16 / _w8 for every projection
+        if self._can_w16(rows) or self._can_w8(rows) or self._can_w4(rows):   # psg_split_gemm_w16 / _w8 / _w4 for every projection
             return False
         L = self.layers[0] if self.layers else None
         ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
@@ -603,7 +650,7 @@ class LlamaDecodeEngine:
         m = self.cfg.llm
         rows, D = resid.shape
         plan = _plan_split_mm if self.plan_split else (lambda r, w, k3=False: None)
-        planes = 2 if self._w16_all or self._w8_layers else 3
+        planes = 2 if self._w16_all or self._w8_layers or self._w4_layers else 3
         if planes == 3:
             weight = lambda L, k: L[k + "_s"]                                               # noqa: E731
             mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
@@ -611,6 +658,8 @@ class LlamaDecodeEngine:
         else:
             if self._w8_layers:                                 # W' = q s: the exact fp16 image of q, s as the column scale
                 weight = lambda L, k: (self._w8h[L[k].data_ptr()], self._w8[L[k].data_ptr()][1])   # noqa: E731
+            elif self._w4_layers:                               # W' = (fp4(q) 2^(e - 127)) s: likewise
+                weight = lambda L, k: (self._w4h[L[k].data_ptr()], self._w4[L[k].data_ptr()][2])   # noqa: E731
             else:
                 weight = lambda L, k: (self._w16[L[k].data_ptr()], self._ones(L[k].shape[0]))   # noqa: E731
             split = ops.split_f16x2
@@ -652,7 +701,7 @@ class LlamaDecodeEngine:
 
     def _can_persist(self, rows, slot):
         m = self.cfg.llm
-        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32 and not self._w8
+        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32 and not self._w8 and not self._w4
                 and self.kv is None                            # the persistent decoder layer is multi-head only
                 and ops.decode_layer_supported(rows, m.hidden, m.inter, m.heads, self.dtype, self.device))
 
@@ -730,29 +779,55 @@ class LlamaDecodeEngine:
         """`_decode_step_w16` over FP8-quantised decoder layers: 1 byte per weight from HBM, the same two fp16 products per
         projection on the exactly widened bytes, the per-row weight scale applied in fp32 where a slice is stored.  The
         lm_head runs on the stream ITS tensor has: bytes, fp16 values or fp32."""
+        return self._decode_step_wq(st)
+
+    def _can_w4(self, rows):
+        """fp32s decode steps over MXFP4-quantised decoder layers: every projection as psg_split_gemm_w4 - or, for a shape
+        of W4_STREAM_AS_FP8, as psg_split_gemm_w8 on its exact FP8 image - the row kernels writing the two-plane operand
+        directly (`_decode_step_w4`)."""
         m = self.cfg.llm
-        x, w8 = st["x"], self._w8
+        return (self._w4_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
+                and self.dtype == torch.float32 and m.hidden % 256 == 0 and m.inter % 256 == 0 and m.inter <= 16384
+                and m.hidden <= 8192 and m.vocab % 16 == 0)
+
+    def _decode_step_w4(self, st):
+        """`_decode_step_w8` over MXFP4-quantised decoder layers: 4.25 bits per weight from HBM, nibbles and block scale
+        widened exactly to fp16 in registers, the same two fp16 products per projection."""
+        return self._decode_step_wq(st)
+
+    def _split_mm_q(self, a2, inv, w):
+        """The pair-form projection of a quantised matrix on the stream it has: FP8 bytes (an FP8 matrix, or the exact FP8
+        image of an MXFP4 shape that streams faster so) or MXFP4 nibbles."""
+        w8 = self._w8.get(w.data_ptr())
+        if w8 is not None:
+            return ops.split_gemm_w8(a2, inv, *w8)
+        return ops.split_gemm_w4(a2, inv, *self._w4[w.data_ptr()])
+
+    def _decode_step_wq(self, st):
+        m = self.cfg.llm
+        x, mm = st["x"], self._split_mm_q
         K, D = x.shape
         att = torch.empty((K, D), device=self.device, dtype=torch.float32)
         a2, inv = ops.rmsnorm_split2(x, None, self.layers[0]["ln1"], m.rms_eps)
         for l, L in enumerate(self.layers):
-            qkv = ops.split_gemm_w8(a2, inv, *w8[L["wqkv"].data_ptr()])
+            qkv = mm(a2, inv, L["wqkv"])
             ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
                             st["vc"][l], att, kv_heads=self.kv)
             a2o, invo = ops.split_f16x2(att)
-            o = ops.split_gemm_w8(a2o, invo, *w8[L["wo"].data_ptr()])
+            o = mm(a2o, invo, L["wo"])
             a2, inv = ops.rmsnorm_split2(x, o, L["ln2"], m.rms_eps)
-            gu = ops.split_gemm_w8(a2, inv, *w8[L["wgu"].data_ptr()])
+            gu = mm(a2, inv, L["wgu"])
             act = torch.empty((K, m.inter), device=self.device, dtype=torch.float32)
             ops.silu_mul(gu, act)
             a2a, inva = ops.split_f16x2(act)
-            d = ops.split_gemm_w8(a2a, inva, *w8[L["wdown"].data_ptr()])
+            d = mm(a2a, inva, L["wdown"])
             if l + 1 < len(self.layers):
                 a2, inv = ops.rmsnorm_split2(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
         head = self.lm_head.data_ptr()
-        if head in w8 and self.lm_head.shape[1] % 128 == 0:
+        if ((head in self._w8 and self.lm_head.shape[1] % 128 == 0)
+                or (head in self._w4 and self._w4[head][1] is not None)):
             a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
-            return ops.split_gemm_w8(a2, inv, *w8[head])
+            return mm(a2, inv, self.lm_head)
         if head in self._w16:
             a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
             return ops.split_gemm_w16(a2, inv, self._w16[head])
@@ -763,7 +838,7 @@ class LlamaDecodeEngine:
     def _can_fuse(self, rows):
         m = self.cfg.llm
         D = m.hidden
-        return (bool(self.fuse_rowops) and not self._w8 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
+        return (bool(self.fuse_rowops) and not self._w8 and not self._w4 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
                 and self.resid_dtype == self.dtype and rows <= 32 and D in (1024, 4096) and m.inter >= 1024 and m.inter % 64 == 0
                 and m.vocab >= 1024 and m.vocab % 16 == 0)
 
@@ -1059,7 +1134,8 @@ class LlamaDecodeEngine:
         persist = hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
         w16 = not persist and self._can_w16(st["x"].shape[0])
         w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])
-        fused = not persist and not w16 and not w8 and self._can_fuse(st["x"].shape[0]) and hi > lo
+        w4 = not persist and not w16 and not w8 and self._can_w4(st["x"].shape[0])
+        fused = not persist and not w16 and not w8 and not w4 and self._can_fuse(st["x"].shape[0]) and hi > lo
         if persist:                                            # one counter block per layer launch, zeroed once per call
             per_step = ops.decode_layer_counters(self.device) * len(self.layers)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
@@ -1076,6 +1152,8 @@ class LlamaDecodeEngine:
                 logits = self._decode_step_w16(st)
             elif w8:
                 logits = self._decode_step_w8(st)
+            elif w4:
+                logits = self._decode_step_w4(st)
             elif fused:
                 logits = self._decode_step_fused(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             else:

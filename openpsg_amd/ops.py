@@ -825,6 +825,64 @@ def skinny_gemm_w8(x, w8, col_scale, mode=0) -> Partials:
     return Partials(part)
 
 
+def mxfp4_exp_image(e) -> torch.Tensor:
+    """The block exponents e uint8 [N, K / 32] of an MXFP4 matrix (weights.quantize_mxfp4_rows), K % 256 == 0, re-laid-out
+    for psg_gemm_w4.hip's K step of 256: uint8 [K / 256, N, 2, 4] with [t, n, h, j] = e[n, 8 t + 2 j + h].  The exponents
+    of 32 consecutive rows of one step are then 256 contiguous bytes (one LDS-DMA per wave) and the four a lane needs
+    one dword."""
+    N, B = e.shape
+    if e.dtype != torch.uint8 or B % 8:
+        raise PsgHipError(f"mxfp4_exp_image: e must be uint8 [N, K / 32] with K % 256 == 0, got {e.dtype} {tuple(e.shape)}")
+    return e.reshape(N, B // 8, 4, 2).permute(1, 0, 3, 2).contiguous()
+
+
+def _w4_args(name, w4, e_img, col_scale, K):
+    if w4.dtype != torch.uint8 or w4.dim() != 2 or w4.shape[1] * 2 != K:
+        raise PsgHipError(f"{name}: w4 must be fp4 nibbles uint8 [N, {K // 2}], got {w4.dtype} {tuple(w4.shape)}")
+    N = w4.shape[0]
+    if K % 256 == 0 and (e_img.dtype != torch.uint8 or tuple(e_img.shape) != (K // 256, N, 2, 4) or not e_img.is_contiguous()):
+        raise PsgHipError(f"{name}: e_img must be mxfp4_exp_image(e): uint8 [{K // 256}, {N}, 2, 4], got {e_img.dtype} "
+                          f"{tuple(e_img.shape)}")
+    if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (N,):
+        raise PsgHipError(f"{name}: col_scale must be fp32 [{N}], got {col_scale.dtype} {tuple(col_scale.shape)}")
+    return N
+
+
+def split_gemm_w4(x2, inv_scale, w4, e_img, col_scale, mode=0) -> Partials:
+    """`split_gemm_w8` over an MXFP4-quantised weight W' = fp4(w4) * 2^(e - 127) * col_scale[:, None]
+    (weights.quantize_mxfp4_rows; `e_img` = mxfp4_exp_image(e)): 4.25 bits per weight from HBM, widened exactly to fp16 with
+    the block scale in registers; fp32 slices [S, M, N] of (xh . w + xl . w) * inv_scale * col_scale (psg_split_gemm_w4).
+    K % 256 == 0.  mode 1 / 2: slab-aligned / stream-K ranges, 0 = the library's estimate."""
+    import ctypes
+    lib, ctx, st = _env(x2)
+    _, M, K = x2.shape
+    assert x2.shape[0] == 2 and x2.dtype == torch.float16
+    N = _w4_args("split_gemm_w4", w4, e_img, col_scale, K)
+    s = ctypes.c_int(0)
+    check(lib.psg_split_gemm_w4_plan(ctx, M, N, K, int(mode), ctypes.byref(s)), "psg_split_gemm_w4_plan")
+    part = torch.empty((s.value, M, N), device=x2.device, dtype=torch.float32)
+    check(lib.psg_split_gemm_w4(ctx, _p(x2), _p(inv_scale, torch.float32), _p(w4, name="w4"), _p(e_img, name="e_img"),
+                                _p(col_scale), _p(part), M, N, K, s.value, int(mode), st), "psg_split_gemm_w4")
+    return Partials(part)
+
+
+def skinny_gemm_w4(x, w4, e_img, col_scale, mode=0) -> Partials:
+    """`skinny_gemm_w8` of <= 32 bf16 / fp16 rows over an MXFP4-quantised weight (see `split_gemm_w4`): fp32 slices
+    [S, M, N] of (x . w) * col_scale (psg_skinny_gemm_w4).  K % 256 == 0."""
+    import ctypes
+    lib, ctx, st = _env(x)
+    M, K = x.shape
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise PsgHipError(f"skinny_gemm_w4: x must be bf16 or fp16, got {x.dtype}")
+    N = _w4_args("skinny_gemm_w4", w4, e_img, col_scale, K)
+    s = ctypes.c_int(0)
+    check(lib.psg_skinny_gemm_w4_plan(ctx, M, N, K, _dt(x), int(mode), ctypes.byref(s)), "psg_skinny_gemm_w4_plan")
+    part = torch.empty((s.value, M, N), device=x.device, dtype=torch.float32)
+    check(lib.psg_skinny_gemm_w4(ctx, _p(x, name="x"), _p(w4, name="w4"), _p(e_img, name="e_img"), _p(col_scale), _p(part), M,
+                                 N, K, s.value, _dt(x), int(mode), st), "psg_skinny_gemm_w4")
+    return Partials(part)
+
+
 def batch_gemm(x, w, slab_rows=0, mode=0) -> Partials:
     """Decode-step projection for 33..160 rows (several images' pairs decoded together): fp32 split-K slices of x @ w.T
     like `skinny_gemm`'s, the weight streamed from HBM once (psg_batch_gemm; bf16 / fp16).

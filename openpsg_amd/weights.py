@@ -237,20 +237,136 @@ def is_quantized(weights: dict, key: str) -> bool:
     return key + SCALE_SUFFIX in weights
 
 
+def quant_format(weights: dict, key: str):
+    """None, 'fp8' or 'mxfp4': how the matrix `key` comes in `weights` (an MXFP4 matrix has its block exponents beside it)."""
+    if not is_quantized(weights, key):
+        return None
+    return "mxfp4" if key + BEXP_SUFFIX in weights else "fp8"
+
+
+# ---- MXFP4-quantised LLM matrices (DESIGN 14) -------------------------------------------------------------------------
+# OCP Microscaling FP4: E2M1 elements (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), one power-of-two exponent per block of 32
+# consecutive k, anchored to the row: a matrix is (q, e, s) = (uint8 [N, K / 2]: two codes per byte, the LOW nibble the
+# even k; uint8 [N, K / 32]: 127 + E_b - Emax[n], in 114..127; fp32 [N]: 2^Emax[n]) and its value is
+#     W'[n, k] = fp4(q[n, k]) * 2^(e[n, k // 32] - 127) * s[n].
+# E_b = floor(log2 max|block|) - 2 (the OCP rule: E2M1's largest binade is 2^2), floored at Emax[n] - 13 with Emax the
+# row's largest E_b, so that W' / s is a NORMAL fp16 number or zero and W' is exactly an FP8 model (mxfp4_as_fp8_rows).
+BEXP_SUFFIX = "_bexp"                                              # `<name>.weight` -> `<name>.weight_bexp`
+MXFP4_BLOCK = 32
+MXFP4_EXP_SPAN = 13                                                # a block's exponent lies at most this far below its row's
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)              # the magnitudes of codes 0..7; bit 3 is the sign
+
+
+def quantize_mxfp4_rows(W: torch.Tensor):
+    """W [N, K], K % 32 == 0 -> (q uint8 [N, K / 2], e uint8 [N, K / 32], s fp32 [N]) as defined above.  An element is the
+    nearest grid point to W / 2^E_b, ties to the even code, magnitudes above 6 saturate; a value that rounds to zero takes
+    code 0x0, never 0x8 (-0), so that quantising W' again returns the same codes.  An all-zero block takes the floor
+    exponent, an all-zero row Emax = 0.  Emax is not taken below -126 (s stays a normal fp32 number)."""
+    if W.dim() != 2 or W.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4_rows takes a matrix [N, K] with K % {MXFP4_BLOCK} == 0, got shape {tuple(W.shape)}")
+    N, K = W.shape
+    Wb = W.to(torch.float32).reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = Wb.abs().amax(dim=2)
+    nz = amax > 0
+    Eb = torch.frexp(amax)[1].to(torch.int32) - 3                  # amax = m 2^x, m in [0.5, 1): floor(log2) = x - 1
+    Eb = torch.where(nz, Eb, torch.full_like(Eb, -1000))
+    Emax = Eb.amax(dim=1)
+    Emax = torch.where(nz.any(dim=1), Emax, torch.zeros_like(Emax)).clamp_(min=-126)
+    Eb = torch.maximum(Eb, (Emax - MXFP4_EXP_SPAN)[:, None])
+    a = Wb.abs().to(torch.float64) * torch.exp2(-Eb.to(torch.float64))[:, :, None]      # exact: a power-of-two scale
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8)
+            + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = code + (((Wb < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.reshape(N, K // 2, 2)
+    q = code[:, :, 0] | (code[:, :, 1] << 4)
+    e = (127 + Eb - Emax[:, None]).to(torch.uint8)
+    s = torch.exp2(Emax.to(torch.float32))
+    return q.contiguous(), e.contiguous(), s
+
+
+def _mxfp4_unscaled(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """fp4(q) * 2^(e - 127) as fp32 [N, K] (exact)."""
+    N, Kh = q.shape
+    q = q.view(torch.uint8) if q.dtype != torch.uint8 else q
+    code = torch.stack((q & 0xF, q >> 4), dim=2).reshape(N, 2 * Kh).to(torch.int64)
+    grid = torch.tensor(MXFP4_GRID + tuple(-g for g in MXFP4_GRID), dtype=torch.float32, device=q.device)
+    bs = (e.to(torch.int32) << 23).view(torch.float32)             # 2^(e - 127), as the kernels build it
+    return (grid[code].reshape(N, -1, MXFP4_BLOCK) * bs[:, :, None]).reshape(N, 2 * Kh)
+
+
+def dequantize_mxfp4_rows(q: torch.Tensor, e: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """W' = (fp4(q) * 2^(e - 127)) * s[:, None] (the bracket is exact, then one fp32 rounding per element), then `dtype`."""
+    return (_mxfp4_unscaled(q, e) * s.to(torch.float32)[:, None]).to(dtype)
+
+
+def mxfp4_as_fp8_rows(q: torch.Tensor, e: torch.Tensor, s: torch.Tensor):
+    """The exact FP8 image of an MXFP4 matrix with e in 114..127: (e4m3fn bytes uint8 [N, K] of W' / s * 64, fp32 row scales
+    s / 64).  The values lie in 2^-8 .. 384 on e4m3fn's grid, so `dequantize_fp8_rows` of the pair is W' bit for bit."""
+    if int(e.min()) < 127 - MXFP4_EXP_SPAN or int(e.max()) > 127:
+        raise ValueError(f"mxfp4_as_fp8_rows: block exponents must lie in {127 - MXFP4_EXP_SPAN}..127")
+    q8 = (_mxfp4_unscaled(q, e) * 64.0).to(torch.float8_e4m3fn)
+    return q8.view(torch.uint8), s.to(torch.float32) / 64.0
+
+
+def _take_mxfp4(out: dict, path):
+    """The MXFP4 matrices of a checkpoint - `*.weight` uint8 [N, K / 2] (low nibble = even k) with a sibling `*.weight_scale`
+    uint8 [N, K / 32] (E8M0: the block's scale is 2^(byte - 127)) - row-anchored into the model above: s = 2^(largest
+    exponent byte of the row's non-zero blocks - 127) under name + '_scale', the bytes rebased to 127 = the row's largest
+    under name + '_bexp', all-zero blocks moved to the floor.  The value of every element is unchanged."""
+    from ._lib import PsgHipError
+    for ks in [k for k in out if k.endswith(".weight" + SCALE_SUFFIX)]:
+        kw = ks[:-len(SCALE_SUFFIX)]
+        w, sc = out.get(kw), out[ks]
+        if w is None or w.dtype != torch.uint8 or sc.dtype != torch.uint8:
+            continue
+        if w.dim() != 2 or sc.dim() != 2 or sc.shape[0] != w.shape[0]:
+            raise PsgHipError(f"{path}: MXFP4 tensor {kw}: weight {tuple(w.shape)} / weight_scale {tuple(sc.shape)} are not "
+                              "[N, K / 2] / [N, K / 32]")
+        N, K = w.shape[0], 2 * w.shape[1]
+        if K % MXFP4_BLOCK or sc.shape[1] * MXFP4_BLOCK != K:
+            raise PsgHipError(f"{path}: MXFP4 tensor {kw}: K = {K} with {sc.shape[1]} block exponents per row (K % "
+                              f"{MXFP4_BLOCK} == 0 and one exponent per {MXFP4_BLOCK} elements)")
+        lo, hi = w & 0xF, w >> 4
+        if bool(((lo == 8) | (hi == 8)).any()):
+            raise PsgHipError(f"{path}: MXFP4 tensor {kw} holds the code 0x8 (-0): not part of the model (re-quantising "
+                              "would not return it); write +0 (0x0)")
+        if bool((sc == 255).any()):
+            raise PsgHipError(f"{path}: MXFP4 tensor {kw}: weight_scale holds 0xFF (E8M0 NaN)")
+        nzb = (w.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK // 2) != 0).any(dim=2)          # (no 0x8: a zero block is zero bytes)
+        eb = sc.to(torch.int32)
+        emax = torch.where(nzb, eb, torch.full_like(eb, -1)).amax(dim=1)
+        emax = torch.where(emax >= 0, emax, torch.full_like(emax, 127))                   # an all-zero row: s = 1
+        rel = 127 + eb - emax[:, None]
+        if bool((nzb & (rel < 127 - MXFP4_EXP_SPAN)).any()):
+            n, b = [int(v[0]) for v in torch.nonzero(nzb & (rel < 127 - MXFP4_EXP_SPAN), as_tuple=True)]
+            raise PsgHipError(f"{path}: MXFP4 tensor {kw}: block {b} of row {n} lies 2^{int(emax[n] - eb[n, b])} below its "
+                              f"row's largest block exponent (at most 2^{MXFP4_EXP_SPAN}: the widened weight must stay a "
+                              "normal fp16 number)")
+        out[kw + BEXP_SUFFIX] = torch.where(nzb, rel, torch.full_like(rel, 127 - MXFP4_EXP_SPAN)).to(torch.uint8).contiguous()
+        out[ks] = torch.exp2((emax - 127).to(torch.float32))
+    return out
+
+
 def llm_quant_keys(n_layers: int, lm_head: bool = False):
-    """Names of the matrices llm_weight_quant='fp8' quantises: q/k/v/o/gate/up/down of the kept layers (+ the lm_head on
+    """Names of the matrices llm_weight_quant quantises: q/k/v/o/gate/up/down of the kept layers (+ the lm_head on
     request); never the embedding, the norms or language_projection."""
     keys = [f"language_model.model.layers.{l}.{n}" for l in range(n_layers) for n in LLM_QUANT_MATRICES]
     return keys + (["language_model.lm_head.weight"] if lm_head else [])
 
 
-def quantize_llm_weights(weights: dict, n_layers: int, lm_head: bool = False) -> dict:
+def quantize_llm_weights(weights: dict, n_layers: int, lm_head: bool = False, fmt: str = "fp8") -> dict:
     """`weights` with every matrix of `llm_quant_keys` replaced by its (q, s): the byte tensor under the matrix's own name,
-    the scales under name + '_scale'.  A matrix that already comes as (q, s) - an FP8 checkpoint - is kept as it is."""
+    the scales under name + '_scale'; fmt='mxfp4': its (q, e, s), the block exponents under name + '_bexp'.  A matrix that
+    already comes quantised - an FP8 or MXFP4 checkpoint - is kept as it is."""
+    if fmt not in ("fp8", "mxfp4"):
+        raise ValueError(f"quantize_llm_weights: fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
     out = dict(weights)
     for k in llm_quant_keys(n_layers, lm_head):
         if k in out and not is_quantized(out, k):
-            out[k], out[k + SCALE_SUFFIX] = quantize_fp8_rows(out[k])
+            if fmt == "fp8":
+                out[k], out[k + SCALE_SUFFIX] = quantize_fp8_rows(out[k])
+            else:
+                out[k], out[k + BEXP_SUFFIX], out[k + SCALE_SUFFIX] = quantize_mxfp4_rows(out[k])
     return out
 
 
@@ -262,6 +378,8 @@ def _take_fp8_pairs(out: dict, path):
         del out[k]
     for ks in [k for k in out if k.endswith(".weight" + SCALE_SUFFIX)]:
         kw = ks[:-len(SCALE_SUFFIX)]
+        if kw + BEXP_SUFFIX in out:                                    # an MXFP4 matrix (_take_mxfp4)
+            continue
         w, s = out.get(kw), out[ks].to(torch.float32)
         if w is None or w.dtype != torch.float8_e4m3fn or w.dim() != 2:
             raise PsgHipError(f"{path}: {ks} has no float8_e4m3fn matrix {kw} beside it")
@@ -357,7 +475,9 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
     + shards, pytorch_model.bin, pytorch_model.bin.index.json + shards (in that order, as from_pretrained prefers them).
     An FP8 checkpoint (a `*.weight` of dtype float8_e4m3fn with a sibling `*.weight_scale`: per-tensor scalar, [N] or
     [N, 1]) is taken as it is: the matrix stays float8_e4m3fn, its scale becomes fp32 [N] under name + '_scale', nothing
-    is re-quantised; `*.input_scale` entries are ignored (weight-only execution)."""
+    is re-quantised; `*.input_scale` entries are ignored (weight-only execution).  An MXFP4 checkpoint (`*.weight` uint8
+    [N, K / 2] with a sibling `*.weight_scale` uint8 [N, K / 32]) is row-anchored (`_take_mxfp4`): name + '_scale' fp32 [N],
+    name + '_bexp' uint8 [N, K / 32]."""
     import json
     import os
     from ._lib import PsgHipError
@@ -411,4 +531,4 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
     bias = sorted(k for k in out if k.endswith(".bias"))
     if bias:
         raise PsgHipError(f"{path}: bias tensors are not built (Llama / Mistral projections have none): {bias[:3]}")
-    return _take_fp8_pairs(out, path)
+    return _take_fp8_pairs(_take_mxfp4(out, path), path)

@@ -48,8 +48,9 @@ def parser():
     ap.add_argument("--llm-dir", help="local HuggingFace checkpoint directory of the LLM (config.json + model.safetensors / "
                     "shards / pytorch_model*.bin): read by the head's constructor as the reference's from_pretrained does "
                     "(V4:99-103); without it the LLM is seeded random weights of --llm-layers layers")
-    ap.add_argument("--llm-weight-quant", choices=["fp8"], default=None,
-                    help="fp8: the LLM's projection matrices as OCP e4m3fn bytes with per-row scales (decode steps stream one "
+    ap.add_argument("--llm-weight-quant", choices=["fp8", "mxfp4"], default=None,
+                    help="mxfp4: OCP Microscaling FP4 (two codes per byte, one exponent per 32 weights, one scale per row: "
+                    "4.25 bits per weight); an MXFP4 checkpoint in --llm-dir is taken as it is either way.  fp8: the LLM's projection matrices as OCP e4m3fn bytes with per-row scales (decode steps stream one "
                     "byte per weight); an FP8 checkpoint in --llm-dir is taken as it is either way")
     return ap
 
