@@ -153,7 +153,10 @@ int psg_bias_gelu(psg_ctx*, const void* x, const float* bias, int64_t rows, int 
 /* ---- K5: Q-Former self-attention, HF-IB:471-515 (eager 176-196).
  * qkv [(B*nq + B*T)][3*hidden] = [Q|K|V] of the query rows then the text rows; text_mask uint8
  * [B][T] (V4:158-159; masked keys get additive finfo.min).  nq + T <= 64, head_dim 64.
- * query_rows_only != 0 computes only the nq query rows of each pair (last layer, V4:185). */
+ * query_rows_only: 0 = every row, out [(B*nq + B*T)][hidden] in the layout of qkv; 1 = only the nq query rows of each
+ * pair (last layer, V4:185), same layout, the text rows of out are not written; 2 = only the cls row (row 0) of each
+ * pair, written COMPACT: out [B][hidden], out[p] = the cls row of pair p, nothing else is written (every dtype).
+ * Any other value: PSG_ERR_INVALID. */
 int psg_qformer_self_attn(psg_ctx*, const void* qkv, const uint8_t* text_mask, int B, int T, int nq,
                           int heads, int query_rows_only, void* out, int dtype, void* stream);
 
@@ -180,7 +183,8 @@ int psg_qformer_self_attn_cls(psg_ctx*, const void* q_cls, const void* kv, const
  * sum_j p_j x_j, which the caller projects through W_v,h (+ b_v) - fp32 on both sides because a 768-term product of
  * rounded factors would lose what the 64-term q.k keeps.  Same function as psg_qformer_self_attn_cls up to rounding
  * (fp32: 1e-6); the K | V projection of every row of every pair is not computed at all.
- * hidden 768 = 12 heads only; PSG_ERR_UNSUPPORTED when a pair's rows exceed the LDS (fp32, > 48 rows). */
+ * hidden 768 = 12 heads only; PSG_ERR_UNSUPPORTED when a pair's rows exceed the LDS (fp32, > 52 rows:
+ * 3072 bytes a row beside the 3072-byte probability table in 160 KiB). */
 int psg_qformer_cls_attn_input(psg_ctx*, const void* x_query, const void* x_text, const int32_t* text_index,
                                const void* g, const uint8_t* text_mask, int B, int T, int nq, int heads, int hidden,
                                void* xbar, int dtype, void* stream);

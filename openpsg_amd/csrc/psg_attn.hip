@@ -94,10 +94,15 @@ extern "C" int psg_qformer_self_attn(psg_ctx* ctx, const void* qkv, const uint8_
               T_, nq);
   PSG_REQUIRE(nq + T_ <= 64, PSG_ERR_UNSUPPORTED,
               "psg_qformer_self_attn: %d query rows + %d prompt tokens > 64 keys (one wavefront)", nq, T_);
+  PSG_REQUIRE(query_rows_only >= 0 && query_rows_only <= 2, PSG_ERR_INVALID,
+              "psg_qformer_self_attn: query_rows_only=%d (0 = every row, 1 = the query rows, 2 = the cls row, compact)",
+              query_rows_only);
   // bf16 activations with the standard geometry run on the matrix cores (psg_selfattn_mfma.hip);
-  // option selfattn_scalar forces the scalar kernel (on-device cross-check)
+  // option selfattn_scalar forces the scalar kernel (on-device cross-check).  Mode 2 (the cls row only, written compact
+  // to out[p]) is not the 16-bit matrix-core kernel's, which writes whole row tiles at the full layout: the scalar
+  // kernel, which implements it for every dtype, takes it (the fp32 matrix kernel has the mode itself).
   const int force_scalar = ctx->opt.selfattn_scalar;
-  if ((dtype == PSG_BF16 || dtype == PSG_F16) && nq >= 32 && nq + T_ <= 64 && !force_scalar)
+  if ((dtype == PSG_BF16 || dtype == PSG_F16) && nq >= 32 && nq + T_ <= 64 && !force_scalar && query_rows_only != 2)
     return psg_self_attn_mfma_launch(qkv, nullptr, text_mask, B, T_, nq, heads, query_rows_only, out, dtype, (hipStream_t)stream);
   if (dtype == PSG_F32 && !force_scalar)                    // exact f32 matrix instructions (psg_attn_f32.hip)
     return psg_self_attn_f32_launch(qkv, nullptr, text_mask, B, T_, nq, heads, query_rows_only, out, (hipStream_t)stream);
@@ -464,7 +469,7 @@ __global__ void __launch_bounds__(256) qformer_cls_attn_input_kernel(const T* __
 // block text_index[p] (or p when text_index is NULL) of T rows per pair - pairs with the same prompt may share one block
 // (and one row of text_mask); xbar [heads][B][hidden] (fp32) = sum_j softmax_j(g_h . x_j / 8 + mask_j) x_j.
 // PSG_ERR_UNSUPPORTED outside hidden 768 / 12 heads or when the rows of one pair do not fit the LDS (fp32 with more
-// than 48 rows): use the K | V form then.
+// than 52 rows): use the K | V form then.
 extern "C" int psg_qformer_cls_attn_input(psg_ctx* ctx, const void* x_query, const void* x_text, const int32_t* text_index,
                                           const void* g, const uint8_t* text_mask, int B, int T_, int nq, int heads,
                                           int hidden, void* xbar, int dtype, void* stream) {

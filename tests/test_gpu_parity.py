@@ -158,6 +158,12 @@ def test_cross_attn_mfma_vs_fp32_reference(L, N, P):
     e_s = (out_s.float() - ref).abs().max().item()
     print(f"L={L}: LDS-DMA kernel err {e_m:.3e}, first-generation kernel err {e_1:.3e}, simple err {e_s:.3e}")
     assert e_s < 2e-2 and e_m < 3e-2 and e_1 < 3e-2               # bf16 outputs of O(1) values
+    # and the derived bound against float64 (tests/qformer_attn_ref.py: u |ref| + u A + 2e-5)
+    from tests.qformer_attn_ref import attn_bound, xattn64
+    from tests.rowops_ref_common import _check
+    ref64, A64 = xattn64(q.cpu(), k.cpu(), v.cpu(), pm.cpu(), heads, 33, "uniform")
+    for name, o in (("LDS-DMA", out_m), ("first generation", out_1), ("simple", out_s)):
+        _check(f"cross_attn {name} L={L}", o.cpu(), ref64, attn_bound(ref64, A64, torch.bfloat16))
     if L <= 320:                                                  # same per-unit arithmetic, other data movement
         assert torch.equal(out_m, out_1)
     # empty pair (0,0): uniform softmax over the L real keys == mean of V
@@ -859,6 +865,11 @@ def test_self_attn_mfma_vs_fp32_reference(B, T, q_only):
         worst = max(worst, (got - o[:n]).abs().max().item())
     print(f"self_attn mfma B={B} T={T} q_only={q_only}: max err {worst:.3e}")
     assert worst < 3e-2
+    # and the derived bound against float64 (tests/qformer_attn_ref.py: u |ref| + u A + 2e-5)
+    from tests.qformer_attn_ref import attn_bound, selfattn64
+    from tests.rowops_ref_common import _check
+    ref64, A64 = selfattn64(qkv.cpu(), tmask.cpu(), B, T, nq, heads, "query" if q_only else "all")
+    _check(f"self_attn mfma B={B} T={T}", out[:ref64.shape[0]].cpu(), ref64, attn_bound(ref64, A64, torch.bfloat16))
 
 
 @pytest.mark.parametrize("geo", [((1024, 1024), None, None, 50), ((768, 1024), (720, 960), (750, 1000), 12)])
