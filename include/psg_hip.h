@@ -73,8 +73,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   603  relation likelihoods over a token trie: psg_tree_attn, psg_token_logprobs added
  *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added
  *   605  training branch in bf16: psg_train_bf16_* added
- *   606  MXFP4-quantised LLM weights: psg_split_gemm_w4(_plan), psg_skinny_gemm_w4(_plan) added */
-#define PSG_ABI_VERSION 606
+ *   606  MXFP4-quantised LLM weights: psg_split_gemm_w4(_plan), psg_skinny_gemm_w4(_plan) added
+ *   607  quantised matrices as the only resident copy: psg_expand_w8, psg_expand_w4 added */
+#define PSG_ABI_VERSION 607
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -390,6 +391,17 @@ int psg_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const vo
 int psg_skinny_gemm_w4_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
 int psg_skinny_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img, const float* col_scale, float* part, int M,
                        int N, int K, int slots, int dtype, int mode, void* stream);
+/* The dense operand of a quantised matrix, rebuilt from its bytes (an engine that keeps only the bytes resident
+ * expands a matrix into a scratch buffer right before the one large-M product that reads it).  q: e4m3fn bytes [N][K]
+ * (psg_expand_w8) or fp4 nibbles [N][K / 2], the low nibble the even k, with the RAW block exponents e uint8 [N][K / 32] in
+ * 114..127 (psg_expand_w4: the model's own e, not the e_img of the w4 products).
+ *   s == NULL (out_dtype PSG_F16 only): out[n][k] = e4m3(q) resp. e2m1(q) 2^(e - 127) as fp16 - exact;
+ *   s fp32 [N]: out[n][k] = float32(that value) * s[n] - ONE fp32 multiply - rounded ONCE to nearest even into out_dtype
+ *   (PSG_F32 / PSG_F16 / PSG_BF16): weights.dequantize_fp8_rows / dequantize_mxfp4_rows bit for bit.
+ * out is [N][K] contiguous; exactly N * K elements are written.  N >= 1, K % 32 == 0, q and out 16-byte aligned (16-byte
+ * accesses), else PSG_ERR_UNSUPPORTED.  A streaming kernel: non-temporal loads of the bytes, ordinary stores. */
+int psg_expand_w8(psg_ctx*, const void* q, const float* s, void* out, int N, int K, int out_dtype, void* stream);
+int psg_expand_w4(psg_ctx*, const void* q, const void* e, const float* s, void* out, int N, int K, int out_dtype, void* stream);
 /* psg_skinny_gemm(PSG_F32) over weights STORED as fp16: x fp32 [M][K], w fp16 [N][K], the same plan (psg_skinny_gemm_plan
  * with PSG_F32), the same f32 matrix instructions on the exactly widened weights in the same order - part is bit-identical
  * to the fp32-weight call on w.float(), at half the weight bytes.  For weights that ARE fp16 values: the reference's LLM is

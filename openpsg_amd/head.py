@@ -35,8 +35,8 @@ from .qformer import RelationQueryEngine
 from .registry import HEADS
 from .rel_scores import MAX_RANKED_TRIPLES, assemble, build_relation_trie
 from .tokenizers import WordTokenizer
-from .weights import (head_shapes, hf_checkpoint_has_weights, is_hf_checkpoint_dir, llm_shapes, read_hf_llama_config,
-                      read_hf_llama_weights)
+from .weights import (head_shapes, hf_checkpoint_has_weights, is_hf_checkpoint_dir, llm_quant_keys, llm_shapes,
+                      read_hf_llama_config, read_hf_llama_weights)
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32,
            "fp16": torch.float16, "float16": torch.float16, "half": torch.float16, "mixed": torch.float16,
@@ -237,6 +237,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # + one fp32 scale per row (weights.quantize_mxfp4_rows): 4.25 bits
                                                # per weight in those steps, W' = fp4(q) 2^(e - 127) s likewise
                  llm_quantize_lm_head=False,   # quantised: the lm_head as well (never the embedding, norms, language_projection)
+                 llm_weight_resident='all',    # 'all' | 'quantised': what a quantised LLM keeps in HBM.  'all': W' in
+                                               # the engine's dtype beside the bytes (+ the fp16 image of the fp32s prompt
+                                               # pass).  'quantised': the bytes, exponents and row scales ONLY - dense operands
+                                               # are rebuilt into a scratch buffer right before each product of more than 32
+                                               # rows (psg_expand_w8 / _w4), bit for bit the ones 'all' stores; inference only
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -252,6 +257,12 @@ class RelationTransformerHeadV4(nn.Module):
         if llm_weight_quant is not None and "binary" not in rel_cls_type:
             raise PsgHipError(f"llm_weight_quant={llm_weight_quant!r} quantises the LLM; rel_cls_type={rel_cls_type!r} has no "
                               "LLM stage")
+        if llm_weight_resident not in ("all", "quantised"):
+            raise PsgHipError(f"llm_weight_resident must be 'all' or 'quantised', got {llm_weight_resident!r}")
+        if llm_weight_resident == "quantised" and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_weight_resident='quantised' is about the LLM's weights; rel_cls_type={rel_cls_type!r} has no "
+                              "LLM stage")
+        self.llm_weight_resident = llm_weight_resident
         if llm_quantize_lm_head and llm_weight_quant is None:
             raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4'")
         self.llm_weight_quant = llm_weight_quant
@@ -461,11 +472,19 @@ class RelationTransformerHeadV4(nn.Module):
         if wrong:                                       # e.g. a grouped-query checkpoint under a multi-head config
             raise PsgHipError(f"LLM weights of the wrong shape ({len(wrong)}), e.g. {wrong[:2]} "
                               f"({self.cfg.llm.heads} query / {self.cfg.llm.n_kv_heads} key-value heads)")
-        w = self.quantize_llm_weights(weights)
+        if self.llm_weight_resident == "quantised":
+            # the dense model never reaches the device: a matrix is quantised where it lives, uploaded and dropped when the
+            # engine asks for it (peak = the final footprint + the pieces of one matrix in flight)
+            from .weights import LazyQuantWeights
+            quant = llm_quant_keys(n_layers, self.llm_quantize_lm_head) if self.llm_weight_quant is not None else []
+            w = LazyQuantWeights(weights, quant, self.llm_weight_quant, self.device)
+        else:
+            w = self.quantize_llm_weights(weights)
         w["language_projection.weight"] = self.language_projection.weight.data
         w["language_projection.bias"] = self.language_projection.bias.data
         self._llm_engine = LlamaDecodeEngine(w, self.cfg, self.device, self.act_dtype, n_layers=n_layers,
-                                             resid_dtype=self.resid_dtype, prefill_split=self.prefill_split)
+                                             resid_dtype=self.resid_dtype, prefill_split=self.prefill_split,
+                                             resident=self.llm_weight_resident)
         return self
 
     def quantize_llm_weights(self, weights: dict) -> dict:
@@ -744,6 +763,10 @@ class RelationTransformerHeadV4(nn.Module):
         prompt / label token grids.  `sampled` / `selected` replace the random draws (V4:173 `qformer_sampler`,
         V4:222-228 `random.sample`).  Returns a dict shared by the loss-only and the gradient paths."""
         import random
+        if self.llm_weight_resident == "quantised" and self.has_binary:
+            raise PsgHipError("llm_weight_resident='quantised' is an inference mode: the training forward would keep views of "
+                              "an expansion scratch that the next product overwrites - build the head with "
+                              "llm_weight_resident='all' to train")
         dev = self.device
         feat = inputs['mask_features']
         assert feat.shape[0] == 1, 'only support batch size 1 for now.'                     # V4:112

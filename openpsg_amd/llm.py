@@ -219,9 +219,34 @@ def _measure_batch_plan(x, pool):
     return best
 
 
+class QuantMatrix:
+    """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
+    `lm_head` hold in place of W'.  Carries the shape and dtype W' would have and the quantised parts - (q, s) for FP8,
+    (q, the raw block exponents e, the decode kernel's exponent image, s) for MXFP4.  `data_ptr()` is q's address: the key of
+    the engine's byte-stream tables, alive exactly as long as the bytes are.  A dense operand exists only for the length of
+    one product, in the engine's scratch (`LlamaDecodeEngine._dense`)."""
+    __slots__ = ("name", "fmt", "shape", "dtype", "device", "q", "e", "e_img", "s")
+
+    def __init__(self, name, fmt, shape, dtype, q, s, e=None, e_img=None):
+        self.name, self.fmt, self.shape, self.dtype, self.device = name, fmt, torch.Size(shape), dtype, q.device
+        self.q, self.s, self.e, self.e_img = q, s, e, e_img
+
+    def data_ptr(self):
+        return self.q.data_ptr()
+
+    def numel(self):
+        return self.shape[0] * self.shape[1]
+
+    def parts(self):
+        return [t for t in (self.q, self.e, self.e_img, self.s) if t is not None]
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.parts())
+
+
 class LlamaDecodeEngine:
     def __init__(self, weights: dict, cfg: PSGConfig, device, dtype=torch.bfloat16, n_layers=None, resid_dtype=None,
-                 prefill_split=False):
+                 prefill_split=False, resident="all"):
         """prefill_split (fp32 engines): the prompt pass's projections as split-fp16 products on the 16-bit matrix cores,
         `linear_split` below; the decode steps stay exact fp32 (psg_gemm_f32.hip).
         resid_dtype: storage type of the residual stream; None = `dtype` (what HF keeps for a model cast to 16
@@ -229,6 +254,15 @@ class LlamaDecodeEngine:
         of 2 x layers updates - never rounded to 16 bits; costs 160 KB more traffic per decode row kernel)."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
+        if resident not in ("all", "quantised"):
+            raise PsgHipError(f"resident must be 'all' or 'quantised', got {resident!r}")
+        # resident='quantised' (DESIGN 15): a quantised matrix is held as its bytes only - no W', no fp16 image - and every
+        # product that reads a dense operand (more than 32 rows) has it expanded into a scratch buffer first (`_dense`)
+        self.resident = resident
+        lean = resident == "quantised"
+        if lean and dtype == torch.float32 and not prefill_split:
+            raise PsgHipError("resident='quantised': the exact fp32 mode (dtype='fp32') reads W' in every decode step, there is "
+                              "nothing to drop - use dtype='fp32s' / 'mixed' / 'bf16' / 'fp16', or resident='all'")
         self.resid_dtype = dtype if resid_dtype is None else resid_dtype
         if self.resid_dtype not in (dtype, torch.float32):
             raise PsgHipError(f"residual dtype must be {dtype} or float32, got {self.resid_dtype}")
@@ -260,6 +294,52 @@ class LlamaDecodeEngine:
                               quant_format, _mxfp4_unscaled)
         self._w8, self._w8h = {}, {}
         self._w4, self._w4h = {}, {}
+        if lean:
+            from .weights import llm_quant_keys
+            dense = [k for k in llm_quant_keys(m.layers if n_layers is None else n_layers) if k + SCALE_SUFFIX not in weights]
+            if dense:
+                raise PsgHipError(f"resident='quantised' needs every decoder-layer matrix quantised; {len(dense)} are not (e.g. "
+                                  f"{dense[0]}): set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint, or use "
+                                  "resident='all'")
+
+        def lean_matrix(keys):
+            """resident='quantised': the matrix of `keys` as a `QuantMatrix`.  A key's parts are read together, one key
+            after the other (the loader quantises a matrix when it is asked for and keeps none, head.load_llm_weights)."""
+            name = keys[0].rsplit(".", 2)[0] + "." + "|".join(k.split(".")[-2] for k in keys)
+            qs, scs, es = [], [], []
+            for k in keys:
+                qs.append(weights[k].to(self.device).view(torch.uint8))
+                scs.append(weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1))
+                es.append(weights[k + BEXP_SUFFIX].to(self.device) if k + BEXP_SUFFIX in weights else None)
+            if any(e is None for e in es) and not all(e is None for e in es):
+                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
+            q = (torch.cat(qs, 0) if len(qs) > 1 else qs[0]).contiguous()
+            sc = (torch.cat(scs, 0) if len(scs) > 1 else scs[0]).contiguous()
+            del qs, scs
+            if sc.numel() != q.shape[0]:
+                raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
+            if es[0] is None:
+                N, K = q.shape
+                if N % 16 or K % 128:
+                    raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the FP8 byte-stream kernels of the "
+                                      "decode steps (N % 16 == 0, K % 128 == 0), and there is no W' to fall back on: "
+                                      "resident='all' runs it on W'")
+                w = QuantMatrix(name, "fp8", (N, K), dtype, q, sc)
+                self._w8[w.data_ptr()] = (q, sc)
+                return w
+            e = (torch.cat(es, 0) if len(es) > 1 else es[0]).contiguous()
+            N, K = q.shape[0], 2 * q.shape[1]
+            if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
+                raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
+                                  "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
+            if N % 16 or K % 256:
+                raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the MXFP4 nibble-stream kernels of the "
+                                  "decode steps (N % 16 == 0, K % 256 == 0), and there is no W' to fall back on: "
+                                  "resident='all' runs it on W'")
+            # (a W4_STREAM_AS_FP8 shape streams as nibbles here: its FP8 image would be a second resident copy)
+            w = QuantMatrix(name, "mxfp4", (N, K), dtype, q, sc, e, ops.mxfp4_exp_image(e))
+            self._w4[w.data_ptr()] = (q, w.e_img, sc)
+            return w
 
         def matrix(*keys):
             """The (row-concatenated) matrix of `keys` in the engine's dtype; registers its byte stream when every part
@@ -267,6 +347,8 @@ class LlamaDecodeEngine:
             quant = [k + SCALE_SUFFIX in weights for k in keys]
             if any(quant) and not all(quant):
                 raise PsgHipError(f"{keys}: some parts are FP8-quantised and some are not")
+            if lean and quant[0]:
+                return lean_matrix(keys)
             if not quant[0]:
                 return act(torch.cat([weights[k] for k in keys], 0) if len(keys) > 1 else weights[keys[0]])
             fmts = {quant_format(weights, k) for k in keys}
@@ -362,7 +444,7 @@ class LlamaDecodeEngine:
         # kernel choice follows the row count: a pair decoded in a batch of 3 (decodes DEALT over the ranks of a pair-sharded
         # job) then gives the bits it gives in the batch of 20.  ~1.3x the prompt pass's GEMM time: the sharded
         # pipeline switches it on, a single GPU does not need it
-        self.row_invariant = False
+        self._row_invariant = False
         self.split_i2 = bool(_lib.get_option(dev_i, "split_i2"))
         self._i2_w = {}
         self.proj_s = ops.split_f16x3(self.proj_w, weights=True) if self.prefill_split else None
@@ -392,8 +474,18 @@ class LlamaDecodeEngine:
         self._w_pools = {}
         for L in self.layers:
             for k in ("wqkv", "wo", "wgu", "wdown"):
-                self._w_pools.setdefault(tuple(L[k].shape), []).append(L[k])
-        self._w_pools.setdefault(tuple(self.lm_head.shape), []).append(self.lm_head)
+                if not isinstance(L[k], QuantMatrix):          # (pools time dense tensors in rotation, PSG_PLAN=measure)
+                    self._w_pools.setdefault(tuple(L[k].shape), []).append(L[k])
+        if not isinstance(self.lm_head, QuantMatrix):
+            self._w_pools.setdefault(tuple(self.lm_head.shape), []).append(self.lm_head)
+        # resident='quantised': one scratch buffer per slot (`head.submit` runs two streams), as large as the largest
+        # quantised matrix in the engine's dtype - the widest form `_dense` makes (the unscaled fp16 operand of the fp32s
+        # prompt pass uses its head).  Allocated once, outside any graph: captured graphs replay against its address
+        self._slot = 0
+        self._scratch = {}
+        self._scratch_elems = max([w.numel() for w in self._quant_matrices()], default=0)
+        if lean:
+            self._scratch_for(0)
         self._dl_ws = {}
         self._dl_host_buf = None
         self.use_graph = True            # capture the batched decode in a HIP graph (per input shape)
@@ -407,6 +499,80 @@ class LlamaDecodeEngine:
         inv_freq = 1.0 / (m.rope_theta ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))
         ang = torch.arange(4096, dtype=torch.float32)[:, None] * inv_freq[None, :]
         self.rope = (ang.cos().contiguous().to(self.device), ang.sin().contiguous().to(self.device))
+
+    @property
+    def row_invariant(self):
+        return self._row_invariant
+
+    @row_invariant.setter
+    def row_invariant(self, on):
+        if on and self.resident == "quantised":
+            raise PsgHipError("resident='quantised': the row-invariant prompt pass (pair-sharded pipelines) reads dense "
+                              "interleaved images of every weight - build the engine with resident='all'")
+        self._row_invariant = bool(on)
+
+    def _quant_matrices(self):
+        """The `QuantMatrix` handles of an engine with resident='quantised' (none otherwise)."""
+        ws = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
+        return [w for w in ws if isinstance(w, QuantMatrix)]
+
+    def _scratch_for(self, slot):
+        buf = self._scratch.get(slot)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise PsgHipError(f"resident='quantised': slot {slot}'s scratch must exist before a graph is captured")
+            buf = self._scratch[slot] = torch.empty(self._scratch_elems, device=self.device, dtype=self.dtype)
+        return buf
+
+    def _dense(self, w, unscaled=False):
+        """THE accessor for the dense operand of a product.  A tensor is its own operand.  A `QuantMatrix` is expanded on
+        the current stream into the current slot's scratch (psg_expand_w8 / _w4) and a view of that is returned: W' in the
+        engine's dtype - weights.dequantize_*_rows bit for bit - or, `unscaled`, the exact fp16 image of W' / s (the fp32s
+        two-plane prompt pass applies s as the column scale).  The view is valid until the slot's next expansion: expand
+        per matrix, immediately before its product."""
+        if not isinstance(w, QuantMatrix):
+            return w
+        buf = self._scratch_for(self._slot)
+        if unscaled:
+            buf = buf.view(torch.float16)
+        s = None if unscaled else w.s
+        if w.fmt == "fp8":
+            return ops.expand_w8(w.q, s, out=buf)
+        return ops.expand_w4(w.q, w.e, s, out=buf)
+
+    def resident_bytes(self):
+        """What the engine holds in HBM, in bytes (numel * element_size): `quantised` - the byte streams, block exponents
+        and row scales of its quantised matrices; `scratch` - every slot's expansion scratch; `other` - every other tensor
+        (embedding, norms, projections, rotary tables, and with resident='all' the dense copies W' and their fp16 / split
+        images); `total`.  KV caches and graph pools belong to a generation, not to the engine, and are not counted."""
+        seen, quant = set(), 0
+        for t in [p for w in self._quant_matrices() for p in w.parts()] + \
+                 [p for ent in list(self._w8.values()) + list(self._w4.values()) for p in ent if p is not None]:
+            if t.data_ptr() not in seen:
+                seen.add(t.data_ptr())
+                quant += t.numel() * t.element_size()
+        scratch = 0
+        for t in self._scratch.values():
+            seen.add(t.data_ptr())
+            scratch += t.numel() * t.element_size()
+        other = 0
+
+        def walk(o):
+            nonlocal other
+            if isinstance(o, torch.Tensor):
+                if o.is_cuda and o.data_ptr() not in seen:
+                    seen.add(o.data_ptr())
+                    other += o.numel() * o.element_size()
+            elif isinstance(o, dict):
+                for v in o.values():
+                    walk(v)
+            elif isinstance(o, (list, tuple)):
+                for v in o:
+                    walk(v)
+        for name in ("embed", "lm_head", "final_norm", "proj_w", "proj_b", "proj_s", "layers", "rope", "_w8h", "_w4h", "_w16",
+                     "_i2_w", "_ones_cache"):
+            walk(getattr(self, name, None))
+        return dict(quantised=quant, scratch=scratch, other=other, total=quant + scratch + other)
 
     def _dense_split(self, ws):
         """Does `linear_split` run this split weight on psg_dense_gemm (the row-invariant path)?"""
@@ -496,6 +662,7 @@ class LlamaDecodeEngine:
                 x2, inv = ops.split_f16x2(x)
                 return ops.split_gemm_w4(x2, inv, *w4)
             return ops.skinny_gemm_w4(x, *w4)
+        w = self._dense(w)                                    # (resident='quantised': W' expanded into the slot's scratch)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
             if wh is not None and self.prefill_split:         # fp32s: two fp16 products of the split rows, 2 bytes per weight
@@ -558,13 +725,14 @@ class LlamaDecodeEngine:
         rounded: the 16-bit product, where the caller has it: without `out_dtype` it is widened instead of computed again."""
         if self._mm_out_dtype is None:
             try:
-                torch.mm(h[:1], self.lm_head[:16].t(), out_dtype=torch.float32)
+                probe = self.embed if isinstance(self.lm_head, QuantMatrix) else self.lm_head
+                torch.mm(h[:1], probe[:16].t(), out_dtype=torch.float32)
                 self._mm_out_dtype = True
             except (TypeError, RuntimeError):
                 self._mm_out_dtype = False
         if self._mm_out_dtype:
-            return torch.mm(h, self.lm_head.t(), out_dtype=torch.float32)
-        return (F.linear(h, self.lm_head) if rounded is None else rounded).float()
+            return torch.mm(h, self._dense(self.lm_head).t(), out_dtype=torch.float32)
+        return (F.linear(h, self._dense(self.lm_head)) if rounded is None else rounded).float()
 
     # ---- one pass over `rows` token rows -------------------------------------------------------
     def _forward(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, decode=False, prefill_shape=None, rope_pos=None,
@@ -656,7 +824,9 @@ class LlamaDecodeEngine:
             mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
             split = ops.split_f16x3
         else:
-            if self._w8_layers:                                 # W' = q s: the exact fp16 image of q, s as the column scale
+            if self.resident == "quantised":                    # the same operand, expanded right before its product
+                weight = lambda L, k: (self._dense(L[k], unscaled=True), L[k].s)                # noqa: E731
+            elif self._w8_layers:                               # W' = q s: the exact fp16 image of q, s as the column scale
                 weight = lambda L, k: (self._w8h[L[k].data_ptr()], self._w8[L[k].data_ptr()][1])   # noqa: E731
             elif self._w4_layers:                               # W' = (fp4(q) 2^(e - 127)) s: likewise
                 weight = lambda L, k: (self._w4h[L[k].data_ptr()], self._w4[L[k].data_ptr()][2])   # noqa: E731
@@ -902,6 +1072,9 @@ class LlamaDecodeEngine:
         X [K, S, D] COMPACT sequences (pads removed), seq_len int32 [K], rope_pos int32 [K*S] = each row's position
         in the reference's PADDED sequence (HF numbers positions 0..T-1 over pads in a plain forward), rows int32:
         flat row indices whose logits are wanted.  Returns logits [len(rows), vocab] in the activation dtype."""
+        if self.resident == "quantised":
+            raise PsgHipError("resident='quantised': the training forward would keep views of a scratch buffer that the next "
+                              "product overwrites - train on an engine built with resident='all'")
         m = self.cfg.llm
         K, S, D = X.shape
         dev = self.device
@@ -1053,6 +1226,7 @@ class LlamaDecodeEngine:
         """Prompt pass + first greedy token (+ the relation-likelihood pass over `trie`, whose rows own the cache slots
         behind the decode region).  Returns the decode state (KV caches, token / flag buffers)."""
         m = self.cfg.llm
+        self._slot = int(slot)
         K, maxlen, D = X.shape
         nv = self.cfg.qformer.num_query
         ctx_len = maxlen + max_new + (trie.n_int if trie is not None else 0)
@@ -1131,6 +1305,7 @@ class LlamaDecodeEngine:
     def _steps(self, st, lo, hi):
         """Decode steps lo .. hi-1 (step s writes tokens[:, s])."""
         m = self.cfg.llm
+        self._slot = int(st.get("slot", 0))
         persist = hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
         w16 = not persist and self._can_w16(st["x"].shape[0])
         w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])

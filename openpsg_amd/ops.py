@@ -836,6 +836,51 @@ def mxfp4_exp_image(e) -> torch.Tensor:
     return e.reshape(N, B // 8, 4, 2).permute(1, 0, 3, 2).contiguous()
 
 
+def _expand_out(name, N, K, s, out, dtype, device):
+    """The [N, K] result of an expansion: `out`'s first N * K elements (any contiguous buffer of the result's dtype that is
+    large enough - the engine's scratch) or a fresh tensor.  The unscaled form (s None) is fp16."""
+    dtype = torch.float16 if s is None else (dtype or (out.dtype if out is not None else torch.float32))
+    if s is None and out is not None and out.dtype != torch.float16:
+        raise PsgHipError(f"{name}: the unscaled form (s None) is fp16, out is {out.dtype}")
+    if s is not None and (s.dtype != torch.float32 or tuple(s.shape) != (N,)):
+        raise PsgHipError(f"{name}: s must be fp32 [{N}], got {s.dtype} {tuple(s.shape)}")
+    if out is None:
+        return torch.empty((N, K), device=device, dtype=dtype)
+    if out.dtype != dtype or not out.is_contiguous() or out.numel() < N * K:
+        raise PsgHipError(f"{name}: out must be a contiguous {dtype} buffer of >= {N * K} elements, got {out.dtype} "
+                          f"{tuple(out.shape)}")
+    return out.view(-1)[:N * K].view(N, K)
+
+
+def expand_w8(q, s=None, out=None, dtype=None) -> torch.Tensor:
+    """The dense operand of an FP8-quantised matrix (psg_expand_w8).  q: e4m3fn bytes [N, K] (uint8 /
+    float8_e4m3fn), K % 32 == 0.  s None: float16(q), exact.  s fp32 [N]: W' = float32(q) * s[:, None] rounded once into
+    `dtype` (fp32 / fp16 / bf16; default `out`'s, else fp32) - weights.dequantize_fp8_rows bit for bit.  Returns [N, K]: a
+    view of `out`'s head when a buffer is given (elements behind N * K are not touched)."""
+    lib, ctx, st = _env(q)
+    if q.dtype not in (torch.uint8, torch.float8_e4m3fn) or q.dim() != 2:
+        raise PsgHipError(f"expand_w8: q must be e4m3fn bytes [N, K] (uint8 / float8_e4m3fn), got {q.dtype} {tuple(q.shape)}")
+    N, K = q.shape
+    y = _expand_out("expand_w8", N, K, s, out, dtype, q.device)
+    check(lib.psg_expand_w8(ctx, _p(q, name="q"), _p(s), _p(y), N, K, _dt(y), st), "psg_expand_w8")
+    return y
+
+
+def expand_w4(q, e, s=None, out=None, dtype=None) -> torch.Tensor:
+    """`expand_w8` for an MXFP4-quantised matrix (psg_expand_w4): q fp4 nibbles uint8 [N, K / 2] (low nibble = even k), e the
+    model's RAW block exponents uint8 [N, K / 32] in 114..127 (not `mxfp4_exp_image`).  s None: fp4(q) * 2^(e - 127) as
+    fp16, exact.  s fp32 [N]: weights.dequantize_mxfp4_rows(q, e, s, dtype) bit for bit."""
+    lib, ctx, st = _env(q)
+    if q.dtype != torch.uint8 or q.dim() != 2:
+        raise PsgHipError(f"expand_w4: q must be fp4 nibbles uint8 [N, K / 2], got {q.dtype} {tuple(q.shape)}")
+    N, K = q.shape[0], 2 * q.shape[1]
+    if e.dtype != torch.uint8 or e.dim() != 2 or e.shape[0] != N or e.shape[1] * 32 != K:
+        raise PsgHipError(f"expand_w4: e must be uint8 [{N}, K / 32] with K = {K}, got {e.dtype} {tuple(e.shape)}")
+    y = _expand_out("expand_w4", N, K, s, out, dtype, q.device)
+    check(lib.psg_expand_w4(ctx, _p(q, name="q"), _p(e, name="e"), _p(s), _p(y), N, K, _dt(y), st), "psg_expand_w4")
+    return y
+
+
 def _w4_args(name, w4, e_img, col_scale, K):
     if w4.dtype != torch.uint8 or w4.dim() != 2 or w4.shape[1] * 2 != K:
         raise PsgHipError(f"{name}: w4 must be fp4 nibbles uint8 [N, {K // 2}], got {w4.dtype} {tuple(w4.shape)}")

@@ -370,6 +370,65 @@ def quantize_llm_weights(weights: dict, n_layers: int, lm_head: bool = False, fm
     return out
 
 
+class LazyQuantWeights(dict):
+    """The mapping `quantize_llm_weights` would return, without ever holding it: what llm_weight_resident='quantised' hands
+    the decode engine.  A matrix of `quant_keys` that is not quantised yet is quantised in row chunks WHERE IT
+    LIVES (`quantize_fp8_rows` / `quantize_mxfp4_rows`: rows are independent, so the chunks give the bits of the one-shot call
+    on the same device - the model is the one `quantize_llm_weights` makes of the same tensors, which a quantiser run on
+    another device need not be: torch divides by a scalar as a multiplication by its reciprocal on the GPU), its parts are
+    moved to `device` and handed out under its own name, name + '_scale' and name + '_bexp' - for the ONE matrix asked for
+    last; the previous one is dropped.  Everything else comes from
+    `weights` as it is; plain dict entries (language_projection.*) are set on the object.  The dense model
+    therefore never reaches `device` on the way: host weights are quantised on the host and only bytes are uploaded; weights
+    that already live on the device cost one chunk in fp32 plus the quantiser's temporaries."""
+
+    def __init__(self, weights: dict, quant_keys, fmt, device, chunk_elems: int = 1 << 22):
+        super().__init__()
+        if quant_keys and fmt not in ("fp8", "mxfp4"):
+            raise ValueError(f"LazyQuantWeights: fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
+        self._src, self._fmt, self._device, self._chunk = weights, fmt, torch.device(device), int(chunk_elems)
+        self._quant = {k for k in quant_keys if k in weights and not is_quantized(weights, k)}
+        self._last = (None, None)
+
+    def _base(self, key):
+        """(matrix name, part) when `key` names a part of a matrix this object quantises, else None."""
+        if key in self._quant:
+            return key, "q"
+        if key.endswith(SCALE_SUFFIX) and key[:-len(SCALE_SUFFIX)] in self._quant:
+            return key[:-len(SCALE_SUFFIX)], "s"
+        if self._fmt == "mxfp4" and key.endswith(BEXP_SUFFIX) and key[:-len(BEXP_SUFFIX)] in self._quant:
+            return key[:-len(BEXP_SUFFIX)], "e"
+        return None
+
+    def __contains__(self, key):
+        return dict.__contains__(self, key) or self._base(key) is not None or key in self._src
+
+    def __getitem__(self, key):
+        if dict.__contains__(self, key):
+            return dict.__getitem__(self, key)
+        hit = self._base(key)
+        if hit is None:
+            return self._src[key]
+        name, part = hit
+        if self._last[0] != name:
+            self._last = (None, None)                              # (drop the previous matrix before making this one)
+            self._last = (name, self._quantise(self._src[name]))
+        return self._last[1][part]
+
+    def _quantise(self, W):
+        W = torch.as_tensor(W)
+        # (a chunk is at most a quarter of the matrix: the MXFP4 quantiser's float64 temporaries are ~8 x the chunk's fp32
+        # bytes, and the load must stay within a few fp32 copies of ONE matrix above the final footprint)
+        rows = max(1, min(self._chunk, W.numel() // 4) // max(1, int(W.shape[1])))
+        out = []
+        for r0 in range(0, W.shape[0], rows):
+            Wc = W[r0:r0 + rows]
+            out.append(quantize_fp8_rows(Wc) if self._fmt == "fp8" else quantize_mxfp4_rows(Wc))
+            del Wc
+        parts = [(torch.cat(p, 0) if len(p) > 1 else p[0]).to(self._device) for p in zip(*out)]
+        return dict(zip(("q", "s") if self._fmt == "fp8" else ("q", "e", "s"), parts))
+
+
 def _take_fp8_pairs(out: dict, path):
     """The (weight, weight_scale) pairs of an FP8 checkpoint, as stored: weight stays float8_e4m3fn, the scale becomes
     fp32 [N] (a per-tensor scalar is expanded).  Activation scales (`input_scale`) are dropped: execution is weight-only."""

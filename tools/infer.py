@@ -52,6 +52,10 @@ def parser():
                     help="mxfp4: OCP Microscaling FP4 (two codes per byte, one exponent per 32 weights, one scale per row: "
                     "4.25 bits per weight); an MXFP4 checkpoint in --llm-dir is taken as it is either way.  fp8: the LLM's projection matrices as OCP e4m3fn bytes with per-row scales (decode steps stream one "
                     "byte per weight); an FP8 checkpoint in --llm-dir is taken as it is either way")
+    ap.add_argument("--llm-weight-resident", choices=["all", "quantised"], default="all",
+                    help="quantised: a quantised LLM (--llm-weight-quant, or an FP8 / MXFP4 checkpoint in --llm-dir) keeps only "
+                    "its bytes, exponents and row scales in HBM; dense operands are rebuilt into a scratch buffer right before "
+                    "each product of more than 32 rows (same results bit for bit, inference only)")
     return ap
 
 
@@ -67,7 +71,8 @@ def build_head(a, dev):
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
                                          llm_model_name=a.llm_dir, llm_feature_size=llm.hidden, llm_truncate_num=trunc,
                                          on_parse_error="skip", pair_selector=a.selector,
-                                         llm_weight_quant=getattr(a, "llm_weight_quant", None))
+                                         llm_weight_quant=getattr(a, "llm_weight_quant", None),
+                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
     else:
@@ -75,7 +80,8 @@ def build_head(a, dev):
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
                                          llm_config=llm, on_parse_error="skip", pair_selector=a.selector,
-                                         llm_weight_quant=getattr(a, "llm_weight_quant", None))
+                                         llm_weight_quant=getattr(a, "llm_weight_quant", None),
+                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
