@@ -74,8 +74,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   604  FP8-quantised LLM weights: psg_split_gemm_w8(_plan), psg_skinny_gemm_w8(_plan) added
  *   605  training branch in bf16: psg_train_bf16_* added
  *   606  MXFP4-quantised LLM weights: psg_split_gemm_w4(_plan), psg_skinny_gemm_w4(_plan) added
- *   607  quantised matrices as the only resident copy: psg_expand_w8, psg_expand_w4 added */
-#define PSG_ABI_VERSION 607
+ *   607  quantised matrices as the only resident copy: psg_expand_w8, psg_expand_w4 added
+ *   608  quantised weights in the batched decode: psg_batch_gemm_w8(_plan), psg_batch_split_gemm_w8(_plan),
+ *        psg_batch_gemm_w4(_plan), psg_batch_split_gemm_w4(_plan) added */
+#define PSG_ABI_VERSION 608
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -391,6 +393,30 @@ int psg_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const vo
 int psg_skinny_gemm_w4_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
 int psg_skinny_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img, const float* col_scale, float* part, int M,
                        int N, int K, int slots, int dtype, int mode, void* stream);
+/* The w8 / w4 projections for 33 <= M <= 160 rows (several images' pairs decoded together over a quantised
+ * LLM).  Operands, weight model and arithmetic are exactly those of the four entries above - w8 + col_scale, w4 + e_img +
+ * col_scale, exact widening in registers, 16-bit matrix cores, fp32 accumulation, the scales applied once in fp32 at the
+ * slice store:
+ *   psg_batch_gemm_w8 / _w4 (`dtype` = PSG_BF16 / PSG_F16, x [M][K]):  part[slot][m][n] = (x . q)[m][n] * col_scale[n];
+ *   psg_batch_split_gemm_w8 / _w4 (x2 fp16 planes [2][M][K] + inv_scale [M], psg_split_f16x2):
+ *     part[slot][m][n] = (xh . q + xl . q)[m][n] * inv_scale[m] * col_scale[n].
+ * 33 <= M <= 160, N % 16 == 0, K % 128 == 0 (w8) / K % 256 == 0 (w4), else PSG_ERR_UNSUPPORTED without a launch.  fp32
+ * slices part[slots][M][N], slots <= 16, k-ordered, no atomics, unused slots zero-filled: exactly the consumers of
+ * psg_batch_gemm / psg_skinny_gemm read them; nothing past slots * M * N floats is written.  The k range of every slot is
+ * a function of (N, K, mode) and the entry ONLY - not of M, not of the other rows: rows 0..32 of a 160-row call are
+ * bit-equal to the same rows of a 33-row call.  `slots` must be what the plan entry returns; mode as the w8 family's. */
+int psg_batch_gemm_w8_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
+int psg_batch_gemm_w8(psg_ctx*, const void* x, const void* w8, const float* col_scale, float* part, int M, int N, int K,
+                      int slots, int dtype, int mode, void* stream);
+int psg_batch_split_gemm_w8_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_batch_split_gemm_w8(psg_ctx*, const void* x2, const float* inv_scale, const void* w8, const float* col_scale,
+                            float* part, int M, int N, int K, int slots, int mode, void* stream);
+int psg_batch_gemm_w4_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
+int psg_batch_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img, const float* col_scale, float* part, int M,
+                      int N, int K, int slots, int dtype, int mode, void* stream);
+int psg_batch_split_gemm_w4_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_batch_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const void* w4, const void* e_img,
+                            const float* col_scale, float* part, int M, int N, int K, int slots, int mode, void* stream);
 /* The dense operand of a quantised matrix, rebuilt from its bytes (an engine that keeps only the bytes resident
  * expands a matrix into a scratch buffer right before the one large-M product that reads it).  q: e4m3fn bytes [N][K]
  * (psg_expand_w8) or fp4 nibbles [N][K / 2], the low nibble the even k, with the RAW block exponents e uint8 [N][K / 32] in

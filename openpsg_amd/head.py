@@ -242,6 +242,10 @@ class RelationTransformerHeadV4(nn.Module):
                                                # pass).  'quantised': the bytes, exponents and row scales ONLY - dense operands
                                                # are rebuilt into a scratch buffer right before each product of more than 32
                                                # rows (psg_expand_w8 / _w4), bit for bit the ones 'all' stores; inference only
+                 llm_batch_weight_stream='dense',   # 'dense' | 'quantised': what forward_batch's decode steps of 33..160 rows
+                                               # read of a quantised LLM.  'dense': W' (today's launches).
+                                               # 'quantised': the bytes / nibbles, on psg_batch_gemm_q.hip - 1 / 0.53 bytes per
+                                               # weight, and no expansion per step with llm_weight_resident='quantised'
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -263,6 +267,12 @@ class RelationTransformerHeadV4(nn.Module):
             raise PsgHipError(f"llm_weight_resident='quantised' is about the LLM's weights; rel_cls_type={rel_cls_type!r} has no "
                               "LLM stage")
         self.llm_weight_resident = llm_weight_resident
+        if llm_batch_weight_stream not in ("dense", "quantised"):
+            raise PsgHipError(f"llm_batch_weight_stream must be 'dense' or 'quantised', got {llm_batch_weight_stream!r}")
+        if llm_batch_weight_stream == "quantised" and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_batch_weight_stream='quantised' is about the LLM's weights; rel_cls_type={rel_cls_type!r} "
+                              "has no LLM stage")
+        self.llm_batch_weight_stream = llm_batch_weight_stream
         if llm_quantize_lm_head and llm_weight_quant is None:
             raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4'")
         self.llm_weight_quant = llm_weight_quant
@@ -340,6 +350,10 @@ class RelationTransformerHeadV4(nn.Module):
             tokenizers = self.default_tokenizers
         self.llm_model_name = llm_model_name
         pretrained_dir = bool(load_pretrained_llm) and is_hf_checkpoint_dir(llm_model_name)
+        if llm_batch_weight_stream == "quantised" and llm_weight_quant is None and not pretrained_dir:
+            # (a checkpoint directory may hold a quantised model: the engine refuses it at load time if it does not)
+            raise PsgHipError("llm_batch_weight_stream='quantised' streams a quantised LLM's bytes: set llm_weight_quant='fp8' / "
+                              "'mxfp4' or load an FP8 / MXFP4 checkpoint directory")
         if llm_config is not None:
             llm = llm_config
         elif pretrained_dir:
@@ -484,7 +498,8 @@ class RelationTransformerHeadV4(nn.Module):
         w["language_projection.bias"] = self.language_projection.bias.data
         self._llm_engine = LlamaDecodeEngine(w, self.cfg, self.device, self.act_dtype, n_layers=n_layers,
                                              resid_dtype=self.resid_dtype, prefill_split=self.prefill_split,
-                                             resident=self.llm_weight_resident)
+                                             resident=self.llm_weight_resident,
+                                             batch_quant_stream=self.llm_batch_weight_stream == "quantised")
         return self
 
     def quantize_llm_weights(self, weights: dict) -> dict:

@@ -219,6 +219,43 @@ def _measure_batch_plan(x, pool):
     return best
 
 
+# Decode steps with 33..160 rows over a QUANTISED matrix, engine option batch_quant_stream: psg_batch_gemm_q.hip
+# streams the bytes / nibbles where the steps above run on the dense W'.  Like _BATCH_PLAN_TABLE a FIXED table, never a
+# per-process measurement: a listed row range sends a measured loser (tools/batch_quant_bench.py: the stream's range of
+# times not wholly below the dense path's) back to the dense path; a shape that is not listed streams.
+#   key: (format 'fp8' / 'mxfp4', form 'single' / 'pair', N, K) -> [(rows from, rows below), ...]
+# resident='quantised' never consults it: there the alternative is the expansion plus the dense product.
+# Measured at the Llama-2-7B shapes and 40 / 80 / 160 rows = 2 / 3 / 5 x tiles (profiles/batch_quant_bench.json; the row
+# ranges are those of the tile counts: 33..64, 65..96, 97..160).  The pair form (fp32s, against the library SGEMM on fp32
+# W') wins by 1.08-3.9 x everywhere but o in fp8 at 40 rows (level).  The single form meets 2-byte paths that stream at
+# 2-3 TB/s and is matrix-core bound from 80 rows on: it keeps q|k|v (and mxfp4 gate|up) up to 64 rows, down from 97 rows
+# (mxfp4: up to 64 as well) and the lm_head up to 96 rows (fp8: 65..96).
+_BATCH_QUANT_DENSE: dict = {
+    ("fp8", "single", 12288, 4096): [(65, 161)],               # q|k|v: 31.2 / 42.0 us against the library's 29.1 / 37.3
+    ("fp8", "single", 4096, 4096): [(33, 161)],                # o: 11.3 / 25.2 / 20.8 against 10.0 / 16.6 / 19.1
+    ("fp8", "pair", 4096, 4096): [(33, 65)],                   # o, 40 rows: 24.9 (24.3-25.1) against 24.9 (24.0-26.4): overlap
+    ("fp8", "single", 22016, 4096): [(33, 161)],               # gate|up, 40 rows: 37.2 (36.3-40.7) against 39.6 (38.9-42.2): overlap
+    # down, 40 rows: 19.8 (19.4-20.5) against 20.8 (20.5-21.0): overlap.  65..96 rows (both formats): 2.6 us ahead per launch,
+    # but a `mixed` step of 4 images in which down was the only matrix that streamed ran 0.4-1.2 ms per batch BEHIND the
+    # option-off step (mxfp4: disjoint ranges; DESIGN 16, whole step)
+    ("fp8", "single", 4096, 11008): [(33, 97)],
+    ("fp8", "single", 32000, 4096): [(33, 65), (97, 161)],     # lm_head: 49.5 (48.2-52.6) against 51.7: overlap; 160 rows: 75.3 against 62.2
+    ("mxfp4", "single", 12288, 4096): [(65, 161)],
+    ("mxfp4", "single", 4096, 4096): [(33, 161)],
+    ("mxfp4", "single", 22016, 4096): [(65, 161)],
+    ("mxfp4", "single", 4096, 11008): [(65, 97)],
+    ("mxfp4", "single", 32000, 4096): [(97, 161)],
+}
+
+
+def _batch_quant_route(fmt, form, N, K, rows, table=None):
+    """'stream' or 'dense' for a decode projection of `rows` rows over a quantised [N, K] matrix."""
+    for lo, hi in (_BATCH_QUANT_DENSE if table is None else table).get((fmt, form, int(N), int(K)), ()):
+        if lo <= rows < hi:
+            return "dense"
+    return "stream"
+
+
 class QuantMatrix:
     """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
     `lm_head` hold in place of W'.  Carries the shape and dtype W' would have and the quantised parts - (q, s) for FP8,
@@ -246,12 +283,14 @@ class QuantMatrix:
 
 class LlamaDecodeEngine:
     def __init__(self, weights: dict, cfg: PSGConfig, device, dtype=torch.bfloat16, n_layers=None, resid_dtype=None,
-                 prefill_split=False, resident="all"):
+                 prefill_split=False, resident="all", batch_quant_stream=False):
         """prefill_split (fp32 engines): the prompt pass's projections as split-fp16 products on the 16-bit matrix cores,
         `linear_split` below; the decode steps stay exact fp32 (psg_gemm_f32.hip).
         resid_dtype: storage type of the residual stream; None = `dtype` (what HF keeps for a model cast to 16
         bits), torch.float32 with a 16-bit `dtype` = mixed mode (16-bit GEMM operands, the residual stream - the sum
-        of 2 x layers updates - never rounded to 16 bits; costs 160 KB more traffic per decode row kernel)."""
+        of 2 x layers updates - never rounded to 16 bits; costs 160 KB more traffic per decode row kernel).
+        batch_quant_stream: decode steps of 33..160 rows stream a quantised matrix's bytes (`_batch_quant`)
+        instead of reading W'."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
         if resident not in ("all", "quantised"):
@@ -411,6 +450,10 @@ class LlamaDecodeEngine:
         self._w4_layers = n_q4 > 0                               # ... as nibbles (or, per shape, as their exact FP8 image)
         self.use_skinny = True
         self.prefill_split = bool(prefill_split) and dtype == torch.float32
+        self.batch_quant_stream = bool(batch_quant_stream)
+        if self.batch_quant_stream and not (self._w8 or self._w4):
+            raise PsgHipError("batch_quant_stream streams a quantised LLM's bytes in the batched decode, and no matrix of this "
+                              "model is quantised: set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint")
         # fp32 engines: are the projection weights fp16 VALUES?  The reference's LLM is the frozen Llama-2-7b-hf checkpoint
         # (fp16 on disk, configs/psg/baseline_v4_ov.py:61-65) upcast by from_pretrained (V4:99-100): if every element of
         # every projection round-trips through fp16, the decode steps stream an fp16 copy - half the HBM bytes - instead
@@ -640,11 +683,12 @@ class LlamaDecodeEngine:
             t = self._ones_cache[n] = torch.ones(n, device=self.device, dtype=torch.float32)
         return t
 
-    def linear(self, x, w, ws=None, decode=False):
+    def linear(self, x, w, ws=None, decode=False, batch_stream=True):
         """Bias-free projection.  Decode-step shapes (<= 32 rows) use the hand-written weight-streaming kernel - in
         the 16-bit modes and in the fp32 mode (the reference's own precision, V4:99-100) alike; the prompt pass goes
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
-        psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm)."""
+        psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm) - or, with
+        batch_quant_stream, over a quantised matrix's bytes (`_batch_quant`; batch_stream=False: the caller keeps W')."""
         w8 = self._w8.get(w.data_ptr()) if self._w8 else None
         if (w8 is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and w.shape[0] % 16 == 0
                 and w.shape[1] % 128 == 0 and (self.prefill_split or x.dtype != torch.float32)):
@@ -662,6 +706,11 @@ class LlamaDecodeEngine:
                 x2, inv = ops.split_f16x2(x)
                 return ops.split_gemm_w4(x2, inv, *w4)
             return ops.skinny_gemm_w4(x, *w4)
+        if (self.batch_quant_stream and batch_stream and decode and self.use_skinny and 32 < x.shape[0] <= 160 and x.dtype == w.dtype
+                and (w8 is not None or w4 is not None) and (self.prefill_split or x.dtype != torch.float32)):
+            out = self._batch_quant(x, w, w8, w4)
+            if out is not None:
+                return out
         w = self._dense(w)                                    # (resident='quantised': W' expanded into the slot's scratch)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
@@ -698,6 +747,28 @@ class LlamaDecodeEngine:
             return self.linear_split(x, ws, w)
         return F.linear(x, w)
 
+    def _batch_quant(self, x, w, w8, w4):
+        """Decode projection of 33..160 rows over a quantised matrix on its byte / nibble stream (psg_batch_gemm_q.hip,
+        DESIGN 16): fp32 slices for the consumers of `ops.batch_gemm`, or None where the shape does not fit the kernels or
+        the routing table sends it to the dense path.  fp32s rows go through `split_f16x2` and the pair form, 16-bit rows
+        take the single form.  A matrix with an FP8 image (FP8 itself, or a W4_STREAM_AS_FP8 shape) streams that, as below
+        33 rows."""
+        rows, (N, K) = int(x.shape[0]), w.shape
+        if w8 is not None and K % 128 == 0:
+            fmt, args = "fp8", w8
+        elif w4 is not None and w4[1] is not None:
+            fmt, args = "mxfp4", w4
+        else:
+            return None
+        pair = x.dtype == torch.float32
+        if N % 16 or (self.resident != "quantised"
+                      and _batch_quant_route(fmt, "pair" if pair else "single", N, K, rows) == "dense"):
+            return None
+        if pair:
+            x2, inv = ops.split_f16x2(x)
+            return (ops.batch_split_gemm_w8 if fmt == "fp8" else ops.batch_split_gemm_w4)(x2, inv, *args)
+        return (ops.batch_gemm_w8 if fmt == "fp8" else ops.batch_gemm_w4)(x, *args)
+
     def decode_uses_library(self, rows) -> bool:
         """Does a decode step of `rows` rows run a library GEMM?  Above 32 rows, without the weight-streaming kernel, or
         when a projection's K slice does not fit it at this row count (`_streams`: fp32 at K = 14336, Mistral-7B's
@@ -711,11 +782,12 @@ class LlamaDecodeEngine:
         ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
         return not all(self._streams(rows, w, self.dtype) for w in ws)
 
-    def logits(self, h):
+    def logits(self, h, batch_stream=True):
         """lm_head.  <= 32 rows: the weight-streaming kernel (fp32 split-K partials, summed inside the greedy step);
         more rows (several images' pairs decoded together): the library GEMM with an fp32 result, so that the greedy
-        argmax sees unrounded logits on this path too (exact_argmax)."""
-        out = self.linear(h, self.lm_head, decode=True)
+        argmax sees unrounded logits on this path too (exact_argmax) - or, with batch_quant_stream and a quantised
+        lm_head, the fp32 slices of its byte stream (batch_stream=False, the trie pass: never)."""
+        out = self.linear(h, self.lm_head, decode=True, batch_stream=batch_stream)
         if isinstance(out, ops.Partials) or not self.exact_argmax or h.dtype == torch.float32:
             return out
         return self._lm_head_f32(h, out)
@@ -1295,7 +1367,7 @@ class LlamaDecodeEngine:
                     rope_bound=int(maxlen + trie.max_depth))
         h = self._forward(resid, row_pair, tok_pos, kc, vc, ctx_len, rope_pos=rope_pos, tree=tree)
         if h.dtype == torch.float32:
-            logits = self.logits(h)
+            logits = self.logits(h, batch_stream=False)
         else:                                                  # fp32 logits of the 16-bit modes, ONE product (`logits` would
             logits = self._lm_head_f32(h)                      # run the 16-bit product first and discard it)
         row_out = (row_pair.to(torch.int64) * (E + 1) + T["child_off"][(row_node + 1).long()].to(torch.int64)).contiguous()

@@ -947,6 +947,65 @@ def batch_gemm(x, w, slab_rows=0, mode=0) -> Partials:
     return Partials(part)
 
 
+def _batch_q(entry, x, planes, args, M, N, K, mode):
+    """Plan + launch of one psg_batch_*_w8 / _w4 entry: `args` = the pointers between ctx and `part`."""
+    import ctypes
+    lib, ctx, st = _env(x)
+    s = ctypes.c_int(0)
+    dt = () if planes else (_dt(x),)
+    check(getattr(lib, f"psg_{entry}_plan")(ctx, M, N, K, *dt, int(mode), ctypes.byref(s)), f"psg_{entry}_plan")
+    part = torch.empty((s.value, M, N), device=x.device, dtype=torch.float32)
+    check(getattr(lib, f"psg_{entry}")(ctx, *args, _p(part), M, N, K, s.value, *dt, int(mode), st), f"psg_{entry}")
+    return Partials(part)
+
+
+def batch_gemm_w8(x, w8, col_scale, mode=0) -> Partials:
+    """`batch_gemm` for 33..160 bf16 / fp16 rows over an FP8-quantised weight W' = e4m3(w8) * col_scale[:, None]: one byte
+    per weight from HBM, `skinny_gemm_w8`'s arithmetic; fp32 slices [S, M, N] of (x . q) * col_scale (psg_batch_gemm_w8).
+    K % 128 == 0.  A row's slices do not depend on M or on the other rows."""
+    M, K = x.shape
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise PsgHipError(f"batch_gemm_w8: x must be bf16 or fp16, got {x.dtype}")
+    N = _w8_args("batch_gemm_w8", w8, col_scale, K)
+    return _batch_q("batch_gemm_w8", x, False, (_p(x, name="x"), _p(w8, name="w8"), _p(col_scale)), M, N, K, mode)
+
+
+def _x2_args(name, x2, inv_scale):
+    if x2.dim() != 3 or x2.shape[0] != 2 or x2.dtype != torch.float16 or not x2.is_contiguous():
+        raise PsgHipError(f"{name}: x2 must be the fp16 planes [2, M, K] of split_f16x2, got {x2.dtype} {tuple(x2.shape)}")
+    if inv_scale.dtype != torch.float32 or tuple(inv_scale.shape) != (x2.shape[1],):
+        raise PsgHipError(f"{name}: inv_scale must be fp32 [{x2.shape[1]}], got {inv_scale.dtype} {tuple(inv_scale.shape)}")
+    return x2.shape[1], x2.shape[2]
+
+
+def batch_split_gemm_w8(x2, inv_scale, w8, col_scale, mode=0) -> Partials:
+    """`split_gemm_w8` for 33..160 fp32 rows given as the planes of `split_f16x2`: fp32 slices [S, M, N] of
+    (xh . q + xl . q) * inv_scale * col_scale (psg_batch_split_gemm_w8).  K % 128 == 0."""
+    M, K = _x2_args("batch_split_gemm_w8", x2, inv_scale)
+    N = _w8_args("batch_split_gemm_w8", w8, col_scale, K)
+    return _batch_q("batch_split_gemm_w8", x2, True, (_p(x2), _p(inv_scale), _p(w8, name="w8"), _p(col_scale)), M, N, K, mode)
+
+
+def batch_gemm_w4(x, w4, e_img, col_scale, mode=0) -> Partials:
+    """`batch_gemm_w8` over an MXFP4-quantised weight (see `split_gemm_w4`; `e_img` = mxfp4_exp_image(e)): fp32 slices
+    [S, M, N] of (x . w) * col_scale (psg_batch_gemm_w4).  K % 256 == 0."""
+    M, K = x.shape
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise PsgHipError(f"batch_gemm_w4: x must be bf16 or fp16, got {x.dtype}")
+    N = _w4_args("batch_gemm_w4", w4, e_img, col_scale, K)
+    return _batch_q("batch_gemm_w4", x, False, (_p(x, name="x"), _p(w4, name="w4"), _p(e_img, name="e_img"), _p(col_scale)),
+                    M, N, K, mode)
+
+
+def batch_split_gemm_w4(x2, inv_scale, w4, e_img, col_scale, mode=0) -> Partials:
+    """`batch_split_gemm_w8` over an MXFP4-quantised weight: fp32 slices [S, M, N] of (xh . w + xl . w) * inv_scale *
+    col_scale (psg_batch_split_gemm_w4).  K % 256 == 0."""
+    M, K = _x2_args("batch_split_gemm_w4", x2, inv_scale)
+    N = _w4_args("batch_split_gemm_w4", w4, e_img, col_scale, K)
+    return _batch_q("batch_split_gemm_w4", x2, True,
+                    (_p(x2), _p(inv_scale), _p(w4, name="w4"), _p(e_img, name="e_img"), _p(col_scale)), M, N, K, mode)
+
+
 def skinny_gemm_fused(kind, x_out, w, sync, *, inp=None, resid=None, norm_w=None, eps=0.0, attn=None, splits=None):
     """Decode projection with its producer row operation in the same launch (psg_skinny_gemm_fused):
     the prologue `kind` computes x_out [M, K] from `inp` (Partials / activation tensor / None), then

@@ -56,6 +56,9 @@ def parser():
                     help="quantised: a quantised LLM (--llm-weight-quant, or an FP8 / MXFP4 checkpoint in --llm-dir) keeps only "
                     "its bytes, exponents and row scales in HBM; dense operands are rebuilt into a scratch buffer right before "
                     "each product of more than 32 rows (same results bit for bit, inference only)")
+    ap.add_argument("--llm-batch-weight-stream", choices=["dense", "quantised"], default="dense",
+                    help="quantised: decode steps of 33..160 rows (several images decoded together) stream a quantised LLM's "
+                    "bytes / nibbles instead of its dense weights, and never expand them with --llm-weight-resident quantised")
     return ap
 
 
@@ -72,7 +75,8 @@ def build_head(a, dev):
                                          llm_model_name=a.llm_dir, llm_feature_size=llm.hidden, llm_truncate_num=trunc,
                                          on_parse_error="skip", pair_selector=a.selector,
                                          llm_weight_quant=getattr(a, "llm_weight_quant", None),
-                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"))
+                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
+                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
     else:
@@ -81,7 +85,8 @@ def build_head(a, dev):
         head = RelationTransformerHeadV4(dtype=a.dtype, device=str(dev), tokenizers="word", max_object_num=a.objects,
                                          llm_config=llm, on_parse_error="skip", pair_selector=a.selector,
                                          llm_weight_quant=getattr(a, "llm_weight_quant", None),
-                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"))
+                                         llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
+                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
