@@ -76,8 +76,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   606  MXFP4-quantised LLM weights: psg_split_gemm_w4(_plan), psg_skinny_gemm_w4(_plan) added
  *   607  quantised matrices as the only resident copy: psg_expand_w8, psg_expand_w4 added
  *   608  quantised weights in the batched decode: psg_batch_gemm_w8(_plan), psg_batch_split_gemm_w8(_plan),
- *        psg_batch_gemm_w4(_plan), psg_batch_split_gemm_w4(_plan) added */
-#define PSG_ABI_VERSION 608
+ *        psg_batch_gemm_w4(_plan), psg_batch_split_gemm_w4(_plan) added
+ *   609  group-wise INT4 LLM weights (GPTQ / AWQ): psg_split_gemm_int4(_plan), psg_skinny_gemm_int4(_plan) added */
+#define PSG_ABI_VERSION 609
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -393,6 +394,24 @@ int psg_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const vo
 int psg_skinny_gemm_w4_plan(psg_ctx*, int M, int N, int K, int dtype, int mode, int* slots);
 int psg_skinny_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img, const float* col_scale, float* part, int M,
                        int N, int K, int slots, int dtype, int mode, void* stream);
+/* The same projections over a group-wise INT4 weight (GPTQ / AWQ checkpoints): W'[n][k] = float(gs[n][k / 128]) *
+ * (q[n][k] - gz[n][k / 128]) (openpsg_amd/weights.py dequantize_int4_groups), 4-bit codes q, one fp16 scale and one 4-bit zero
+ * point per 128 weights of a row.  Both operands come RE-LAID-OUT for the kernel (psg_gemm_int4.hip's header has the
+ * orders): q_img uint8 [N][K / 2] = ops.int4_q_image(q), the codes of 8 consecutive k permuted within their dword;
+ * g_img uint8 [K / 256][N][8] = ops.int4_group_image(gs, gz): the two fp16 scales, then the two zero points of the row's
+ * groups in unit t, then two zero bytes.  4.25 bits per weight stream from HBM ONCE per call; the codes are widened to the
+ * exact integers q - z in the x operand's 16-bit type, multiplied on the 16-bit matrix cores with fp32 accumulation, and
+ * each group's partial sum is scaled by gs in fp32 inside the K loop.  The PAIR form's inv_scale is applied at the slice
+ * store; there is no column scale.
+ *   psg_split_gemm_int4 (fp32s): x2 / inv_scale as psg_split_gemm_w16's;  psg_skinny_gemm_int4: x [M][K] bf16 / fp16.
+ * M <= 32, N % 16 == 0, K % 256 == 0, group == 128, x / q_img / g_img 16-byte aligned, else PSG_ERR_UNSUPPORTED without a
+ * launch.  Slices, plan entries and modes as the w8 family's. */
+int psg_split_gemm_int4_plan(psg_ctx*, int M, int N, int K, int group, int mode, int* slots);
+int psg_split_gemm_int4(psg_ctx*, const void* x2, const float* inv_scale, const void* q_img, const void* g_img, float* part,
+                        int M, int N, int K, int group, int slots, int mode, void* stream);
+int psg_skinny_gemm_int4_plan(psg_ctx*, int M, int N, int K, int group, int dtype, int mode, int* slots);
+int psg_skinny_gemm_int4(psg_ctx*, const void* x, const void* q_img, const void* g_img, float* part, int M, int N, int K,
+                         int group, int slots, int dtype, int mode, void* stream);
 /* The w8 / w4 projections for 33 <= M <= 160 rows (several images' pairs decoded together over a quantised
  * LLM).  Operands, weight model and arithmetic are exactly those of the four entries above - w8 + col_scale, w4 + e_img +
  * col_scale, exact widening in registers, 16-bit matrix cores, fp32 accumulation, the scales applied once in fp32 at the

@@ -56,6 +56,11 @@ __device__ __forceinline__ uint32_t psg_lds_read32(uint32_t a) {
   asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(a) : "memory");
   return v;
 }
+__device__ __forceinline__ psg_u32x2 psg_lds_read64(uint32_t a) {
+  psg_u32x2 v;
+  asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"(a) : "memory");
+  return v;
+}
 __device__ __forceinline__ void psg_lds_write64(uint32_t a, psg_u32x2 v) {
   asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(v) : "memory");
 }

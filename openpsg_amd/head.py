@@ -236,6 +236,10 @@ class RelationTransformerHeadV4(nn.Module):
                                                # 'mxfp4': OCP Microscaling FP4, two E2M1 codes per byte + one exponent byte per 32 k
                                                # + one fp32 scale per row (weights.quantize_mxfp4_rows): 4.25 bits
                                                # per weight in those steps, W' = fp4(q) 2^(e - 127) s likewise
+                                               # 'int4g': group-wise INT4 as GPTQ / AWQ checkpoints hold it - 4-bit codes, one fp16
+                                               # scale and one 4-bit zero point per 128 weights of a row
+                                               # (weights.quantize_int4_groups): 4.25 bits per weight in those steps,
+                                               # W' = gs (q - gz); a GPTQ / AWQ checkpoint directory is taken as it is
                  llm_quantize_lm_head=False,   # quantised: the lm_head as well (never the embedding, norms, language_projection)
                  llm_weight_resident='all',    # 'all' | 'quantised': what a quantised LLM keeps in HBM.  'all': W' in
                                                # the engine's dtype beside the bytes (+ the fp16 image of the fp32s prompt
@@ -256,8 +260,9 @@ class RelationTransformerHeadV4(nn.Module):
                               "offered: 'If use fp16, the loss will be nan', V4)")
         self.train_precision = train_precision
         self._train_llm_copy = None
-        if llm_weight_quant not in (None, "fp8", "mxfp4"):
-            raise PsgHipError(f"llm_weight_quant must be None, 'fp8' or 'mxfp4', got {llm_weight_quant!r}")
+        if llm_weight_quant not in (None, "fp8", "mxfp4", "int4g"):
+            raise PsgHipError(f"llm_weight_quant must be None, 'fp8', 'mxfp4' or 'int4g', got {llm_weight_quant!r}" +
+                              (" (group-wise INT4 is spelled 'int4g')" if llm_weight_quant == "int4" else ""))
         if llm_weight_quant is not None and "binary" not in rel_cls_type:
             raise PsgHipError(f"llm_weight_quant={llm_weight_quant!r} quantises the LLM; rel_cls_type={rel_cls_type!r} has no "
                               "LLM stage")
@@ -274,7 +279,14 @@ class RelationTransformerHeadV4(nn.Module):
                               "has no LLM stage")
         self.llm_batch_weight_stream = llm_batch_weight_stream
         if llm_quantize_lm_head and llm_weight_quant is None:
-            raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4'")
+            raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4' or 'int4g'")
+        # group-wise INT4 has the decode kernels of <= 32 rows only: no expand kernel, no 33..160-row kernel
+        if llm_weight_quant == "int4g" and llm_weight_resident == "quantised":
+            raise PsgHipError("llm_weight_resident='quantised' is not built for the INT4 format (llm_weight_quant='int4g'): "
+                              "there is no expand kernel for it - use llm_weight_resident='all'")
+        if llm_weight_quant == "int4g" and llm_batch_weight_stream == "quantised":
+            raise PsgHipError("llm_batch_weight_stream='quantised' is not built for the INT4 format (llm_weight_quant='int4g'): "
+                              "there is no 33..160-row kernel for it - use llm_batch_weight_stream='dense'")
         self.llm_weight_quant = llm_weight_quant
         self.llm_quantize_lm_head = bool(llm_quantize_lm_head)
         if rel_cls_type not in REL_CLS_TYPES:
@@ -353,7 +365,7 @@ class RelationTransformerHeadV4(nn.Module):
         if llm_batch_weight_stream == "quantised" and llm_weight_quant is None and not pretrained_dir:
             # (a checkpoint directory may hold a quantised model: the engine refuses it at load time if it does not)
             raise PsgHipError("llm_batch_weight_stream='quantised' streams a quantised LLM's bytes: set llm_weight_quant='fp8' / "
-                              "'mxfp4' or load an FP8 / MXFP4 checkpoint directory")
+                              "'mxfp4' or load an FP8 / MXFP4 checkpoint directory ('int4g' has no such kernel)")
         if llm_config is not None:
             llm = llm_config
         elif pretrained_dir:
@@ -480,12 +492,17 @@ class RelationTransformerHeadV4(nn.Module):
                    not (".layers." in k and int(k.split(".layers.")[1].split(".")[0]) >= n_layers)]
         if missing:
             raise PsgHipError(f"LLM weights missing {len(missing)} tensors, e.g. {missing[:3]}")
-        def stored(k):                                  # an MXFP4 matrix [N, K] comes as two codes per byte: [N, K / 2]
-            return (need[k][0], need[k][1] // 2) if k + "_bexp" in weights else need[k]
+        def stored(k):                                  # an MXFP4 / INT4 matrix [N, K] comes as two codes per byte: [N, K / 2]
+            return (need[k][0], need[k][1] // 2) if k + "_bexp" in weights or k + "_gscale" in weights else need[k]
         wrong = [(k, tuple(weights[k].shape), stored(k)) for k in need if k in weights and tuple(weights[k].shape) != stored(k)]
         if wrong:                                       # e.g. a grouped-query checkpoint under a multi-head config
             raise PsgHipError(f"LLM weights of the wrong shape ({len(wrong)}), e.g. {wrong[:2]} "
                               f"({self.cfg.llm.heads} query / {self.cfg.llm.n_kv_heads} key-value heads)")
+        if any(k.endswith("_gscale") for k in weights) and (self.llm_weight_resident == "quantised"
+                                                            or self.llm_batch_weight_stream == "quantised"):
+            opt = "llm_weight_resident" if self.llm_weight_resident == "quantised" else "llm_batch_weight_stream"
+            raise PsgHipError(f"{opt}='quantised' is not built for the INT4 format (a GPTQ / AWQ checkpoint): there is no "
+                              "expand kernel and no 33..160-row kernel for it")
         if self.llm_weight_resident == "quantised":
             # the dense model never reaches the device: a matrix is quantised where it lives, uploaded and dropped when the
             # engine asks for it (peak = the final footprint + the pieces of one matrix in flight)
@@ -505,8 +522,8 @@ class RelationTransformerHeadV4(nn.Module):
     def quantize_llm_weights(self, weights: dict) -> dict:
         """What `load_llm_weights` hands the decode engine: with llm_weight_quant='fp8' every q/k/v/o/gate/up/down matrix
         of the kept layers (+ the lm_head with llm_quantize_lm_head) as (e4m3fn bytes under its name, fp32 row scales
-        under name + '_scale'), with 'mxfp4' as (fp4 nibbles, name + '_bexp', name + '_scale'); matrices that already come
-        quantised are kept.  Otherwise a plain copy of the dict."""
+        under name + '_scale'), with 'mxfp4' as (fp4 nibbles, name + '_bexp', name + '_scale'), with 'int4g' as (4-bit codes,
+        name + '_gscale', name + '_gzero'); matrices that already come quantised are kept.  Otherwise a plain copy of the dict."""
         if self.llm_weight_quant is None:
             return dict(weights)
         from .weights import quantize_llm_weights

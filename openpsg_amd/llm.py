@@ -88,6 +88,12 @@ def _split_mm(a3, w3, plan=None, out_dtype=torch.float32):
 # weight and is kept for these shapes only
 W4_STREAM_AS_FP8 = {"pair": frozenset(), "single": frozenset()}
 
+# Group-wise INT4 shapes (N, K) that do NOT stream as codes (acceptance rule): a shape goes here when
+# tools/int4_bench.py measured psg_gemm_int4.hip's range of times not wholly below the range of what the engine runs for
+# the shape on W' without the stream (pair: the fp32 decode kernel, single: the 16-bit skinny kernel).  The engine then
+# runs it on W'; no image is kept for it
+INT4_STREAM_OFF = {"pair": frozenset(), "single": frozenset()}
+
 
 def _plan_split_mm(rows, w3, out_dtype=torch.float32, k3=False, pool=None):
     """The form the library product of this shape runs in: a pure function of the shape (`_SPLIT_PLAN_TABLE`; 'whole' for
@@ -329,10 +335,20 @@ class LlamaDecodeEngine:
         # exponent image, s) for the decode steps of <= 32 rows, `_w4h` the exact fp16 image of W' / s for the fp32s prompt
         # pass.  A shape of W4_STREAM_AS_FP8 (measured slower as nibbles than as bytes) gets its exact FP8 image in `_w8`
         # as well and streams through the FP8 kernels: the same W' bit for bit
-        from .weights import (BEXP_SUFFIX, SCALE_SUFFIX, dequantize_fp8_rows, dequantize_mxfp4_rows, mxfp4_as_fp8_rows,
-                              quant_format, _mxfp4_unscaled)
+        # Group-wise INT4 matrices (GPTQ / AWQ): `name` holds two 4-bit codes per byte, `name + '_gscale'` the fp16
+        # group scales gs, `name + '_gzero'` the zero points gz; W' = gs (q - gz) goes under the existing key likewise and
+        # `_wi4` keeps (the kernel's code image, its group image) for the decode steps of <= 32 rows - for groups of 128, K %
+        # 256 == 0 and shapes not in INT4_STREAM_OFF.  W' is no fp16 value (gs is an arbitrary fp16 number): the fp32s prompt
+        # pass runs on it as generic fp32 weights, the three-product split route - there is no two-plane image
+        from .weights import (BEXP_SUFFIX, GSCALE_SUFFIX, GZERO_SUFFIX, SCALE_SUFFIX, dequantize_fp8_rows, dequantize_int4_groups,
+                              dequantize_mxfp4_rows, is_quantized, mxfp4_as_fp8_rows, quant_format, _mxfp4_unscaled)
         self._w8, self._w8h = {}, {}
         self._w4, self._w4h = {}, {}
+        self._wi4, self._int4 = {}, set()                        # the INT4 streams / every INT4 matrix (data_ptr of W')
+        if any(str(k).endswith(GSCALE_SUFFIX) for k in weights.keys()) and (lean or batch_quant_stream):
+            opt = "resident='quantised'" if lean else "batch_quant_stream"
+            raise PsgHipError(f"{opt} is not built for the INT4 format: there is no expand kernel and no 33..160-row kernel "
+                              "for it")
         if lean:
             from .weights import llm_quant_keys
             dense = [k for k in llm_quant_keys(m.layers if n_layers is None else n_layers) if k + SCALE_SUFFIX not in weights]
@@ -383,7 +399,7 @@ class LlamaDecodeEngine:
         def matrix(*keys):
             """The (row-concatenated) matrix of `keys` in the engine's dtype; registers its byte stream when every part
             is quantised (per-row scales commute with the concatenation)."""
-            quant = [k + SCALE_SUFFIX in weights for k in keys]
+            quant = [is_quantized(weights, k) for k in keys]
             if any(quant) and not all(quant):
                 raise PsgHipError(f"{keys}: some parts are FP8-quantised and some are not")
             if lean and quant[0]:
@@ -391,8 +407,33 @@ class LlamaDecodeEngine:
             if not quant[0]:
                 return act(torch.cat([weights[k] for k in keys], 0) if len(keys) > 1 else weights[keys[0]])
             fmts = {quant_format(weights, k) for k in keys}
+            if len(fmts) > 1 and "int4" in fmts:
+                raise PsgHipError(f"{keys}: some parts are INT4-quantised and some FP8- / MXFP4-quantised")
             if len(fmts) > 1:
                 raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
+            if fmts == {"int4"}:
+                q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
+                gss = [weights[k + GSCALE_SUFFIX].to(self.device) for k in keys]
+                gzs = [weights[k + GZERO_SUFFIX].to(self.device) for k in keys]
+                N, K = q.shape[0], 2 * q.shape[1]
+                B = gss[0].shape[-1]
+                if (any(t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != B for t in gss) or B <= 0 or K % B
+                        or K // B not in (32, 64, 128)
+                        or any(z.dtype != torch.uint8 or z.shape != t.shape for z, t in zip(gzs, gss))
+                        or sum(t.shape[0] for t in gss) != N):
+                    raise PsgHipError(f"{keys}: group scales must be fp16 and zero points uint8 [{N} rows in all, K / G] with G "
+                                      f"in (32, 64, 128) and K = {K} (weights.quantize_int4_groups), got "
+                                      f"{[(t.dtype, tuple(t.shape)) for t in gss + gzs]}")
+                gs, gz = torch.cat(gss, 0).contiguous(), torch.cat(gzs, 0).contiguous()
+                absf = gs.float().abs()
+                if not bool(torch.isfinite(absf).all()) or bool((absf < 2.0 ** -14).any()) or int(gz.max()) > 15:
+                    raise PsgHipError(f"{keys}: group scales must be finite, normal fp16 numbers and zero points 0..15")
+                w = dequantize_int4_groups(q, gs, gz, dtype).contiguous()
+                self._int4.add(w.data_ptr())
+                if (K // B == 128 and K % 256 == 0 and N % 16 == 0
+                        and (N, K) not in INT4_STREAM_OFF["pair" if dtype == torch.float32 else "single"]):
+                    self._wi4[w.data_ptr()] = (ops.int4_q_image(q), ops.int4_group_image(gs, gz))
+                return w
             q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
             sc = torch.cat([weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1) for k in keys], 0)
             if sc.numel() != q.shape[0]:
@@ -426,7 +467,8 @@ class LlamaDecodeEngine:
             p = f"language_model.model.layers.{l}."
             for n, rows_ in (("q", m.hidden), ("k", m.kv_dim), ("v", m.kv_dim)):
                 shp = tuple(weights[p + f"self_attn.{n}_proj.weight"].shape)
-                if p + f"self_attn.{n}_proj.weight" + BEXP_SUFFIX in weights:      # (MXFP4: two codes per byte)
+                if (p + f"self_attn.{n}_proj.weight" + BEXP_SUFFIX in weights
+                        or p + f"self_attn.{n}_proj.weight" + GSCALE_SUFFIX in weights):   # (MXFP4 / INT4: two codes per byte)
                     shp = (shp[0], 2 * shp[1])
                 if shp != (rows_, m.hidden):
                     raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
@@ -439,6 +481,10 @@ class LlamaDecodeEngine:
                 ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
         layer_w = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
         n_q4 = sum(t.data_ptr() in self._w4 for t in layer_w)
+        n_qi = sum(t.data_ptr() in self._int4 for t in layer_w)
+        if n_qi and (n_qi < len(layer_w) or self._w8 or self._w4):
+            raise PsgHipError(f"{n_qi} of the {len(layer_w)} decoder-layer matrices are INT4-quantised: all or none, and one format")
+        self._wi4_layers = n_qi > 0 and all(t.data_ptr() in self._wi4 for t in layer_w)   # every layer matrix streams as codes
         n_q = sum(t.data_ptr() in self._w8 and t.data_ptr() not in self._w4 for t in layer_w)
         if n_q and n_q4:
             raise PsgHipError(f"{n_q} decoder-layer matrices are FP8-quantised and {n_q4} MXFP4-quantised: one format")
@@ -469,7 +515,7 @@ class LlamaDecodeEngine:
         if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
             tensors = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
             for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
-                if t.data_ptr() in self._w8 or t.data_ptr() in self._w4:   # (has its byte stream: never counted, `_w16_all` stays false)
+                if t.data_ptr() in self._w8 or t.data_ptr() in self._w4 or t.data_ptr() in self._int4:   # (has its byte stream: never counted, `_w16_all` stays false)
                     continue
                 h = t.half()
                 if torch.equal(h.float(), t):
@@ -590,7 +636,8 @@ class LlamaDecodeEngine:
         images); `total`.  KV caches and graph pools belong to a generation, not to the engine, and are not counted."""
         seen, quant = set(), 0
         for t in [p for w in self._quant_matrices() for p in w.parts()] + \
-                 [p for ent in list(self._w8.values()) + list(self._w4.values()) for p in ent if p is not None]:
+                 [p for ent in list(self._w8.values()) + list(self._w4.values()) + list(self._wi4.values()) for p in ent
+                  if p is not None]:
             if t.data_ptr() not in seen:
                 seen.add(t.data_ptr())
                 quant += t.numel() * t.element_size()
@@ -706,6 +753,15 @@ class LlamaDecodeEngine:
                 x2, inv = ops.split_f16x2(x)
                 return ops.split_gemm_w4(x2, inv, *w4)
             return ops.skinny_gemm_w4(x, *w4)
+        wi4 = self._wi4.get(w.data_ptr()) if self._wi4 else None
+        if (wi4 is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
+                and (self.prefill_split or x.dtype != torch.float32)):
+            # group-wise INT4 matrix, <= 32 rows: 4.25 bits per weight (psg_gemm_int4.hip; an image exists only for G = 128,
+            # K % 256 == 0, N % 16 == 0 and shapes outside INT4_STREAM_OFF)
+            if x.dtype == torch.float32:
+                x2, inv = ops.split_f16x2(x)
+                return ops.split_gemm_int4(x2, inv, *wi4)
+            return ops.skinny_gemm_int4(x, *wi4)
         if (self.batch_quant_stream and batch_stream and decode and self.use_skinny and 32 < x.shape[0] <= 160 and x.dtype == w.dtype
                 and (w8 is not None or w4 is not None) and (self.prefill_split or x.dtype != torch.float32)):
             out = self._batch_quant(x, w, w8, w4)
@@ -944,6 +1000,7 @@ class LlamaDecodeEngine:
     def _can_persist(self, rows, slot):
         m = self.cfg.llm
         return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32 and not self._w8 and not self._w4
+                and not self._int4
                 and self.kv is None                            # the persistent decoder layer is multi-head only
                 and ops.decode_layer_supported(rows, m.hidden, m.inter, m.heads, self.dtype, self.device))
 
@@ -1037,12 +1094,29 @@ class LlamaDecodeEngine:
         widened exactly to fp16 in registers, the same two fp16 products per projection."""
         return self._decode_step_wq(st)
 
+    def _can_int4(self, rows):
+        """fp32s decode steps over group-wise INT4 decoder layers, every one of which has its code stream (groups of 128, K %
+        256 == 0, none in INT4_STREAM_OFF): every projection as psg_split_gemm_int4, the row kernels writing the two-plane
+        operand directly (`_decode_step_int4`)."""
+        m = self.cfg.llm
+        return (self._wi4_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
+                and self.dtype == torch.float32 and m.hidden % 256 == 0 and m.inter % 256 == 0 and m.inter <= 16384
+                and m.hidden <= 8192 and m.vocab % 16 == 0)
+
+    def _decode_step_int4(self, st):
+        """`_decode_step_w4` over group-wise INT4 decoder layers: 4.25 bits per weight from HBM, the codes widened to the
+        exact integers q - z in fp16, the same two fp16 products per projection, each group's sum scaled in fp32."""
+        return self._decode_step_wq(st)
+
     def _split_mm_q(self, a2, inv, w):
         """The pair-form projection of a quantised matrix on the stream it has: FP8 bytes (an FP8 matrix, or the exact FP8
-        image of an MXFP4 shape that streams faster so) or MXFP4 nibbles."""
+        image of an MXFP4 shape that streams faster so), MXFP4 nibbles or INT4 codes."""
         w8 = self._w8.get(w.data_ptr())
         if w8 is not None:
             return ops.split_gemm_w8(a2, inv, *w8)
+        wi4 = self._wi4.get(w.data_ptr())
+        if wi4 is not None:
+            return ops.split_gemm_int4(a2, inv, *wi4)
         return ops.split_gemm_w4(a2, inv, *self._w4[w.data_ptr()])
 
     def _decode_step_wq(self, st):
@@ -1067,7 +1141,7 @@ class LlamaDecodeEngine:
                 a2, inv = ops.rmsnorm_split2(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
         head = self.lm_head.data_ptr()
         if ((head in self._w8 and self.lm_head.shape[1] % 128 == 0)
-                or (head in self._w4 and self._w4[head][1] is not None)):
+                or (head in self._w4 and self._w4[head][1] is not None) or head in self._wi4):
             a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
             return mm(a2, inv, self.lm_head)
         if head in self._w16:
@@ -1080,7 +1154,7 @@ class LlamaDecodeEngine:
     def _can_fuse(self, rows):
         m = self.cfg.llm
         D = m.hidden
-        return (bool(self.fuse_rowops) and not self._w8 and not self._w4 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
+        return (bool(self.fuse_rowops) and not self._w8 and not self._w4 and not self._int4 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
                 and self.resid_dtype == self.dtype and rows <= 32 and D in (1024, 4096) and m.inter >= 1024 and m.inter % 64 == 0
                 and m.vocab >= 1024 and m.vocab % 16 == 0)
 
@@ -1382,7 +1456,8 @@ class LlamaDecodeEngine:
         w16 = not persist and self._can_w16(st["x"].shape[0])
         w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])
         w4 = not persist and not w16 and not w8 and self._can_w4(st["x"].shape[0])
-        fused = not persist and not w16 and not w8 and not w4 and self._can_fuse(st["x"].shape[0]) and hi > lo
+        i4 = not persist and not w16 and not w8 and not w4 and self._can_int4(st["x"].shape[0])
+        fused = not persist and not w16 and not w8 and not w4 and not i4 and self._can_fuse(st["x"].shape[0]) and hi > lo
         if persist:                                            # one counter block per layer launch, zeroed once per call
             per_step = ops.decode_layer_counters(self.device) * len(self.layers)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
@@ -1401,6 +1476,8 @@ class LlamaDecodeEngine:
                 logits = self._decode_step_w8(st)
             elif w4:
                 logits = self._decode_step_w4(st)
+            elif i4:
+                logits = self._decode_step_int4(st)
             elif fused:
                 logits = self._decode_step_fused(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             else:

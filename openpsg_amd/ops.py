@@ -928,6 +928,83 @@ def skinny_gemm_w4(x, w4, e_img, col_scale, mode=0) -> Partials:
     return Partials(part)
 
 
+INT4_NIBBLE_OF_K = (0, 4, 1, 5, 2, 6, 3, 7)     # psg_gemm_int4.hip: the nibble of a dword of q_img that holds k = 8 d + e
+
+
+def int4_q_image(q) -> torch.Tensor:
+    """The codes q uint8 [N, K / 2] of a group-wise INT4 matrix (weights.quantize_int4_groups: two codes per byte, the low
+    nibble the even k), K % 8 == 0, re-laid-out for psg_gemm_int4.hip's unpack: uint8 [N, K / 2] in which the code of
+    k = 8 d + e sits in nibble INT4_NIBBLE_OF_K[e] of little-endian dword d of the row (nibble i = bits 4 i .. 4 i + 3)."""
+    if q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] % 4:
+        raise PsgHipError(f"int4_q_image: q must be uint8 [N, K / 2] with K % 8 == 0, got {q.dtype} {tuple(q.shape)}")
+    N, Kh = q.shape
+    codes = torch.stack((q & 15, q >> 4), dim=2).reshape(N, Kh // 4, 8)           # [n, d, e] = the code of k = 8 d + e
+    inv = sorted(range(8), key=lambda e: INT4_NIBBLE_OF_K[e])                      # nibble i holds e = inv[i]
+    nib = codes[:, :, inv].reshape(N, Kh, 2)
+    return (nib[:, :, 0] | (nib[:, :, 1] << 4)).contiguous()
+
+
+def int4_group_image(gs, gz) -> torch.Tensor:
+    """The group scales gs fp16 [N, K / 128] and zero points gz uint8 [N, K / 128] (0..15) of a group-wise INT4 matrix with
+    groups of 128, K % 256 == 0, re-laid-out for psg_gemm_int4.hip's K step of 256: uint8 [K / 256, N, 8], a row's 8 bytes =
+    the fp16 scales of groups 2 t and 2 t + 1 (little-endian), their zero points, two zero bytes.  The groups of 32
+    consecutive rows of one step are then 256 contiguous bytes (one LDS-DMA per wave) and a lane's one 8-byte read."""
+    if (gs.dtype != torch.float16 or gz.dtype != torch.uint8 or gs.dim() != 2 or gs.shape != gz.shape or gs.shape[1] % 2):
+        raise PsgHipError("int4_group_image: gs fp16 / gz uint8 [N, K / 128] with K % 256 == 0, got "
+                          f"{gs.dtype} {tuple(gs.shape)} / {gz.dtype} {tuple(gz.shape)}")
+    N, B = gs.shape
+    img = torch.zeros((B // 2, N, 8), dtype=torch.uint8, device=gs.device)
+    img[:, :, 0:4] = gs.contiguous().view(torch.uint8).reshape(N, B // 2, 4).permute(1, 0, 2)
+    img[:, :, 4:6] = gz.reshape(N, B // 2, 2).permute(1, 0, 2)
+    return img
+
+
+def _int4_args(name, q_img, g_img, K, group):
+    if q_img.dtype != torch.uint8 or q_img.dim() != 2 or q_img.shape[1] * 2 != K:
+        raise PsgHipError(f"{name}: q_img must be int4_q_image(q): uint8 [N, {K // 2}], got {q_img.dtype} {tuple(q_img.shape)}")
+    N = q_img.shape[0]
+    if K % 256 == 0 and group == 128 and (g_img.dtype != torch.uint8 or tuple(g_img.shape) != (K // 256, N, 8)):
+        raise PsgHipError(f"{name}: g_img must be int4_group_image(gs, gz): uint8 [{K // 256}, {N}, 8], got {g_img.dtype} "
+                          f"{tuple(g_img.shape)}")
+    return N
+
+
+def split_gemm_int4(x2, inv_scale, q_img, g_img, mode=0, group=128) -> Partials:
+    """`split_gemm_w4` over a group-wise INT4 weight W' = float(gs) * (q - gz) per group of 128 (weights.quantize_int4_groups /
+    a GPTQ or AWQ checkpoint; `q_img` = int4_q_image(q), `g_img` = int4_group_image(gs, gz)): 4.25 bits per weight from HBM,
+    the codes widened to the exact integers q - z in fp16, each group's partial sum scaled in fp32; fp32 slices [S, M, N] of
+    sum_g gs_g (xh . (q - z) + xl . (q - z))_g * inv_scale (psg_split_gemm_int4).  K % 256 == 0, group == 128.  mode 1 / 2:
+    slab-aligned / stream-K ranges, 0 = the library's estimate."""
+    import ctypes
+    lib, ctx, st = _env(x2)
+    _, M, K = x2.shape
+    assert x2.shape[0] == 2 and x2.dtype == torch.float16
+    N = _int4_args("split_gemm_int4", q_img, g_img, K, group)
+    s = ctypes.c_int(0)
+    check(lib.psg_split_gemm_int4_plan(ctx, M, N, K, int(group), int(mode), ctypes.byref(s)), "psg_split_gemm_int4_plan")
+    part = torch.empty((s.value, M, N), device=x2.device, dtype=torch.float32)
+    check(lib.psg_split_gemm_int4(ctx, _p(x2), _p(inv_scale, torch.float32), _p(q_img, name="q_img"), _p(g_img, name="g_img"),
+                                  _p(part), M, N, K, int(group), s.value, int(mode), st), "psg_split_gemm_int4")
+    return Partials(part)
+
+
+def skinny_gemm_int4(x, q_img, g_img, mode=0, group=128) -> Partials:
+    """`skinny_gemm_w4` of <= 32 bf16 / fp16 rows over a group-wise INT4 weight (see `split_gemm_int4`): fp32 slices
+    [S, M, N] of sum_g gs_g (x . (q - z))_g (psg_skinny_gemm_int4).  K % 256 == 0, group == 128."""
+    import ctypes
+    lib, ctx, st = _env(x)
+    M, K = x.shape
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise PsgHipError(f"skinny_gemm_int4: x must be bf16 or fp16, got {x.dtype}")
+    N = _int4_args("skinny_gemm_int4", q_img, g_img, K, group)
+    s = ctypes.c_int(0)
+    check(lib.psg_skinny_gemm_int4_plan(ctx, M, N, K, int(group), _dt(x), int(mode), ctypes.byref(s)), "psg_skinny_gemm_int4_plan")
+    part = torch.empty((s.value, M, N), device=x.device, dtype=torch.float32)
+    check(lib.psg_skinny_gemm_int4(ctx, _p(x, name="x"), _p(q_img, name="q_img"), _p(g_img, name="g_img"), _p(part), M, N, K,
+                                   int(group), s.value, _dt(x), int(mode), st), "psg_skinny_gemm_int4")
+    return Partials(part)
+
+
 def batch_gemm(x, w, slab_rows=0, mode=0) -> Partials:
     """Decode-step projection for 33..160 rows (several images' pairs decoded together): fp32 split-K slices of x @ w.T
     like `skinny_gemm`'s, the weight streamed from HBM once (psg_batch_gemm; bf16 / fp16).

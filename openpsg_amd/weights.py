@@ -234,11 +234,14 @@ def dequantize_fp8_rows(q: torch.Tensor, s: torch.Tensor, dtype=torch.float32) -
 
 
 def is_quantized(weights: dict, key: str) -> bool:
-    return key + SCALE_SUFFIX in weights
+    return key + SCALE_SUFFIX in weights or key + GSCALE_SUFFIX in weights
 
 
 def quant_format(weights: dict, key: str):
-    """None, 'fp8' or 'mxfp4': how the matrix `key` comes in `weights` (an MXFP4 matrix has its block exponents beside it)."""
+    """None, 'fp8', 'mxfp4' or 'int4': how the matrix `key` comes in `weights` (an MXFP4 matrix has its block exponents beside
+    it, a group-wise INT4 matrix its group scales and zero points)."""
+    if key + GSCALE_SUFFIX in weights:
+        return "int4"
     if not is_quantized(weights, key):
         return None
     return "mxfp4" if key + BEXP_SUFFIX in weights else "fp8"
@@ -347,6 +350,176 @@ def _take_mxfp4(out: dict, path):
     return out
 
 
+# ---- group-wise INT4 LLM matrices (GPTQ / AWQ checkpoints) ---------------------------------------------------
+# A matrix W [N, K] with group size G is (q, gs, gz) = (uint8 [N, K / 2]: two 4-bit codes per byte, the LOW nibble the even
+# k - MXFP4's storage order; fp16 [N, K / G]: finite, non-zero group scales; uint8 [N, K / G]: zero points 0..15) and its
+# value is
+#     W'[n, k] = float(gs[n, k // G]) * (q[n, k] - gz[n, k // G]):
+# the integer difference is exact, the product one fp32 rounding.  G in {32, 64, 128}, K % G == 0; it is K / gs.shape[1].
+# Groups lie within a row, so the model commutes with the engine's row concatenations (q|k|v, gate|up).
+GSCALE_SUFFIX = "_gscale"                                          # `<name>.weight` -> `<name>.weight_gscale`
+GZERO_SUFFIX = "_gzero"                                            # `<name>.weight` -> `<name>.weight_gzero`
+INT4_GROUPS = (32, 64, 128)
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)                               # AWQ gemm: nibble i of word m holds column 8 m + AWQ_ORDER[i]
+
+
+def _nearest_fp16(x: torch.Tensor) -> torch.Tensor:
+    """float64 x in [2^-14, 65504] -> the nearest fp16, ties to even, without the double rounding of a cast through fp32."""
+    c = x.to(torch.float32).to(torch.float16).view(torch.int16).to(torch.int32)
+    cand = torch.stack((c - 1, c, c + 1), dim=-1)                  # (positive: the neighbours are the bit patterns +- 1)
+    val = cand.to(torch.int16).view(torch.float16).to(torch.float64)
+    err = (val - x.unsqueeze(-1)).abs()
+    err = torch.where(torch.isfinite(val), err, torch.full_like(err, float("inf")))
+    tie = err == err.amin(dim=-1, keepdim=True)                    # (two candidates equally near: the even bit pattern)
+    pick = torch.where(tie & (cand % 2 == 0), 0, torch.where(tie, 1, 2)).argmin(dim=-1, keepdim=True)
+    return cand.gather(-1, pick).squeeze(-1).to(torch.int16).view(torch.float16)
+
+
+def _int4_group(name, K, n_groups):
+    if n_groups <= 0 or K % n_groups or K // n_groups not in INT4_GROUPS or K % (K // n_groups):
+        raise ValueError(f"{name}: K = {K} with {n_groups} groups per row (a group is one of {INT4_GROUPS} weights, K % G == 0)")
+    return K // n_groups
+
+
+def quantize_int4_groups(W: torch.Tensor, group: int = 128):
+    """W [N, K] -> (q uint8 [N, K / 2], gs fp16 [N, K / G], gz uint8 [N, K / G]): round to nearest, asymmetric, per (row,
+    group) in float64: lo = min(min w, 0), hi = max(max w, 0); s = (hi - lo) / 15 rounded to the nearest fp16 and clamped to
+    [2^-14, 65504]; with that s, z = clamp(rint(-lo / s), 0, 15) and q = clamp(rint(w / s) + z, 0, 15), rint ties to even.
+    An all-zero group gets s = 2^-14, z = 0, q = 0."""
+    if W.dim() != 2 or group not in INT4_GROUPS or W.shape[1] % group:
+        raise ValueError(f"quantize_int4_groups takes a matrix [N, K] with K % group == 0 and group in {INT4_GROUPS}, got shape "
+                         f"{tuple(W.shape)}, group {group}")
+    N, K = W.shape
+    Wg = W.to(torch.float64).reshape(N, K // group, group)
+    lo = Wg.amin(dim=2).clamp_max(0.0)
+    hi = Wg.amax(dim=2).clamp_min(0.0)
+    gs = _nearest_fp16(((hi - lo) / 15.0).clamp(2.0 ** -14, 65504.0))
+    s = gs.to(torch.float64)
+    z = torch.round(-lo / s).clamp_(0, 15)
+    code = (torch.round(Wg / s[:, :, None]) + z[:, :, None]).clamp_(0, 15).to(torch.uint8).reshape(N, K // 2, 2)
+    q = code[:, :, 0] | (code[:, :, 1] << 4)
+    return q.contiguous(), gs.contiguous(), z.to(torch.uint8).contiguous()
+
+
+def dequantize_int4_groups(q: torch.Tensor, gs: torch.Tensor, gz: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """W' = float32(gs) * (q - gz) per group (the difference exact, ONE fp32 rounding per element), then `dtype`."""
+    N, Kh = q.shape
+    K = 2 * Kh
+    G = _int4_group("dequantize_int4_groups", K, gs.shape[1])
+    if q.dtype != torch.uint8 or gs.dtype != torch.float16 or gz.dtype != torch.uint8 or tuple(gz.shape) != tuple(gs.shape) \
+            or gs.shape[0] != N:
+        raise ValueError(f"dequantize_int4_groups: q uint8 [N, K / 2], gs fp16 / gz uint8 [N, K / G], got {q.dtype} "
+                         f"{tuple(q.shape)}, {gs.dtype} {tuple(gs.shape)}, {gz.dtype} {tuple(gz.shape)}")
+    code = torch.stack((q & 15, q >> 4), dim=2).reshape(N, K // G, G).to(torch.float32)
+    return ((code - gz.to(torch.float32)[:, :, None]) * gs.to(torch.float32)[:, :, None]).reshape(N, K).to(dtype)
+
+
+def read_hf_quant_config(path):
+    """The weight-quantisation settings of a GPTQ / AWQ checkpoint directory: `quantization_config` of config.json, or the
+    sibling quantize_config.json of old AutoGPTQ exports; None when there is neither."""
+    import json
+    import os
+    with open(os.path.join(path, "config.json")) as f:
+        qc = json.load(f).get("quantization_config")
+    if qc is None and os.path.isfile(os.path.join(path, "quantize_config.json")):
+        with open(os.path.join(path, "quantize_config.json")) as f:
+            qc = json.load(f)
+    return qc
+
+
+def _unpack_int32_nibbles(t: torch.Tensor, dim: int, order=None) -> torch.Tensor:
+    """int32 words -> uint8 nibbles: `dim` grows eightfold, nibble i (bits 4 i .. 4 i + 3) of word m to index 8 m + i - or,
+    with `order`, to 8 m + order[i]."""
+    t = t.movedim(dim, -1)
+    sh = torch.arange(0, 32, 4, dtype=torch.int32)
+    nib = ((t.unsqueeze(-1) >> sh) & 15).to(torch.uint8)               # [..., words, 8]
+    if order is not None:
+        out = torch.empty_like(nib)
+        out[..., list(order)] = nib
+        nib = out
+    return nib.reshape(*t.shape[:-1], t.shape[-1] * 8).movedim(-1, dim)
+
+
+def _take_int4(out: dict, path):
+    """The group-wise INT4 matrices of a GPTQ / AWQ checkpoint - a linear layer X stored as X.qweight, X.qzeros, X.scales
+    (+ X.g_idx) - converted WITHOUT changing a value to (q, gs, gz) under X.weight, X.weight_gscale, X.weight_gzero.
+    The layouts read (nothing of either tool was available to check them against; INTEGRATION.md repeats this), for K
+    inputs, N outputs, g = k // group_size:
+      GPTQ (quant_method 'gptq' or absent): qweight int32 [K / 8, N], code (k, n) = bits 4 (k % 8) .. + 3 of qweight[k // 8,
+        n]; qzeros int32 [K / G, N / 8], stored (g, n) = bits 4 (n % 8) .. + 3 of qzeros[g, n // 8], z = stored for
+        checkpoint_format 'gptq_v2', else (stored + 1) & 15; scales fp16 [K / G, N];
+      AWQ (quant_method 'awq', version 'gemm', zero_point true): qweight int32 [K, N / 8], qzeros int32 [K / G, N / 8], nibble
+        i of word m holds column 8 m + AWQ_ORDER[i], z = stored; scales fp16 [K / G, N]."""
+    from ._lib import PsgHipError
+    layers = sorted(k[:-len(".qweight")] for k in out if k.endswith(".qweight"))
+    if not layers:
+        return out
+    qc = read_hf_quant_config(path)
+    if qc is None:
+        raise PsgHipError(f"{path}: {layers[0]}.qweight is a packed quantised layer, but there is no quantization_config in "
+                          "config.json and no quantize_config.json")
+    other = sorted(k for k, v in out.items() if k.endswith(".weight" + SCALE_SUFFIX) or
+                   v.dtype in (torch.float8_e4m3fn, torch.float8_e4m3fnuz, torch.float8_e5m2, torch.float8_e5m2fnuz))
+    if other:
+        raise PsgHipError(f"{path}: {layers[0]}.qweight is group-wise INT4 and {other[0]} is FP8 / MXFP4: a checkpoint that mixes "
+                          "quantised formats is not built")
+    method = str(qc.get("quant_method", "gptq")).lower()
+    bits, G = qc.get("bits"), qc.get("group_size")
+    for X in layers:
+        why = None
+        if method not in ("gptq", "awq"):
+            why = f"quant_method {method!r} is not built (gptq, awq)"
+        elif bits != 4:
+            why = f"bits={bits!r}: only 4-bit codes are built"
+        elif G not in INT4_GROUPS:
+            why = f"group_size={G!r}: a group is one of {INT4_GROUPS} weights (per-channel, -1, is not built)"
+        elif qc.get("desc_act"):
+            why = "desc_act=true (act-order) is not built"
+        elif method == "awq" and str(qc.get("version", "gemm")).lower() != "gemm":
+            why = f"AWQ version {qc.get('version')!r} is not built (gemm)"
+        elif method == "awq" and not qc.get("zero_point", True):
+            why = "AWQ with zero_point=false is not built"
+        if why:
+            raise PsgHipError(f"{path}: {X}.qweight: {why}")
+        qw, qz, sc = out.get(X + ".qweight"), out.get(X + ".qzeros"), out.get(X + ".scales")
+        if qz is None or sc is None:
+            raise PsgHipError(f"{path}: {X}.qweight has no {X}.qzeros / {X}.scales beside it")
+        if qw.dtype != torch.int32 or qz.dtype != torch.int32 or sc.dtype != torch.float16 or qw.dim() != 2:
+            raise PsgHipError(f"{path}: {X}: qweight / qzeros must be int32 and scales fp16, got {qw.dtype} / {qz.dtype} / {sc.dtype}")
+        K, N = (qw.shape[0] * 8, qw.shape[1]) if method == "gptq" else (qw.shape[0], qw.shape[1] * 8)
+        consistent = N % 8 == 0 and sc.dim() == 2 and sc.shape[1] == N and tuple(qz.shape) == (sc.shape[0], N // 8)
+        if consistent and K % G:
+            raise PsgHipError(f"{path}: {X}.qweight: K = {K} is no multiple of group_size = {G}")
+        if not consistent or sc.shape[0] != K // G:
+            raise PsgHipError(f"{path}: {X}: qweight {tuple(qw.shape)} as {method} means K = {K}, N = {N}, but scales are "
+                              f"{tuple(sc.shape)} (expected {(K // G, N)}) and qzeros {tuple(qz.shape)} (expected "
+                              f"{(K // G, N // 8)}): the shapes contradict quant_method {method!r}")
+        gi = out.pop(X + ".g_idx", None)
+        if gi is not None and not torch.equal(gi.to(torch.int64).reshape(-1), torch.arange(K, dtype=torch.int64) // G):
+            raise PsgHipError(f"{path}: {X}.g_idx is not k // group_size: act-order (desc_act) is not built")
+        absf = sc.to(torch.float32).abs()
+        if not bool(torch.isfinite(absf).all()) or bool((absf < 2.0 ** -14).any()):
+            raise PsgHipError(f"{path}: {X}.scales holds a zero, subnormal or non-finite scale")
+        b = out.pop(X + ".bias", None)
+        if b is not None and bool((b != 0).any()):
+            raise PsgHipError(f"{path}: {X}.bias is not zero: bias tensors are not built (Llama / Mistral projections have none)")
+        if method == "gptq":
+            code = _unpack_int32_nibbles(qw, 0)                        # [K, N]
+            z = _unpack_int32_nibbles(qz, 1)                           # [K / G, N]
+            if qc.get("checkpoint_format") != "gptq_v2":
+                z = (z + 1) & 15                                       # (the exporter stores z - 1)
+        else:
+            code = _unpack_int32_nibbles(qw, 1, AWQ_ORDER)
+            z = _unpack_int32_nibbles(qz, 1, AWQ_ORDER)
+        code = code.t().reshape(N, K // 2, 2)
+        for k in (".qweight", ".qzeros", ".scales"):
+            del out[X + k]
+        out[X + ".weight"] = (code[:, :, 0] | (code[:, :, 1] << 4)).contiguous()
+        out[X + ".weight" + GSCALE_SUFFIX] = sc.t().contiguous()
+        out[X + ".weight" + GZERO_SUFFIX] = z.t().contiguous()
+    return out
+
+
 def llm_quant_keys(n_layers: int, lm_head: bool = False):
     """Names of the matrices llm_weight_quant quantises: q/k/v/o/gate/up/down of the kept layers (+ the lm_head on
     request); never the embedding, the norms or language_projection."""
@@ -356,15 +529,18 @@ def llm_quant_keys(n_layers: int, lm_head: bool = False):
 
 def quantize_llm_weights(weights: dict, n_layers: int, lm_head: bool = False, fmt: str = "fp8") -> dict:
     """`weights` with every matrix of `llm_quant_keys` replaced by its (q, s): the byte tensor under the matrix's own name,
-    the scales under name + '_scale'; fmt='mxfp4': its (q, e, s), the block exponents under name + '_bexp'.  A matrix that
-    already comes quantised - an FP8 or MXFP4 checkpoint - is kept as it is."""
-    if fmt not in ("fp8", "mxfp4"):
-        raise ValueError(f"quantize_llm_weights: fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
+    the scales under name + '_scale'; fmt='mxfp4': its (q, e, s), the block exponents under name + '_bexp'; fmt='int4g': its
+    (q, gs, gz) in groups of 128, under name, name + '_gscale', name + '_gzero'.  A matrix that already comes quantised - an
+    FP8, MXFP4, GPTQ or AWQ checkpoint - is kept as it is."""
+    if fmt not in ("fp8", "mxfp4", "int4g"):
+        raise ValueError(f"quantize_llm_weights: fmt must be 'fp8', 'mxfp4' or 'int4g', got {fmt!r}")
     out = dict(weights)
     for k in llm_quant_keys(n_layers, lm_head):
         if k in out and not is_quantized(out, k):
             if fmt == "fp8":
                 out[k], out[k + SCALE_SUFFIX] = quantize_fp8_rows(out[k])
+            elif fmt == "int4g":
+                out[k], out[k + GSCALE_SUFFIX], out[k + GZERO_SUFFIX] = quantize_int4_groups(out[k], 128)
             else:
                 out[k], out[k + BEXP_SUFFIX], out[k + SCALE_SUFFIX] = quantize_mxfp4_rows(out[k])
     return out
@@ -536,7 +712,9 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
     [N, 1]) is taken as it is: the matrix stays float8_e4m3fn, its scale becomes fp32 [N] under name + '_scale', nothing
     is re-quantised; `*.input_scale` entries are ignored (weight-only execution).  An MXFP4 checkpoint (`*.weight` uint8
     [N, K / 2] with a sibling `*.weight_scale` uint8 [N, K / 32]) is row-anchored (`_take_mxfp4`): name + '_scale' fp32 [N],
-    name + '_bexp' uint8 [N, K / 32]."""
+    name + '_bexp' uint8 [N, K / 32].  A GPTQ or AWQ checkpoint (`X.qweight`, `X.qzeros`, `X.scales` in place of `X.weight`)
+    is converted value for value to the group-wise INT4 model (`_take_int4`): X.weight uint8 [N, K / 2], X.weight_gscale fp16
+    and X.weight_gzero uint8 [N, K / G]."""
     import json
     import os
     from ._lib import PsgHipError
@@ -587,6 +765,7 @@ def read_hf_llama_weights(path, n_layers=None, prefix="language_model."):
             del sd
     if prefix + "lm_head.weight" not in out:
         raise PsgHipError(f"{path}: no lm_head.weight (tied embeddings are not Llama-2's layout)")
+    out = _take_int4(out, path)                                        # (drops the all-zero biases of its own layers)
     bias = sorted(k for k in out if k.endswith(".bias"))
     if bias:
         raise PsgHipError(f"{path}: bias tensors are not built (Llama / Mistral projections have none): {bias[:3]}")

@@ -1,0 +1,196 @@
+"""llm_weight_quant='int4g' through the whole head (`-m gpu`).  A group-wise INT4 LLM is a model whose matrices ARE
+W' = float(gs) * (q - gz), so - as for FP8 and MXFP4 (tests/test_gpu_llm_w8.py / test_gpu_llm_w4.py, whose helpers and bars
+these are) - the head with the option is held to a head WITHOUT the option that was loaded with W' and to the CPU oracle on
+W', never to the original weights.  Tokens are compared per (pair, step) up to a pair's first near-tie (top-2 margin under
+1e-3 in the option-off head)."""
+import numpy as np
+import pytest
+import torch
+
+from tests import helpers as H
+from tests.test_gpu_llm_w8 import _assert_tokens_agree, _decode, _head, _step_margins
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+_INT4 = ("split_gemm_int4", "skinny_gemm_int4")
+_OTHER = ("split_gemm_w4", "skinny_gemm_w4", "split_gemm_w8", "skinny_gemm_w8")
+
+
+def _dequantised(w, n_layers, lm_head=False):
+    """The dict an option-off head (or the oracle) needs to compute the SAME model: W' in fp32 for every quantised matrix."""
+    from openpsg_amd.weights import dequantize_int4_groups, llm_quant_keys, quantize_llm_weights
+    wq = quantize_llm_weights(w, n_layers, lm_head, fmt="int4g")
+    for k in llm_quant_keys(n_layers, lm_head):
+        wq[k] = dequantize_int4_groups(wq[k], wq.pop(k + "_gscale"), wq.pop(k + "_gzero"))
+    return wq
+
+
+def _spy(monkeypatch):
+    from openpsg_amd import ops
+    calls = {fn: 0 for fn in _INT4 + _OTHER}
+    for fn in calls:
+        def wrapped(*a, _f=getattr(ops, fn), _n=fn, **kw):
+            calls[_n] += 1
+            return _f(*a, **kw)
+        monkeypatch.setattr(ops, fn, wrapped)
+    return calls
+
+
+def _fp32s_pair(case, loader, monkeypatch, lm_head=False):
+    g, cfg, w, scene = loader(case)
+    sup = bool(g["suppress_eos"])
+    ref = _head(cfg, _dequantised(w, cfg.llm.layers, lm_head), "fp32s", suppress_eos=sup)
+    assert not ref.llm_engine._wi4 and not ref.llm_engine._int4 and not ref.llm_engine._w4 and not ref.llm_engine._w8
+    rq0, dec0 = _decode(ref, g, scene)
+    margins = _step_margins(ref, dec0, sup)
+    t0, f0 = np.asarray(dec0["tokens_host"]).copy(), dec0["first_logits"].float().cpu()
+    e0 = rq0["exist_logit"].clone()
+    del ref, rq0, dec0
+    torch.cuda.empty_cache()
+    calls = _spy(monkeypatch)
+    head = _head(cfg, w, "fp32s", suppress_eos=sup, llm_weight_quant="int4g", llm_quantize_lm_head=lm_head)
+    eng = head.llm_engine
+    assert eng._wi4_layers and not eng._w8_layers and not eng._w4_layers and not eng._w16
+    assert len(eng._wi4) == len(eng._int4) == 4 * len(eng.layers) + int(lm_head)
+    # W' is no fp16 value: the prompt pass keeps the three-product split copies
+    assert all(k + "_s" in L for L in eng.layers for k in ("wqkv", "wo", "wgu", "wdown"))
+    assert eng._can_int4(20) and not eng._can_persist(20, 0) and not eng._can_fuse(20)
+    rq, dec = _decode(head, g, scene)
+    assert calls["split_gemm_int4"] > 0 and calls["skinny_gemm_int4"] == 0
+    assert all(calls[fn] == 0 for fn in _OTHER)
+    assert torch.equal(rq["exist_logit"], e0)                                # the relation query never sees the option
+    d = (dec["first_logits"].float().cpu() - f0).abs().max().item()
+    print(f"{case} fp32s: first-step logits, option on vs off on W': {d:.3e}")
+    assert d < 1e-4
+    _assert_tokens_agree(case, np.asarray(dec["tokens_host"]), t0, margins)
+    return g, cfg, w, scene, dec
+
+
+def test_g6_fp32s_agrees_with_the_option_off_head_and_the_oracle_on_the_same_model(monkeypatch):
+    """(a) G6 (Llama-2-7B width, 2 layers, 20 pairs), fp32s: first-step logits within 1e-4 of the option-off head on W',
+    tokens equal up to each pair's first near-tie, existence logits bit-equal, split_gemm_int4 called and no other quantised
+    entry.  (b) the CPU oracle on W': first-step logits within 1e-3.  Both bars are the FP8 / MXFP4 tests'."""
+    from oracle import psg_oracle as O
+    g, cfg, w, scene, dec = _fp32s_pair("G6_llm_7b_width_n6", H.load_case, monkeypatch)
+    wq = _dequantised(w, cfg.llm.layers)
+    sel = g["selected"].tolist()
+    qids, qmask = H.qformer_prompts(scene)
+    pids, pmask = H.llm_prompts(scene, sel)
+    fl = dec["first_logits"].float().cpu()
+    worst = 0.0
+    with torch.no_grad():
+        orq = O.relation_query(wq, cfg, scene["mask_features"], scene["img_meta"], [int(i) for i in scene["object_id_list"]],
+                               scene["pan_results"], qids, qmask)
+        for i, si in enumerate(sel):
+            x, mask = O.llm_inputs(wq, orq["pair_feature"][si], pids[i], pmask[i])
+            _, lg = O.llm_generate(wq, cfg, x, mask, max_new_tokens=1, suppress_eos=bool(g["suppress_eos"]))
+            ref = lg[0]
+            keep = torch.isfinite(ref)
+            worst = max(worst, (fl[i][keep] - ref[keep]).abs().max().item())
+    print(f"G6 fp32s + int4 against the oracle on W': first-step logits {worst:.3e}")
+    assert worst < 1e-3
+
+
+def test_g8_grouped_query_fp32s(monkeypatch):
+    """G8 (4 query / 2 key-value heads: k / v projections of kv_heads x 128 rows) in fp32s, the checks of (a); the lm_head
+    quantised as well."""
+    from tests.test_gpu_gqa_head import load_gqa_case
+    _fp32s_pair("G8_gqa_512_n10", load_gqa_case, monkeypatch, lm_head=True)
+
+
+def test_g1_mixed_is_as_close_to_the_oracle_as_the_option_off_head(monkeypatch):
+    """G1 in `mixed` against the CPU oracle on W': existence logits bit-equal to the option-off head, first-step logit
+    error within twice what the option-off `mixed` head measures against the same oracle in this test."""
+    from oracle import psg_oracle as O
+    g, cfg, w, scene = H.load_case("G1_c1_512_n10")
+    sup = bool(g["suppress_eos"])
+    wq = _dequantised(w, cfg.llm.layers)
+    sel = g["selected"].tolist()
+    qids, qmask = H.qformer_prompts(scene)
+    pids, pmask = H.llm_prompts(scene, sel)
+    refs = []
+    with torch.no_grad():
+        orq = O.relation_query(wq, cfg, scene["mask_features"], scene["img_meta"], [int(i) for i in scene["object_id_list"]],
+                               scene["pan_results"], qids, qmask)
+        for i, si in enumerate(sel):
+            x, mask = O.llm_inputs(wq, orq["pair_feature"][si], pids[i], pmask[i])
+            refs.append(O.llm_generate(wq, cfg, x, mask, max_new_tokens=1, suppress_eos=sup)[1][0])
+    ref = torch.stack(refs)
+    keep = torch.isfinite(ref)
+    off = _head(cfg, wq, "mixed", suppress_eos=sup)
+    rq0, dec0 = _decode(off, g, scene)
+    err_off = (dec0["first_logits"].float().cpu() - ref)[keep].abs().max().item()
+    calls = _spy(monkeypatch)
+    on = _head(cfg, w, "mixed", suppress_eos=sup, llm_weight_quant="int4g")
+    rq1, dec1 = _decode(on, g, scene)
+    assert calls["skinny_gemm_int4"] > 0 and calls["split_gemm_int4"] == 0 and all(calls[fn] == 0 for fn in _OTHER)
+    assert torch.equal(rq1["exist_logit"], rq0["exist_logit"])
+    err_on = (dec1["first_logits"].float().cpu() - ref)[keep].abs().max().item()
+    print(f"G1 mixed against the oracle on W': first-step logits option off {err_off:.3e}, int4 {err_on:.3e}")
+    assert err_on <= 2.0 * err_off
+    margins = _step_margins(off, dec0, sup)
+    _assert_tokens_agree("G1 mixed", np.asarray(dec1["tokens_host"]), np.asarray(dec0["tokens_host"]), margins)
+
+
+def test_forward_batch_of_two_images_runs_on_the_dequantised_model(monkeypatch):
+    """Routing: a <= 32-row decode calls the new entries; a forward_batch of 2 images (40 decode rows) does not, returns
+    per-image results, and its tokens equal the single-image tokens up to each pair's first near-tie."""
+    g, cfg, w, scene = H.load_case("G1_c1_512_n10")
+    sup = bool(g["suppress_eos"])
+    head = _head(cfg, w, "mixed", suppress_eos=sup, llm_weight_quant="int4g")
+    dev = torch.device(DEV)
+    inputs = dict(mask_features=scene["mask_features"].to(dev), img_metas=[scene["img_meta"]],
+                  object_info=[dict(object_id_list=scene["object_id_list"], pan_results=scene["pan_results"].to(dev))])
+    calls = _spy(monkeypatch)
+    single = head(inputs)
+    assert calls["skinny_gemm_int4"] > 0 and all(calls[fn] == 0 for fn in _OTHER)
+    names = H.object_names(scene)
+    rq = head.run_relation_query(scene["mask_features"].to(dev), scene["img_meta"], [int(i) for i in scene["object_id_list"]],
+                                 names, scene["pan_results"].to(dev))
+    dec = head.decode_selected(rq, names)                                    # the single image's tokens, its own selection
+    t1 = np.asarray(dec["tokens_host"]).copy()
+    margins = _step_margins(head, dec, sup)
+    n = dict(calls)
+    res = head.forward_batch([inputs, inputs])
+    assert calls == n                                                        # 40 rows: W' on the batch kernels / the library
+    assert len(res) == 2 and all(set(r) == set(single) for r in res) and len(head.last_batch) == 2
+    for i, lb in enumerate(head.last_batch):
+        _assert_tokens_agree(f"forward_batch image {i}", np.asarray(lb["tokens_host"]), t1, margins)
+
+
+def test_gptq_and_awq_checkpoint_directories_through_the_constructor(tmp_path):
+    """The GPTQ and AWQ checkpoint directories of tests/test_int4_quant_cpu.py read by the head's constructor decode the
+    tokens and rel_pred of a head handed the same (q, gs, gz) through load_weights."""
+    from openpsg_amd.config import PSGConfig, QFormerConfig, tiny_llm
+    from openpsg_amd.head import RelationTransformerHeadV4
+    from openpsg_amd.synthetic import make_scene
+    from openpsg_amd.weights import make_weights_numpy
+    from tests.test_int4_quant_cpu import int4_model, write_int4_checkpoint
+    cfg = PSGConfig(qformer=QFormerConfig(vocab=512), llm=tiny_llm(256, 2, 512, 512), max_object_num=30)
+    w = make_weights_numpy(cfg, seed=5)
+    model = int4_model(cfg)
+    kw = dict(dtype="fp32s", device=DEV, qformer_vocab_size=512, tokenizers="word", max_object_num=30, on_parse_error="skip",
+              suppress_eos=True, llm_feature_size=256)
+    own = {k: v for k, v in w.items() if not k.startswith("language_model.")}
+    fed = dict(own)
+    for k, v in w.items():
+        if k in model:
+            fed[k], fed[k + "_gscale"], fed[k + "_gzero"] = model[k]
+        elif k.startswith("language_model."):
+            fed[k] = v.half()
+    b = RelationTransformerHeadV4(llm_config=cfg.llm, **kw)
+    b.load_weights(fed)
+    assert b.llm_engine._wi4_layers and b.llm_engine.lm_head.data_ptr() not in b.llm_engine._int4
+    scene = make_scene((512, 512), 6, seed=3, device=DEV)
+    inputs = dict(mask_features=scene["mask_features"], img_metas=[scene["img_meta"]],
+                  object_info=[dict(object_id_list=scene["object_id_list"], pan_results=scene["pan_results"])])
+    rb = b(inputs)
+    for tag, args in (("gptq", dict(method="gptq")), ("awq", dict(method="awq"))):
+        d = str(tmp_path / tag)
+        write_int4_checkpoint(d, cfg, w, model, **args)
+        a = RelationTransformerHeadV4(llm_model_name=d, **kw)                 # no option: the checkpoint IS quantised
+        assert a.llm_engine._wi4_layers
+        a.load_state_dict(own, strict=False)
+        ra = a(inputs)
+        assert torch.equal(a.last["tokens"], b.last["tokens"]) and torch.equal(a.last["first_logits"], b.last["first_logits"])
+        assert ra["rel_pred"] == rb["rel_pred"], tag

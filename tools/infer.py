@@ -48,8 +48,9 @@ def parser():
     ap.add_argument("--llm-dir", help="local HuggingFace checkpoint directory of the LLM (config.json + model.safetensors / "
                     "shards / pytorch_model*.bin): read by the head's constructor as the reference's from_pretrained does "
                     "(V4:99-103); without it the LLM is seeded random weights of --llm-layers layers")
-    ap.add_argument("--llm-weight-quant", choices=["fp8", "mxfp4"], default=None,
-                    help="mxfp4: OCP Microscaling FP4 (two codes per byte, one exponent per 32 weights, one scale per row: "
+    ap.add_argument("--llm-weight-quant", choices=["fp8", "mxfp4", "int4g"], default=None,
+                    help="int4g: group-wise INT4 as GPTQ / AWQ checkpoints hold it (4-bit codes, one fp16 scale and one zero point "
+                    "per 128 weights: 4.25 bits per weight); a GPTQ / AWQ checkpoint in --llm-dir is taken as it is either way.  mxfp4: OCP Microscaling FP4 (two codes per byte, one exponent per 32 weights, one scale per row: "
                     "4.25 bits per weight); an MXFP4 checkpoint in --llm-dir is taken as it is either way.  fp8: the LLM's projection matrices as OCP e4m3fn bytes with per-row scales (decode steps stream one "
                     "byte per weight); an FP8 checkpoint in --llm-dir is taken as it is either way")
     ap.add_argument("--llm-weight-resident", choices=["all", "quantised"], default="all",
