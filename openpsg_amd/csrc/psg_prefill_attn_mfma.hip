@@ -137,19 +137,23 @@ prefill_attn_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restr
           o[dt][qt] = E::mfma32(vf[dt].v, pf[qt].v, o[dt][qt]);
     }
   // lane (q = lane&31, hi) holds O[q][32 dt + (r&3) + 8 (r>>2) + 4 hi] for its row of each query tile;
-  // padding rows get zeros (defined output, never consumed: same as the scalar kernel)
+  // padding rows get zeros (defined output, never consumed: same as the scalar kernel).  A select, not the product
+  // with inv_l == 0: in a pair without any real token kclamp sends every V gather to cache row 0, which nobody has
+  // written, and 0 x NaN on the matrix cores is NaN.
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int qi = 32 * qt + l31;
     if (qi < S) {
       uint16_t* op = out + (row0 + qi) * hidden + h * 128 + 4 * hi;
+      const bool live = inv_l[qt] > 0.f;
+      auto fin = [&](float x) { return live ? x * inv_l[qt] : 0.f; };
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           uint2 wv;
-          wv.x = E::pack(o[dt][qt][4 * rr] * inv_l[qt], o[dt][qt][4 * rr + 1] * inv_l[qt]);
-          wv.y = E::pack(o[dt][qt][4 * rr + 2] * inv_l[qt], o[dt][qt][4 * rr + 3] * inv_l[qt]);
+          wv.x = E::pack(fin(o[dt][qt][4 * rr]), fin(o[dt][qt][4 * rr + 1]));
+          wv.y = E::pack(fin(o[dt][qt][4 * rr + 2]), fin(o[dt][qt][4 * rr + 3]));
           *reinterpret_cast<uint2*>(op + 32 * dt + 8 * rr) = wv;
         }
     }

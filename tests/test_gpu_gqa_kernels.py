@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import gqa_ref as R
+from tests import llm_attn_ref as L
 
 pytestmark = pytest.mark.gpu
 
@@ -174,6 +175,9 @@ def test_rope_kvwrite_and_llm_attn_gqa(dtype, G):
         err = (out.cpu().double()[valid] - want[valid]).abs().max().item()
         assert err <= TOL[dtype], f"llm_attn_gqa splits={splits}: {err:.3e}"
         assert bool((out.cpu()[~valid] == 0).all())
+        # and inside the derived bound of tests/llm_attn_ref.py (the scalar kernel keeps its probabilities in fp32)
+        r64, A, gx, n = L.prefix64(q.cpu(), kcc, vcc, tok_pair, tok_pos, heads)
+        L.check(f"llm_attn_gqa splits={splits}", out.cpu(), r64, L.attn_bound(r64, A, gx, n, dt))
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
@@ -206,6 +210,9 @@ def test_prefill_attn_gqa_and_rope_form(dtype, G):
     err = (out.cpu().double()[valid] - want[valid]).abs().max().item()
     assert err <= TOL[dtype], f"prefill_attn_gqa: {err:.3e}"
     assert bool((out.cpu()[~valid] == 0).all())
+    # and inside the derived bound of tests/llm_attn_ref.py (the 16-bit matrix-core kernel rounds its probabilities: + u A)
+    r64, A, gx, n, sv = L.causal64(q.cpu(), kc.cpu(), vc.cpu(), tok_pos, pairs, S, heads, sum_v=True)
+    L.check("prefill_attn_gqa", out.cpu(), r64, L.attn_bound(r64, A, gx, n, dt, p_rounded=dtype != "fp32", sum_v=sv))
     if dtype != "fp32":
         kc2 = torch.full_like(kc, float("nan"))
         vc2 = torch.full_like(kc, float("nan"))

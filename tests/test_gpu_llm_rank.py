@@ -74,6 +74,11 @@ def test_tree_attn_against_float64(dtype, heads, kv_heads):
     else:
         tol = 1e-2 if dtype == torch.bfloat16 else 2e-3
         assert (got - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    # and elementwise inside the derived bound of tests/llm_attn_ref.py (the kernel keeps its probabilities in fp32)
+    from tests import llm_attn_ref as L
+    r64, A, gx, n = L.tree64(qd, kd, vd, row_pair, row_node, plen, anc, base, heads)
+    assert torch.allclose(r64, ref, rtol=0, atol=1e-12)
+    L.check("tree_attn", out.cpu(), r64, L.attn_bound(r64, A, gx, n, dtype))
 
 
 @pytest.mark.parametrize("vocab", [32000, 1000])

@@ -363,6 +363,12 @@ def test_prefill_attn_mfma_vs_scalar_kernel_and_fp32(K, S, heads):
     print(f"K={K} S={S}: mfma err {e_m:.3e}, scalar err {e_s:.3e}")
     assert e_m < 3e-2 and e_s < 3e-2
     assert (out_m[~ok] == 0).all()                                  # padding rows: zeros, like the scalar kernel
+    # and both inside the derived bound of tests/llm_attn_ref.py against float64 (the matrix-core kernel rounds its
+    # probabilities to bf16: + u A)
+    from tests import llm_attn_ref as L
+    r64, A, gx, n, sv = L.causal64(q.cpu(), kc.cpu(), vc.cpu(), pos.cpu(), K, S, heads, sum_v=True)
+    L.check("prefill_attn", out_m.cpu(), r64, L.attn_bound(r64, A, gx, n, torch.bfloat16, p_rounded=True, sum_v=sv))
+    L.check("llm_attn", out_s.cpu(), r64, L.attn_bound(r64, A, gx, n, torch.bfloat16))
 
 
 @pytest.mark.parametrize("dtype,competitors,seed", [("fp32", 0, 5), ("fp32", 1, 2), ("fp32", 1, 1), ("bf16", 1, 2),
