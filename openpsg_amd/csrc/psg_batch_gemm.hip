@@ -26,6 +26,7 @@
 // only - not on the other rows - so a pair's tokens do not depend on its batch neighbours as long as the row count's
 // plan is the same (tests: against the fp32 reference and against psg_skinny_gemm on <= 32 of the rows).
 #include "psg_common.h"
+#include "psg_streamk.h"
 #include "psg_wave.h"
 
 #define BG_BK 64
@@ -34,9 +35,6 @@
 // ring depth.  Deeper rings where the LDS would hold them (4-6 units for the 128-row slabs / <= 96 rows of x) were measured
 // SLOWER (down projection at 160 rows: 35.0 -> 38.1 us, q|k|v at 40 rows: 26.3 -> 30.1): three units everywhere
 constexpr int bg_nst(int) { return 3; }
-
-// first workgroup whose unit range [i T / G, (i + 1) T / G) holds unit u
-__host__ __device__ static inline int bg_owner(int64_t u, int64_t T, int G) { return (int)(((u + 1) * G - 1) / T); }
 
 // S_al > 0: aligned ranges (workgroup i = slab i / S_al, slice i % S_al of its K walk); 0: stream-K
 // PAIR (psg_split_gemm_w16): x holds TWO planes of the same M <= 32 rows - the high and the low fp16 part of fp32
@@ -62,15 +60,8 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
   const int nk = K / BG_BK, NB = (N + BN - 1) / BN;
   const int64_t T = (int64_t)NB * nk;
   const int G = gridDim.x;
-  int64_t g0, g1;
-  if (S_al > 0) {
-    const int sb = blockIdx.x / S_al, sl = blockIdx.x - sb * S_al;
-    g0 = (int64_t)sb * nk + (int64_t)sl * nk / S_al;
-    g1 = (int64_t)sb * nk + (int64_t)(sl + 1) * nk / S_al;
-  } else {
-    g0 = (int64_t)blockIdx.x * T / G;
-    g1 = ((int64_t)blockIdx.x + 1) * T / G;
-  }
+  const psg_sk_span span = psg_sk_range(nk, T, G, S_al);
+  const int64_t g0 = span.g0, g1 = span.g1;
   if (g0 >= g1) return;
   const int wm = wid / WN, wn = wid % WN;
   const int ti0 = wm * TI;
@@ -132,18 +123,12 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
 
   int slab = (int)(g0 / nk), kt = (int)(g0 - (int64_t)slab * nk);
   int pslab = slab, pkt = kt;                                // the unit the next DMA stage fetches
-  auto advance = [&](int& s_, int& k_) {
-    if (++k_ == nk) {
-      k_ = 0;
-      ++s_;
-    }
-  };
   int issued = 0;                                            // units in flight (prologue: NST - 1)
 #pragma unroll
   for (int p = 0; p < NST - 1; ++p)
     if (g0 + p < g1) {
       stage(pslab, pkt, p, 0, PER + 1);
-      advance(pslab, pkt);
+      psg_sk_advance(pslab, pkt, nk);
       ++issued;
     }
   bool after_flush = false;
@@ -211,15 +196,13 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
     mma(af[1], bf[1]);
     __builtin_amdgcn_s_setprio(0);
     if (pf) {
-      advance(pslab, pkt);
+      psg_sk_advance(pslab, pkt, nk);
       ++issued;
     }
 
     const bool slab_end = kt == nk - 1;
     if ((slab_end || u == g1 - 1) && var != 1) {             // the segment ends: one fp32 slice
-      int slot;
-      if (S_al > 0) slot = (int)blockIdx.x % S_al;
-      else slot = (int)blockIdx.x - bg_owner((int64_t)slab * nk, T, G);
+      const int slot = psg_sk_slot(slab, nk, T, G, S_al);
       const int nslots = (slab_end && S_al == 0) ? S : slot + 1;   // ending a slab (stream-K): zero the slots it did not use
       // D[m][n]: register r of a lane = row 8 (r >> 2) + 4 hi + (r & 3) of the tile, column lane & 31.  Row pointers are
       // wave-uniform (scalar), the lane adds ONE 32-bit offset: no per-store address registers
@@ -272,7 +255,7 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
         for (int j = 0; j < TJ; ++j) acc[i][j] = (psg_f32x16){0};
       after_flush = true;
     }
-    advance(slab, kt);
+    psg_sk_advance(slab, kt, nk);
     buf = buf + 1 == NST ? 0 : buf + 1;
   }
 }
@@ -282,21 +265,8 @@ struct bg_plan {
   int mt, tj, grid, slots, s_al;
 };
 
-static int bg_streamk_slots(int N, int K, int BN, int G) {
-  const int nk = K / BG_BK, NB = (N + BN - 1) / BN;
-  const int64_t T = (int64_t)NB * nk;
-  int smax = 1;
-  for (int b = 0; b < NB; ++b) {
-    const int i0 = bg_owner((int64_t)b * nk, T, G), i1 = bg_owner((int64_t)(b + 1) * nk - 1, T, G);
-    if (i1 - i0 + 1 > smax) smax = i1 - i0 + 1;
-  }
-  return smax;
-}
-
-// Candidates: BN = 256 / 128 weight rows per slab x {aligned slices, stream-K}.  Estimated time = the longest range's
-// units x the unit's cost (L2 -> LDS staging of both tiles at ~40 B/clk/CU, or the unit's share of the HBM stream) + the
-// fp32 slices it leaves (written here, read by the consumer).  Aligned ranges need slabs x slices ~ the grid; stream-K
-// balances any shape at the price of a second flush per workgroup and the zero-filled slots.
+// Candidates: BN = 256 / 128 weight rows per slab x psg_sk_make_plan's {aligned slices, stream-K}, the cheapest estimate.
+// The unit's cost: L2 -> LDS staging of both tiles at ~40 B/clk/CU, or the unit's share of the HBM stream.
 static bg_plan bg_make_plan(const psg_ctx* ctx, int64_t M, int N, int K, int bn, int mode_, bool pair = false) {
   bg_plan best{0, 0, 0, 0, 0};
   double best_t = 1e300;
@@ -311,36 +281,12 @@ static bg_plan bg_make_plan(const psg_ctx* ctx, int64_t M, int N, int K, int bn,
     if (pair && tj != 1) continue;
     if (!pair && forced_bn && forced_bn != BN) continue;
     const int NB = (N + BN - 1) / BN;
-    const int64_t T = (int64_t)NB * nk;
     const double unit_us = fmax((double)(mt * 32 + BN) * 128 / (40.0 * 2.4e3), (double)BN * 128 * G / 5.8e6);
-    for (int mode = 1; mode <= 2; ++mode) {
-      if (forced_mode && forced_mode != mode) continue;
-      bg_plan p{mt, tj, 0, 0, 0};
-      double units;
-      if (mode == 1) {
-        int s_al = G / NB;
-        if (s_al < 1) continue;
-        if (s_al > nk) s_al = nk;
-        if (s_al > PSG_MAX_SPLITS) s_al = PSG_MAX_SPLITS;    // what a consumer kernel sums
-        p.s_al = p.slots = s_al;
-        p.grid = NB * s_al;
-        units = (double)((nk + s_al - 1) / s_al);
-      } else {
-        p.grid = T < G ? (int)T : G;                         // every workgroup gets at least one unit: slot ranks are contiguous
-        p.slots = bg_streamk_slots(N, K, BN, p.grid);
-        while (p.slots > PSG_MAX_SPLITS && p.grid > NB) {    // few slabs, long K walks: fewer workgroups = longer segments
-          p.grid = p.grid * 7 / 8 > NB ? p.grid * 7 / 8 : NB;
-          p.slots = bg_streamk_slots(N, K, BN, p.grid);
-        }
-        if (p.slots > PSG_MAX_SPLITS) continue;
-        units = (double)((T + p.grid - 1) / p.grid);
-      }
-      const double slice_bytes = (double)p.slots * (pair ? 32 : M) * N * 4;   // (pair form: the plan must not follow the row count)
-      const double t = units * unit_us + slice_bytes / 3.5e6 + slice_bytes / 8e6 + (mode == 2 ? 3.0 : 0.0);
-      if (t < best_t) {
-        best_t = t;
-        best = p;
-      }
+    double t;                                                // (pair form: the plan must not follow the row count)
+    const psg_sk_plan p = psg_sk_make_plan(G, NB, nk, N, unit_us, pair ? 32 : M, forced_mode, &t);
+    if (t < best_t) {
+      best_t = t;
+      best = bg_plan{mt, tj, p.grid, p.slots, p.s_al};
     }
   }
   return best;
@@ -366,16 +312,8 @@ static int bg_launch(const bg_plan& p, const void* x, const void* w, float* part
   constexpr int STAGE = (MT * 32 + (BG_WAVES / WM) * TJ * 32) * 128;
   constexpr int NST_ = bg_nst(STAGE);
   static_assert(4 * ((MT * 32 + (BG_WAVES / WM) * TJ * 32) / 8 / BG_WAVES + 1) <= 63, "vmcnt field");
-  auto k = batch_gemm_kernel<E, MT, TJ, WM, PAIR>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, NST_ * STAGE);
-  if (e != hipSuccess) {
-    psg_set_error("psg_batch_gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    return PSG_ERR_HIP;
-  }
-  k<<<(unsigned)p.grid, BG_WAVES * 64, NST_ * STAGE, (hipStream_t)stream>>>((const uint16_t*)x, (const uint16_t*)w, part, M,
-                                                                             N, K, p.slots, p.s_al, var, row_scale, wt);
-  PSG_CHECK_LAUNCH("psg_batch_gemm");
-  return PSG_OK;
+  return psg_sk_launch("psg_batch_gemm", batch_gemm_kernel<E, MT, TJ, WM, PAIR>, p.grid, NST_ * STAGE, stream, x, w, part, M, N, K,
+                       p.slots, p.s_al, var, row_scale, wt);
 }
 
 extern "C" int psg_batch_gemm(psg_ctx* ctx, const void* x, const void* w, float* part, int64_t M, int N, int K, int slots,

@@ -28,6 +28,7 @@
 // 5 x tiles), which decides what is staged and multiplied, never which k a slot covers or in what order a row's products
 // are summed: rows 0..32 of a 160-row call are bit-equal to the same rows of a 33-row call.
 #include "psg_common.h"
+#include "psg_streamk.h"
 #include "psg_wave.h"
 
 #define BQ_BK 64
@@ -35,7 +36,6 @@
 #define BQ_WAVES 8
 #define BQ_LDS_MAX (160 * 1024)
 
-__host__ __device__ static inline int bq_owner(int64_t u, int64_t T, int G) { return (int)(((u + 1) * G - 1) / T); }
 __host__ __device__ constexpr int bq_wrow_bytes(int fmt) { return fmt == 8 ? 64 : 32; }
 __host__ __device__ constexpr int bq_stage_bytes(int fmt, bool pair, int mt) {
   return mt * 32 * (pair ? 2 : 1) * 128 + BQ_BN * bq_wrow_bytes(fmt) + (fmt == 4 ? BQ_BN * 8 : 0);
@@ -107,15 +107,8 @@ bq_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, co
   const int nk = K / BQ_BK, NB = (N + BQ_BN - 1) / BQ_BN;
   const int64_t T = (int64_t)NB * nk;
   const int G = gridDim.x;
-  int64_t g0, g1;
-  if (S_al > 0) {
-    const int sb = blockIdx.x / S_al, sl = blockIdx.x - sb * S_al;
-    g0 = (int64_t)sb * nk + (int64_t)sl * nk / S_al;
-    g1 = (int64_t)sb * nk + (int64_t)(sl + 1) * nk / S_al;
-  } else {
-    g0 = (int64_t)blockIdx.x * T / G;
-    g1 = ((int64_t)blockIdx.x + 1) * T / G;
-  }
+  const psg_sk_span span = psg_sk_range(nk, T, G, S_al);
+  const int64_t g0 = span.g0, g1 = span.g1;
   if (g0 >= g1) return;
 
   const int my_cnt = PER + (wid < REM ? 1 : 0);
@@ -173,18 +166,12 @@ bq_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, co
 
   int slab = (int)(g0 / nk), ks = (int)(g0 - (int64_t)slab * nk);
   int pslab = slab, pks = ks;                                // the step the next DMA stage fetches
-  auto advance = [&](int& s_, int& k_) {
-    if (++k_ == nk) {
-      k_ = 0;
-      ++s_;
-    }
-  };
   int issued = 0;                                            // steps in flight (prologue: NST - 1)
 #pragma unroll
   for (int p = 0; p < NST - 1; ++p)
     if (g0 + p < g1) {
       stage(pslab, pks, p);
-      advance(pslab, pks);
+      psg_sk_advance(pslab, pks, nk);
       ++issued;
     }
   bool after_flush = false;
@@ -227,7 +214,7 @@ bq_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, co
     read_x(0, af[0]);
     if (pf) {
       stage(pslab, pks, nb_);
-      advance(pslab, pks);
+      psg_sk_advance(pslab, pks, nk);
       ++issued;
     }
     psg_lgkmwait<4>();
@@ -261,9 +248,7 @@ bq_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, co
 
     const bool slab_end = ks == nk - 1;
     if (slab_end || u == g1 - 1) {                           // the segment ends: one fp32 slice
-      int slot;
-      if (S_al > 0) slot = (int)blockIdx.x % S_al;
-      else slot = (int)blockIdx.x - bq_owner((int64_t)slab * nk, T, G);
+      const int slot = psg_sk_slot(slab, nk, T, G, S_al);
       const int nslots = (slab_end && S_al == 0) ? S : slot + 1;   // ending a slab (stream-K): zero the slots it did not use
       // D[m][n]: register r of a lane = row 8 (r >> 2) + 4 hi + (r & 3) of the tile, column lane & 31
       const int n0 = slab * BQ_BN + wid * 32;
@@ -293,105 +278,44 @@ bq_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, co
       for (int i = 0; i < MT; ++i) acc[i] = (psg_f32x16){0};
       after_flush = true;
     }
-    advance(slab, ks);
+    psg_sk_advance(slab, ks, nk);
     buf = buf + 1 == NST ? 0 : buf + 1;
   }
 }
 
 // ---- host side: plan and launch --------------------------------------------------------------------------------------
-struct bq_plan {
-  int grid, slots, s_al;
-};
-
-static int bq_streamk_slots(int N, int K, int G) {
-  const int nk = K / BQ_BK, NB = (N + BQ_BN - 1) / BQ_BN;
-  const int64_t T = (int64_t)NB * nk;
-  int smax = 1;
-  for (int b = 0; b < NB; ++b) {
-    const int i0 = bq_owner((int64_t)b * nk, T, G), i1 = bq_owner((int64_t)(b + 1) * nk - 1, T, G);
-    if (i1 - i0 + 1 > smax) smax = i1 - i0 + 1;
-  }
-  return smax;
-}
-
-// psg_batch_gemm's estimate: the longest range's steps x the step's cost (L2 -> LDS staging at ~40 B/clk/CU, its matrix
-// instructions at 32 clk on two waves per SIMD, or its share of the HBM stream) + the fp32 slices it leaves (written
-// here, read by the consumer).  mode 1: ranges aligned to the slabs, 2: stream-K, 0: the cheaper estimate.  Made for
-// 160 rows whatever M is: a row's k ranges must not follow the row count.
-static bq_plan bq_make_plan(const psg_ctx* ctx, int N, int K, int fmt, int forced_mode, bool pair) {
-  bq_plan best{0, 0, 0};
-  double best_t = 1e300;
+// psg_sk_make_plan's estimate with this step's cost: L2 -> LDS staging at ~40 B/clk/CU, its matrix instructions at 32 clk
+// on two waves per SIMD, or its share of the HBM stream.  mode 1: ranges aligned to the slabs, 2: stream-K, 0: the cheaper
+// estimate.  Made for 160 rows whatever M is: a row's k ranges must not follow the row count.
+static psg_sk_plan bq_make_plan(const psg_ctx* ctx, int N, int K, int fmt, int forced_mode, bool pair) {
   const int G = ctx->num_cu < 1024 ? ctx->num_cu : 1024;
   const int nk = K / BQ_BK, NB = (N + BQ_BN - 1) / BQ_BN;
-  const int64_t T = (int64_t)NB * nk;
   const int stage = bq_stage_bytes(fmt, pair, 5);
   const double mfma_us = 5.0 * (pair ? 2 : 1) * 4 * 2 * 32 / 2.4e3;
   const double unit_us = fmax(fmax((double)stage / (40.0 * 2.4e3), mfma_us), (double)BQ_BN * bq_wrow_bytes(fmt) * G / 5.8e6);
-  for (int mode = 1; mode <= 2; ++mode) {
-    if (forced_mode && forced_mode != mode) continue;
-    bq_plan p{0, 0, 0};
-    double units;
-    if (mode == 1) {
-      int s_al = G / NB;
-      if (s_al < 1) continue;
-      if (s_al > nk) s_al = nk;
-      if (s_al > PSG_MAX_SPLITS) s_al = PSG_MAX_SPLITS;      // what a consumer kernel sums
-      p.s_al = p.slots = s_al;
-      p.grid = NB * s_al;
-      units = (double)((nk + s_al - 1) / s_al);
-    } else {
-      p.grid = T < G ? (int)T : G;                           // every workgroup gets at least one step: slot ranks are contiguous
-      p.slots = bq_streamk_slots(N, K, p.grid);
-      while (p.slots > PSG_MAX_SPLITS && p.grid > NB) {      // few slabs, long K walks: fewer workgroups = longer segments
-        p.grid = p.grid * 7 / 8 > NB ? p.grid * 7 / 8 : NB;
-        p.slots = bq_streamk_slots(N, K, p.grid);
-      }
-      if (p.slots > PSG_MAX_SPLITS) continue;
-      units = (double)((T + p.grid - 1) / p.grid);
-    }
-    const double slice_bytes = (double)p.slots * 160 * N * 4;
-    const double t = units * unit_us + slice_bytes / 3.5e6 + slice_bytes / 8e6 + (mode == 2 ? 3.0 : 0.0);
-    if (t < best_t) {
-      best_t = t;
-      best = p;
-    }
-  }
-  return best;
+  return psg_sk_make_plan(G, NB, nk, N, unit_us, 160, forced_mode);
 }
 
-static int bq_plan_checked(const char* name, psg_ctx* ctx, int M, int N, int K, int fmt, int mode, bool pair, bq_plan* p,
+static int bq_plan_checked(const char* name, psg_ctx* ctx, int M, int N, int K, int fmt, int mode, bool pair, psg_sk_plan* p,
                            int* slots) {
-  PSG_REQUIRE(ctx && slots, PSG_ERR_INVALID, "%s: NULL argument", name);
   const int kq = fmt == 8 ? 128 : 256;                       // the 32-row families' K granule: the images they already use
-  PSG_REQUIRE(M >= 33 && M <= 160 && N >= 16 && N % 16 == 0 && K >= kq && K % kq == 0 && mode >= 0 && mode <= 2,
-              PSG_ERR_UNSUPPORTED, "%s: M=%d (33..160), N=%d (multiple of 16), K=%d (multiple of %d), mode=%d", name, M, N, K,
-              kq, mode);
+  const int rc = psg_sk_check_args(name, ctx, slots, M, 33, 160, N, K, kq, mode);
+  if (rc != PSG_OK) return rc;
   *p = bq_make_plan(ctx, N, K, fmt, mode, pair);
-  PSG_REQUIRE(p->grid > 0 && p->slots <= PSG_MAX_SPLITS, PSG_ERR_UNSUPPORTED, "%s: no plan with <= %d slices for N=%d K=%d mode=%d",
-              name, PSG_MAX_SPLITS, N, K, mode);
-  *slots = p->slots;
-  return PSG_OK;
+  return psg_sk_plan_ok(name, *p, N, K, mode, slots);
 }
 
 template <typename E, int FMT, bool PAIR, int MT>
-static int bq_launch_mt(const char* name, const bq_plan& p, const void* x, const void* wq, const void* e_img, float* part, int M,
+static int bq_launch_mt(const char* name, const psg_sk_plan& p, const void* x, const void* wq, const void* e_img, float* part, int M,
                         int N, int K, const float* row_scale, const float* col_scale, void* stream) {
   constexpr int LDS = bq_nst(FMT, PAIR, MT) * bq_stage_bytes(FMT, PAIR, MT);
-  auto k = bq_gemm_kernel<E, FMT, PAIR, MT>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (e != hipSuccess) {
-    psg_set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
-    return PSG_ERR_HIP;
-  }
-  k<<<(unsigned)p.grid, BQ_WAVES * 64, LDS, (hipStream_t)stream>>>((const uint16_t*)x, (const uint8_t*)wq, (const uint8_t*)e_img,
-                                                                   part, M, N, K, p.slots, p.s_al, row_scale, col_scale);
-  PSG_CHECK_LAUNCH(name);
-  return PSG_OK;
+  return psg_sk_launch(name, bq_gemm_kernel<E, FMT, PAIR, MT>, p.grid, LDS, stream, x, wq, e_img, part, M, N, K, p.slots, p.s_al,
+                       row_scale, col_scale);
 }
 
 // M picks the x tiles that are staged and multiplied (2 / 3 / 5), nothing else
 template <typename E, int FMT, bool PAIR>
-static int bq_launch(const char* name, const bq_plan& p, const void* x, const void* wq, const void* e_img, float* part, int M,
+static int bq_launch(const char* name, const psg_sk_plan& p, const void* x, const void* wq, const void* e_img, float* part, int M,
                      int N, int K, const float* row_scale, const float* col_scale, void* stream) {
   if (M <= 64) return bq_launch_mt<E, FMT, PAIR, 2>(name, p, x, wq, e_img, part, M, N, K, row_scale, col_scale, stream);
   if (M <= 96) return bq_launch_mt<E, FMT, PAIR, 3>(name, p, x, wq, e_img, part, M, N, K, row_scale, col_scale, stream);
@@ -403,11 +327,11 @@ static int bq_single(const char* name, psg_ctx* ctx, const void* x, const void* 
                      float* part, int M, int N, int K, int slots, int dtype, int mode, void* stream) {
   PSG_REQUIRE(ctx && x && wq && (FMT == 8 || e_img) && col_scale && part, PSG_ERR_INVALID, "%s: NULL argument", name);
   PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "%s: dtype %d (bf16 / fp16)", name, dtype);
-  bq_plan p;
+  psg_sk_plan p;
   int want = 0;
-  const int rc = bq_plan_checked(name, ctx, M, N, K, FMT, mode, false, &p, &want);
+  int rc = bq_plan_checked(name, ctx, M, N, K, FMT, mode, false, &p, &want);
+  if (rc == PSG_OK) rc = psg_sk_check_slots(name, slots, want, N, K);
   if (rc != PSG_OK) return rc;
-  PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "%s: slots=%d, the plan for N=%d K=%d writes %d", name, slots, N, K, want);
   PSG_DISPATCH_E16(dtype, name,
                    return (bq_launch<E, FMT, false>(name, p, x, wq, e_img, part, M, N, K, nullptr, col_scale, stream)));
   return PSG_ERR_INVALID;
@@ -417,17 +341,17 @@ template <int FMT>
 static int bq_pair(const char* name, psg_ctx* ctx, const void* x2, const float* inv_scale, const void* wq, const void* e_img,
                    const float* col_scale, float* part, int M, int N, int K, int slots, int mode, void* stream) {
   PSG_REQUIRE(ctx && x2 && inv_scale && wq && (FMT == 8 || e_img) && col_scale && part, PSG_ERR_INVALID, "%s: NULL argument", name);
-  bq_plan p;
+  psg_sk_plan p;
   int want = 0;
-  const int rc = bq_plan_checked(name, ctx, M, N, K, FMT, mode, true, &p, &want);
+  int rc = bq_plan_checked(name, ctx, M, N, K, FMT, mode, true, &p, &want);
+  if (rc == PSG_OK) rc = psg_sk_check_slots(name, slots, want, N, K);
   if (rc != PSG_OK) return rc;
-  PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "%s: slots=%d, the plan for N=%d K=%d writes %d", name, slots, N, K, want);
   return bq_launch<EF16, FMT, true>(name, p, x2, wq, e_img, part, M, N, K, inv_scale, col_scale, stream);
 }
 
 extern "C" int psg_batch_gemm_w8_plan(psg_ctx* ctx, int M, int N, int K, int dtype, int mode, int* slots) {
   PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "psg_batch_gemm_w8_plan: dtype %d (bf16 / fp16)", dtype);
-  bq_plan p;
+  psg_sk_plan p;
   return bq_plan_checked("psg_batch_gemm_w8_plan", ctx, M, N, K, 8, mode, false, &p, slots);
 }
 extern "C" int psg_batch_gemm_w8(psg_ctx* ctx, const void* x, const void* w8, const float* col_scale, float* part, int M, int N,
@@ -435,7 +359,7 @@ extern "C" int psg_batch_gemm_w8(psg_ctx* ctx, const void* x, const void* w8, co
   return bq_single<8>("psg_batch_gemm_w8", ctx, x, w8, nullptr, col_scale, part, M, N, K, slots, dtype, mode, stream);
 }
 extern "C" int psg_batch_split_gemm_w8_plan(psg_ctx* ctx, int M, int N, int K, int mode, int* slots) {
-  bq_plan p;
+  psg_sk_plan p;
   return bq_plan_checked("psg_batch_split_gemm_w8_plan", ctx, M, N, K, 8, mode, true, &p, slots);
 }
 extern "C" int psg_batch_split_gemm_w8(psg_ctx* ctx, const void* x2, const float* inv_scale, const void* w8,
@@ -445,7 +369,7 @@ extern "C" int psg_batch_split_gemm_w8(psg_ctx* ctx, const void* x2, const float
 }
 extern "C" int psg_batch_gemm_w4_plan(psg_ctx* ctx, int M, int N, int K, int dtype, int mode, int* slots) {
   PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "psg_batch_gemm_w4_plan: dtype %d (bf16 / fp16)", dtype);
-  bq_plan p;
+  psg_sk_plan p;
   return bq_plan_checked("psg_batch_gemm_w4_plan", ctx, M, N, K, 4, mode, false, &p, slots);
 }
 extern "C" int psg_batch_gemm_w4(psg_ctx* ctx, const void* x, const void* w4, const void* e_img, const float* col_scale,
@@ -453,7 +377,7 @@ extern "C" int psg_batch_gemm_w4(psg_ctx* ctx, const void* x, const void* w4, co
   return bq_single<4>("psg_batch_gemm_w4", ctx, x, w4, e_img, col_scale, part, M, N, K, slots, dtype, mode, stream);
 }
 extern "C" int psg_batch_split_gemm_w4_plan(psg_ctx* ctx, int M, int N, int K, int mode, int* slots) {
-  bq_plan p;
+  psg_sk_plan p;
   return bq_plan_checked("psg_batch_split_gemm_w4_plan", ctx, M, N, K, 4, mode, true, &p, slots);
 }
 extern "C" int psg_batch_split_gemm_w4(psg_ctx* ctx, const void* x2, const float* inv_scale, const void* w4, const void* e_img,

@@ -7,9 +7,9 @@
 //          psg_rmsnorm_split2: part = (xh . q + xl . q) inv_scale[m] col_scale[n] - psg_split_gemm_w16's arithmetic over
 //          a weight that has a scale;
 //   single (psg_skinny_gemm_w8, bf16 / fp16 / mixed): x is [M][K] bf16 or fp16: part = (x . q) col_scale[n].
-// The kernel is the pair form of psg_batch_gemm.hip's (stream-K or slab-aligned ranges of (slab, K step) units dealt to
-// one workgroup per CU, LDS-DMA into a 3-unit ring with counted vmcnt, 8 waves x one 32-row weight tile, k-ordered
-// slices without atomics) with the K step widened to 128:
+// The kernel is psg_gemm_q32.h's - the pair form of psg_batch_gemm.hip's (stream-K or slab-aligned ranges of (slab, K step)
+// units dealt to one workgroup per CU, LDS-DMA into a 3-unit ring with counted vmcnt, 8 waves x one 32-row weight tile,
+// k-ordered slices without atomics) - with a K step of 128; this file holds the format: the widening and the sub-step.
 //   * a unit is 256 weight rows x 128 K.  An fp8 row of it is 128 bytes - the row length the 2-byte kernel stages per
 //     K step of 64 - so the weight image keeps that kernel's 16-byte pieces, its XOR swizzle on the source address and
 //     its conflict-free ds_read_b128: ONE read per lane and 32 K (16 fp8) where the 2-byte kernel needs two;
@@ -18,15 +18,7 @@
 //     holds weight piece p (K 16p .. 16p + 15 of the unit) feeds its low 8 values to one v_mfma_f32_32x32x16 and its high
 //     8 to the next, against x pieces 2p and 2p + 1 of the same lane half.  No byte shuffling, 8 conversions per read.
 // A row's result does not depend on the other rows (nor on M: the plan is made for 32 rows whatever M is).
-#include "psg_common.h"
-#include "psg_wave.h"
-
-#define W8_BK 128
-#define W8_BN 256
-#define W8_WAVES 8
-#define W8_NST 3
-
-__host__ __device__ static inline int w8_owner(int64_t u, int64_t T, int G) { return (int)(((u + 1) * G - 1) / T); }
+#include "psg_gemm_q32.h"
 
 template <typename E>
 struct W8Cvt;
@@ -50,318 +42,53 @@ __device__ __forceinline__ typename E::v8 w8_widen(uint32_t d0, uint32_t d1) {
   return (typename E::v8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
-// S_al > 0: aligned ranges (workgroup i = slab i / S_al, slice i % S_al of its K walk); 0: stream-K
-template <typename E, bool PAIR>
-__global__ void __launch_bounds__(W8_WAVES * 64, 1)
-w8_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, float* __restrict__ part, int M, int N, int K,
-               int S, int S_al, const float* __restrict__ row_scale, const float* __restrict__ col_scale) {
-  using v8 = typename E::v8;
-  constexpr int XT = PAIR ? 2 : 1, XR = XT * 32;             // x tiles of 32 rows (PAIR: plane 0, plane 1)
-  constexpr int XH = XR * 128, XB = 2 * XH;                  // one K half of the x image / both
-  constexpr int STAGE = XB + W8_BN * 128;                    // one unit: [x: K half 0 | x: K half 1 | w: 256 rows x 128 B]
-  constexpr int XI = XB / 1024, NI = STAGE / 1024;           // DMA instructions (8 rows x 128 B each): x / per unit
-  constexpr int PER = NI / W8_WAVES;
-  static_assert(NI % W8_WAVES == 0 && XR % 16 == 0, "uniform DMA counts, operand-local swizzle");
-  static_assert((W8_NST - 1) * PER <= 63, "vmcnt field");
-  constexpr int NR = 1 + 2 * XT;                             // LDS reads of one sub-step
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  const int nk = K / W8_BK, NB = (N + W8_BN - 1) / W8_BN;
-  const int64_t T = (int64_t)NB * nk;
-  const int G = gridDim.x;
-  int64_t g0, g1;
-  if (S_al > 0) {
-    const int sb = blockIdx.x / S_al, sl = blockIdx.x - sb * S_al;
-    g0 = (int64_t)sb * nk + (int64_t)sl * nk / S_al;
-    g1 = (int64_t)sb * nk + (int64_t)(sl + 1) * nk / S_al;
-  } else {
-    g0 = (int64_t)blockIdx.x * T / G;
-    g1 = ((int64_t)blockIdx.x + 1) * T / G;
-  }
-  if (g0 >= g1) return;
-
-  const int srow = lane >> 3, sslot = lane & 7;
-  // instruction idx of a unit: 128-byte rows 8 idx .. + 7 of the unit's image; a wave issues idx = wid, wid + 8, ...
-  auto stage_one = [&](int slab, int kt, unsigned char* sb, int idx) {
-    const int r = idx * 8 + srow;
-    const int piece = sslot ^ ((r >> 1) & 7);                // (XR and XI * 8 are multiples of 16: the operand-local row's swizzle)
-    if (idx < XI) {
-      const int half = r / XR, xr = r - half * XR;
-      int gr = xr < M ? xr : M - 1;
-      if (PAIR) gr = (xr >> 5) * M + ((xr & 31) < M ? (xr & 31) : M - 1);   // plane xr >> 5, row xr & 31 of [2][M][K]
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(x + (int64_t)gr * K + kt * W8_BK + half * 64 + piece * 8),
-          (__attribute__((address_space(3))) void*)(sb + idx * 1024), 16, 0, 0);
-    } else {
-      int gr = slab * W8_BN + (r - XI * 8);
-      gr = gr < N ? gr : N - 1;
-      __builtin_amdgcn_global_load_lds(                      // a weight byte is read once by one CU: non-temporal
-          (const __attribute__((address_space(1))) void*)(w + (int64_t)gr * K + kt * W8_BK + piece * 16),
-          (__attribute__((address_space(3))) void*)(sb + idx * 1024), 16, 0, 2);
+// the format of psg_gemm_q32.h's kernel
+struct W8Fmt {
+  static constexpr int BK = 128, SIDE = 0, SIDE_HI = 0;      // two x images per unit (K halves), no side image
+  static constexpr bool COL_SCALE = true;
+  static constexpr const char* ALIGNED = "x and w8";
+  __host__ __device__ static constexpr int nst(bool) { return 3; }
+  template <typename E, int XT>
+  struct Acc {
+    psg_f32x16 acc[XT];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+      for (int i = 0; i < XT; ++i) acc[i] = (psg_f32x16){0};
     }
-  };
-  auto stage = [&](int slab, int kt, int buf, int q0, int q1) {   // this wave's instructions q0 .. q1 - 1 of the unit
-    unsigned char* sb = smem + buf * STAGE;
-    for (int q = q0; q < q1; ++q)
-      if (q < PER) stage_one(slab, kt, sb, wid + W8_WAVES * q);
-  };
-
-  const int l31 = lane & 31, hi = lane >> 5;
-  uint32_t arow[XT];
-#pragma unroll
-  for (int i = 0; i < XT; ++i) arow[i] = (uint32_t)((i * 32 + l31) * 128);
-  const uint32_t aswz = (uint32_t)((l31 >> 1) & 7);          // (tile bases are multiples of 32 rows)
-  const uint32_t brow = (uint32_t)(XB + (wid * 32 + l31) * 128), bswz = aswz;
-
-  union Frag {
-    psg_u32x4 u;
-    v8 v;
-  };
-  psg_f32x16 acc[XT];
-#pragma unroll
-  for (int i = 0; i < XT; ++i) acc[i] = (psg_f32x16){0};
-
-  int slab = (int)(g0 / nk), kt = (int)(g0 - (int64_t)slab * nk);
-  int pslab = slab, pkt = kt;                                // the unit the next DMA stage fetches
-  auto advance = [&](int& s_, int& k_) {
-    if (++k_ == nk) {
-      k_ = 0;
-      ++s_;
-    }
-  };
-  int issued = 0;                                            // units in flight (prologue: W8_NST - 1)
-#pragma unroll
-  for (int p = 0; p < W8_NST - 1; ++p)
-    if (g0 + p < g1) {
-      stage(pslab, pkt, p, 0, PER);
-      advance(pslab, pkt);
-      ++issued;
-    }
-  bool after_flush = false;
-  int buf = 0;
-  constexpr int QH = (PER + 1) / 2;                          // DMA instructions issued beside the first sub-step
-  for (int64_t u = g0; u < g1; ++u) {
-    // unit u landed?  loads complete in order: the younger units' loads may stay outstanding
-    const int ahead = issued - 1;                            // younger units in flight (<= W8_NST - 2)
-    if (after_flush || ahead <= 0) psg_vmwait<0>();           // (stores of a flush may complete out of order with loads)
-    else if (ahead == 1) psg_vmwait<PER>();
-    else psg_vmwait<2 * PER>();
-    after_flush = false;
-    psg_lds_barrier();                                        // unit u is in LDS; nobody reads the buffer of unit u - 1 any more
-    --issued;
-    const bool pf = u + (W8_NST - 1) < g1;
-    int nb_ = buf + (W8_NST - 1);
-    nb_ = nb_ >= W8_NST ? nb_ - W8_NST : nb_;
-    const uint32_t base = smem_lds + (uint32_t)(buf * STAGE);
-    Frag af[2][XT][2];
-    psg_u32x4 bq[2];
-    // sub-step s2: weight piece p = 2 s2 + hi (K 16 p .. + 15 of the unit), x pieces 2 p and 2 p + 1 of the 256-byte row
-    auto read_frags = [&](int s2, Frag (&a_)[XT][2], psg_u32x4& b_) {
-      const uint32_t p = (uint32_t)(2 * s2 + hi);
-      b_ = psg_lds_read128(base + brow + ((p ^ bswz) << 4));
-      const uint32_t xh = base + (p >> 2) * XH, x0 = (2 * p) & 7;
-#pragma unroll
-      for (int i = 0; i < XT; ++i) {
-        a_[i][0].u = psg_lds_read128(xh + arow[i] + ((x0 ^ aswz) << 4));
-        a_[i][1].u = psg_lds_read128(xh + arow[i] + (((x0 + 1) ^ aswz) << 4));
-      }
-    };
-    auto mma = [&](Frag (&a_)[XT][2], psg_u32x4& b_) {
-      const v8 b0 = w8_widen<E>(b_[0], b_[1]), b1 = w8_widen<E>(b_[2], b_[3]);
+    __device__ __forceinline__ void unit(uint32_t) {}
+    // weight piece p (K 16 p .. + 15 of the unit): its low 8 values against x piece 2 p, its high 8 against 2 p + 1
+    __device__ __forceinline__ void step(int, PsgQ32Frag<E> (&a_)[XT][2], psg_u32x4& b_) {
+      const typename E::v8 b0 = w8_widen<E>(b_[0], b_[1]), b1 = w8_widen<E>(b_[2], b_[3]);
 #pragma unroll
       for (int i = 0; i < XT; ++i) acc[i] = E::mfma32(a_[i][0].v, b0, acc[i]);          // D[m][n]
 #pragma unroll
       for (int i = 0; i < XT; ++i) acc[i] = E::mfma32(a_[i][1].v, b1, acc[i]);
-    };
-    read_frags(0, af[0], bq[0]);
-    read_frags(1, af[1], bq[1]);
-    if (pf) stage(pslab, pkt, nb_, 0, QH);
-    psg_lgkmwait<NR>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-    mma(af[0], bq[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    read_frags(2, af[0], bq[0]);
-    if (pf) stage(pslab, pkt, nb_, QH, PER);
-    psg_lgkmwait<NR>();
-    __builtin_amdgcn_sched_barrier(0);
-    mma(af[1], bq[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    read_frags(3, af[1], bq[1]);
-    psg_lgkmwait<NR>();
-    __builtin_amdgcn_sched_barrier(0);
-    mma(af[0], bq[0]);
-    psg_lgkmwait<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    mma(af[1], bq[1]);
-    __builtin_amdgcn_s_setprio(0);
-    if (pf) {
-      advance(pslab, pkt);
-      ++issued;
     }
-
-    const bool slab_end = kt == nk - 1;
-    if (slab_end || u == g1 - 1) {                           // the segment ends: one fp32 slice
-      int slot;
-      if (S_al > 0) slot = (int)blockIdx.x % S_al;
-      else slot = (int)blockIdx.x - w8_owner((int64_t)slab * nk, T, G);
-      const int nslots = (slab_end && S_al == 0) ? S : slot + 1;   // ending a slab (stream-K): zero the slots it did not use
-      // D[m][n]: register r of a lane = row 8 (r >> 2) + 4 hi + (r & 3) of the tile, column lane & 31
-      const int n0 = slab * W8_BN + wid * 32;
-      if (n0 + l31 < N) {
-        const float cs = col_scale[n0 + l31];
-        const int lane_off = 4 * hi * N + l31;
-        float rs[16];                                        // (all sixteen loads in flight before the first store waits)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m_ = 8 * (r >> 2) + (r & 3) + 4 * hi;
-          rs[r] = PAIR ? row_scale[m_ < M ? m_ : M - 1] * cs : cs;
-        }
-        for (int s_ = slot; s_ < nslots; ++s_) {
-          float* ps = part + (int64_t)s_ * M * N;
-          const bool real = s_ == slot;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int mrow = 8 * (r >> 2) + (r & 3);
-            float* rowp = ps + (int64_t)mrow * N + n0;
-            if (mrow + 4 * hi < M) {
-              float val = 0.f;
-              if (real) val = PAIR ? (acc[0][r] + acc[XT - 1][r]) * rs[r] : acc[0][r] * rs[r];
-              rowp[lane_off] = val;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < XT; ++i) acc[i] = (psg_f32x16){0};
-      after_flush = true;
-    }
-    advance(slab, kt);
-    buf = buf + 1 == W8_NST ? 0 : buf + 1;
-  }
-}
-
-// ---- host side: plan and launch --------------------------------------------------------------------------------------
-struct w8_plan {
-  int grid, slots, s_al;
+    __device__ __forceinline__ float out(int r) const { return XT == 2 ? acc[0][r] + acc[XT - 1][r] : acc[0][r]; }
+  };
 };
 
-static int w8_streamk_slots(int N, int K, int G) {
-  const int nk = K / W8_BK, NB = (N + W8_BN - 1) / W8_BN;
-  const int64_t T = (int64_t)NB * nk;
-  int smax = 1;
-  for (int b = 0; b < NB; ++b) {
-    const int i0 = w8_owner((int64_t)b * nk, T, G), i1 = w8_owner((int64_t)(b + 1) * nk - 1, T, G);
-    if (i1 - i0 + 1 > smax) smax = i1 - i0 + 1;
-  }
-  return smax;
-}
-
-// psg_batch_gemm's estimate for one slab height: the longest range's units x the unit's cost (L2 -> LDS staging at
-// ~40 B/clk/CU, or the unit's share of the HBM stream) + the fp32 slices it leaves (written here, read by the consumer).
-// mode 1: ranges aligned to the slabs, 2: stream-K, 0: the cheaper estimate.  Made for 32 rows whatever M is: a row's
-// k ranges must not follow the row count.
-static w8_plan w8_make_plan(const psg_ctx* ctx, int N, int K, int forced_mode, bool pair) {
-  w8_plan best{0, 0, 0};
-  double best_t = 1e300;
-  const int G = ctx->num_cu < 1024 ? ctx->num_cu : 1024;
-  const int nk = K / W8_BK, NB = (N + W8_BN - 1) / W8_BN;
-  const int64_t T = (int64_t)NB * nk;
-  const int stage = (pair ? 128 : 64) * 128 + W8_BN * 128;
-  const double unit_us = fmax((double)stage / (40.0 * 2.4e3), (double)W8_BN * 128 * G / 5.8e6);
-  for (int mode = 1; mode <= 2; ++mode) {
-    if (forced_mode && forced_mode != mode) continue;
-    w8_plan p{0, 0, 0};
-    double units;
-    if (mode == 1) {
-      int s_al = G / NB;
-      if (s_al < 1) continue;
-      if (s_al > nk) s_al = nk;
-      if (s_al > PSG_MAX_SPLITS) s_al = PSG_MAX_SPLITS;      // what a consumer kernel sums
-      p.s_al = p.slots = s_al;
-      p.grid = NB * s_al;
-      units = (double)((nk + s_al - 1) / s_al);
-    } else {
-      p.grid = T < G ? (int)T : G;                           // every workgroup gets at least one unit: slot ranks are contiguous
-      p.slots = w8_streamk_slots(N, K, p.grid);
-      while (p.slots > PSG_MAX_SPLITS && p.grid > NB) {      // few slabs, long K walks: fewer workgroups = longer segments
-        p.grid = p.grid * 7 / 8 > NB ? p.grid * 7 / 8 : NB;
-        p.slots = w8_streamk_slots(N, K, p.grid);
-      }
-      if (p.slots > PSG_MAX_SPLITS) continue;
-      units = (double)((T + p.grid - 1) / p.grid);
-    }
-    const double slice_bytes = (double)p.slots * 32 * N * 4;
-    const double t = units * unit_us + slice_bytes / 3.5e6 + slice_bytes / 8e6 + (mode == 2 ? 3.0 : 0.0);
-    if (t < best_t) {
-      best_t = t;
-      best = p;
-    }
-  }
-  return best;
-}
-
-static int w8_plan_checked(const char* name, psg_ctx* ctx, int M, int N, int K, int mode, bool pair, w8_plan* p, int* slots) {
-  PSG_REQUIRE(ctx && slots, PSG_ERR_INVALID, "%s: NULL argument", name);
-  PSG_REQUIRE(M >= 1 && M <= 32 && N >= 16 && N % 16 == 0 && K >= W8_BK && K % W8_BK == 0 && mode >= 0 && mode <= 2,
-              PSG_ERR_UNSUPPORTED, "%s: M=%d (1..32), N=%d (multiple of 16), K=%d (multiple of %d), mode=%d", name, M, N, K,
-              W8_BK, mode);
-  *p = w8_make_plan(ctx, N, K, mode, pair);
-  PSG_REQUIRE(p->grid > 0 && p->slots <= PSG_MAX_SPLITS, PSG_ERR_UNSUPPORTED, "%s: no plan with <= %d slices for N=%d K=%d mode=%d",
-              name, PSG_MAX_SPLITS, N, K, mode);
-  *slots = p->slots;
-  return PSG_OK;
-}
-
-template <typename E, bool PAIR>
-static int w8_launch(const char* name, const w8_plan& p, const void* x, const void* w8, float* part, int M, int N, int K,
-                     const float* row_scale, const float* col_scale, void* stream) {
-  constexpr int LDS = W8_NST * ((PAIR ? 128 : 64) * 128 + W8_BN * 128);
-  auto k = w8_gemm_kernel<E, PAIR>;
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (e != hipSuccess) {
-    psg_set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
-    return PSG_ERR_HIP;
-  }
-  k<<<(unsigned)p.grid, W8_WAVES * 64, LDS, (hipStream_t)stream>>>((const uint16_t*)x, (const uint8_t*)w8, part, M, N, K,
-                                                                   p.slots, p.s_al, row_scale, col_scale);
-  PSG_CHECK_LAUNCH(name);
-  return PSG_OK;
-}
-
 extern "C" int psg_split_gemm_w8_plan(psg_ctx* ctx, int M, int N, int K, int mode, int* slots) {
-  w8_plan p;
-  return w8_plan_checked("psg_split_gemm_w8_plan", ctx, M, N, K, mode, true, &p, slots);
+  psg_sk_plan p;
+  return psg_q32_plan_checked<W8Fmt>("psg_split_gemm_w8_plan", ctx, M, N, K, mode, true, &p, slots);
 }
 
 extern "C" int psg_split_gemm_w8(psg_ctx* ctx, const void* x2, const float* inv_scale, const void* w8, const float* col_scale,
                                  float* part, int M, int N, int K, int slots, int mode, void* stream) {
   PSG_REQUIRE(ctx && x2 && inv_scale && w8 && col_scale && part, PSG_ERR_INVALID, "psg_split_gemm_w8: NULL argument");
-  w8_plan p;
-  int want = 0;
-  const int rc = w8_plan_checked("psg_split_gemm_w8", ctx, M, N, K, mode, true, &p, &want);
-  if (rc != PSG_OK) return rc;
-  PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "psg_split_gemm_w8: slots=%d, the plan for N=%d K=%d writes %d", slots, N, K, want);
-  return w8_launch<EF16, true>("psg_split_gemm_w8", p, x2, w8, part, M, N, K, inv_scale, col_scale, stream);
+  return psg_q32_run<W8Fmt, true>("psg_split_gemm_w8", ctx, x2, w8, nullptr, inv_scale, col_scale, part, M, N, K, slots, PSG_F16,
+                                  mode, stream);
 }
 
 extern "C" int psg_skinny_gemm_w8_plan(psg_ctx* ctx, int M, int N, int K, int dtype, int mode, int* slots) {
   PSG_REQUIRE(dtype == PSG_BF16 || dtype == PSG_F16, PSG_ERR_UNSUPPORTED, "psg_skinny_gemm_w8_plan: dtype %d (bf16 / fp16)", dtype);
-  w8_plan p;
-  return w8_plan_checked("psg_skinny_gemm_w8_plan", ctx, M, N, K, mode, false, &p, slots);
+  psg_sk_plan p;
+  return psg_q32_plan_checked<W8Fmt>("psg_skinny_gemm_w8_plan", ctx, M, N, K, mode, false, &p, slots);
 }
 
 extern "C" int psg_skinny_gemm_w8(psg_ctx* ctx, const void* x, const void* w8, const float* col_scale, float* part, int M, int N,
                                   int K, int slots, int dtype, int mode, void* stream) {
   PSG_REQUIRE(ctx && x && w8 && col_scale && part, PSG_ERR_INVALID, "psg_skinny_gemm_w8: NULL argument");
-  w8_plan p;
-  int want = 0;
-  const int rc = w8_plan_checked("psg_skinny_gemm_w8", ctx, M, N, K, mode, false, &p, &want);
-  if (rc != PSG_OK) return rc;
-  PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "psg_skinny_gemm_w8: slots=%d, the plan for N=%d K=%d writes %d", slots, N, K, want);
-  PSG_DISPATCH_E16(dtype, "psg_skinny_gemm_w8",
-                   return (w8_launch<E, false>("psg_skinny_gemm_w8", p, x, w8, part, M, N, K, nullptr, col_scale, stream)));
-  return PSG_ERR_INVALID;
+  return psg_q32_run<W8Fmt, false>("psg_skinny_gemm_w8", ctx, x, w8, nullptr, nullptr, col_scale, part, M, N, K, slots, dtype, mode,
+                                   stream);
 }

@@ -104,3 +104,20 @@ def test_unsupported_shapes_are_refused():
         x2 = torch.zeros((2, M, K), dtype=torch.float16, device=DEV)
         with pytest.raises(PsgHipError, match="status"):
             ops.split_gemm_w4(x2, torch.ones(M, device=DEV), q, ei, s)
+    # every operand is fetched by 16-byte LDS-DMA: a misaligned image is refused, in both forms
+    M, N, K = 4, 16, 256
+    q = torch.zeros((N, K // 2), dtype=torch.uint8, device=DEV)
+    ei = torch.full((1, N, 2, 4), 127, dtype=torch.uint8, device=DEV)
+    s = torch.ones(N, device=DEV)
+    x = torch.zeros((M, K), dtype=torch.float16, device=DEV)
+    x2 = torch.zeros((2, M, K), dtype=torch.float16, device=DEV)
+    buf = torch.zeros(N * K // 2 + 16, dtype=torch.uint8, device=DEV)
+    q_off = buf[1:1 + N * K // 2].view(N, K // 2)                               # a nibble image one byte off
+    buf = torch.full((N * 8 + 16,), 127, dtype=torch.uint8, device=DEV)
+    ei_off = buf[8:8 + N * 8].view(1, N, 2, 4)                                  # an exponent image eight bytes off
+    for qi, ee in ((q_off, ei), (q, ei_off)):
+        with pytest.raises(PsgHipError, match="status"):
+            ops.skinny_gemm_w4(x, qi, ee, s)
+        with pytest.raises(PsgHipError, match="status"):
+            ops.split_gemm_w4(x2, torch.ones(M, device=DEV), qi, ee, s)
+    assert ops.skinny_gemm_w4(x, q, ei, s).t.abs().max() == 0

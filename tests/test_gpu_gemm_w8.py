@@ -91,3 +91,15 @@ def test_unsupported_shapes_are_refused():
         with pytest.raises(PsgHipError, match="status"):
             ops.skinny_gemm_w8(torch.zeros((M, K), dtype=torch.float16, device=DEV), q, s[:N].contiguous() if N <= 16 else
                                torch.ones(N, device=DEV))
+    # every operand is fetched by 16-byte LDS-DMA: a misaligned byte image is refused, in both forms
+    M, N, K = 4, 16, 128
+    q = torch.zeros((N, K), dtype=torch.uint8, device=DEV)
+    x = torch.zeros((M, K), dtype=torch.float16, device=DEV)
+    x2 = torch.zeros((2, M, K), dtype=torch.float16, device=DEV)
+    buf = torch.zeros(N * K + 16, dtype=torch.uint8, device=DEV)
+    q_off = buf[1:1 + N * K].view(N, K)                                         # a byte image one byte off
+    with pytest.raises(PsgHipError, match="status"):
+        ops.skinny_gemm_w8(x, q_off, s)
+    with pytest.raises(PsgHipError, match="status"):
+        ops.split_gemm_w8(x2, torch.ones(M, device=DEV), q_off, s)
+    assert ops.skinny_gemm_w8(x, q, s).t.abs().max() == 0
