@@ -77,8 +77,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   607  quantised matrices as the only resident copy: psg_expand_w8, psg_expand_w4 added
  *   608  quantised weights in the batched decode: psg_batch_gemm_w8(_plan), psg_batch_split_gemm_w8(_plan),
  *        psg_batch_gemm_w4(_plan), psg_batch_split_gemm_w4(_plan) added
- *   609  group-wise INT4 LLM weights (GPTQ / AWQ): psg_split_gemm_int4(_plan), psg_skinny_gemm_int4(_plan) added */
-#define PSG_ABI_VERSION 609
+ *   609  group-wise INT4 LLM weights (GPTQ / AWQ): psg_split_gemm_int4(_plan), psg_skinny_gemm_int4(_plan) added
+ *   610  unquantised fp32s weights in the batched decode: psg_batch_split_gemm_w16(_plan), psg_batch_split_gemm_w32(_plan)
+ *        added */
+#define PSG_ABI_VERSION 610
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -436,6 +438,25 @@ int psg_batch_gemm_w4(psg_ctx*, const void* x, const void* w4, const void* e_img
 int psg_batch_split_gemm_w4_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
 int psg_batch_split_gemm_w4(psg_ctx*, const void* x2, const float* inv_scale, const void* w4, const void* e_img,
                             const float* col_scale, float* part, int M, int N, int K, int slots, int mode, void* stream);
+/* The fp32s projections for 33 <= M <= 160 rows over UNQUANTISED weights held as fp16 planes.  x2 / inv_scale as
+ * psg_split_gemm_w16's (psg_split_f16x2); every fp16 x fp16 product is exact in fp32 and all products of an output element
+ * go into one fp32 accumulator:
+ *   psg_batch_split_gemm_w16: w16 fp16 [N] rows of `row_stride` elements (a weight that IS an fp16 value), col_scale [N]:
+ *     part[slot][m][n] = (xh . w + xl . w)[m][n] * inv_scale[m] * col_scale[n];
+ *   psg_batch_split_gemm_w32: w_img fp16, [N] rows of `row_stride` elements that hold the high plane wh at element 0 and the
+ *     low plane wl at element `lo_off` (psg_split_f16x3 order 1 = [wh | wl | wh]: row_stride 3 K, lo_off K; a packed
+ *     [wh | wl] image: row_stride 2 K, lo_off K), col_scale [N] = the inverse row scales of that split:
+ *     part[slot][m][n] = (xh . wh + xh . wl + xl . wh)[m][n] * inv_scale[m] * col_scale[n].
+ * 33 <= M <= 160, N % 16 == 0, K % 64 == 0, x2 / the weight 16-byte aligned with row_stride % 8 == 0, row_stride >= K (w32:
+ * lo_off % 8 == 0, K <= lo_off, lo_off + K <= row_stride), else PSG_ERR_UNSUPPORTED without a launch.  Slices, slots, plan
+ * entries, modes and row independence as the w8 / w4 batch entries above. */
+int psg_batch_split_gemm_w16_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_batch_split_gemm_w16(psg_ctx*, const void* x2, const float* inv_scale, const void* w16, int64_t row_stride,
+                             const float* col_scale, float* part, int M, int N, int K, int slots, int mode, void* stream);
+int psg_batch_split_gemm_w32_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_batch_split_gemm_w32(psg_ctx*, const void* x2, const float* inv_scale, const void* w_img, int64_t row_stride,
+                             int64_t lo_off, const float* col_scale, float* part, int M, int N, int K, int slots, int mode,
+                             void* stream);
 /* The dense operand of a quantised matrix, rebuilt from its bytes (an engine that keeps only the bytes resident
  * expands a matrix into a scratch buffer right before the one large-M product that reads it).  q: e4m3fn bytes [N][K]
  * (psg_expand_w8) or fp4 nibbles [N][K / 2], the low nibble the even k, with the RAW block exponents e uint8 [N][K / 32] in

@@ -250,6 +250,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # read of a quantised LLM.  'dense': W' (today's launches).
                                                # 'quantised': the bytes / nibbles, on psg_batch_gemm_q.hip - 1 / 0.53 bytes per
                                                # weight, and no expansion per step with llm_weight_resident='quantised'
+                 llm_batch_split_gemm='library',    # 'library' | 'own': what forward_batch's decode steps of 33..160 rows run
+                                               # over the UNQUANTISED matrices of an fp32s head.  'library':
+                                               # the SGEMM / the stacked-plane fp16 product (today's launches).  'own':
+                                               # psg_batch_gemm_s.hip - two fp16 products over an fp16-valued weight, three
+                                               # over the prompt pass's split image of a generic one (4 bytes per weight)
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -278,6 +283,16 @@ class RelationTransformerHeadV4(nn.Module):
             raise PsgHipError(f"llm_batch_weight_stream='quantised' is about the LLM's weights; rel_cls_type={rel_cls_type!r} "
                               "has no LLM stage")
         self.llm_batch_weight_stream = llm_batch_weight_stream
+        if llm_batch_split_gemm not in ("library", "own"):
+            raise PsgHipError(f"llm_batch_split_gemm must be 'library' or 'own', got {llm_batch_split_gemm!r}")
+        if llm_batch_split_gemm == "own" and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_batch_split_gemm='own' is about the LLM's decode steps; rel_cls_type={rel_cls_type!r} has "
+                              "no LLM stage")
+        if llm_batch_split_gemm == "own" and dtype != "fp32s":
+            raise PsgHipError(f"llm_batch_split_gemm='own' runs the fp32s batched decode on split-fp16 products; dtype={dtype!r}: "
+                              "the 16-bit modes already run psg_batch_gemm there, and the exact 'fp32' mode keeps its exact SGEMM "
+                              "- use dtype='fp32s' or llm_batch_split_gemm='library'")
+        self.llm_batch_split_gemm = llm_batch_split_gemm
         if llm_quantize_lm_head and llm_weight_quant is None:
             raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4' or 'int4g'")
         # group-wise INT4 has the decode kernels of <= 32 rows only: no expand kernel, no 33..160-row kernel
@@ -516,7 +531,8 @@ class RelationTransformerHeadV4(nn.Module):
         self._llm_engine = LlamaDecodeEngine(w, self.cfg, self.device, self.act_dtype, n_layers=n_layers,
                                              resid_dtype=self.resid_dtype, prefill_split=self.prefill_split,
                                              resident=self.llm_weight_resident,
-                                             batch_quant_stream=self.llm_batch_weight_stream == "quantised")
+                                             batch_quant_stream=self.llm_batch_weight_stream == "quantised",
+                                             batch_split_gemm=self.llm_batch_split_gemm == "own")
         return self
 
     def quantize_llm_weights(self, weights: dict) -> dict:

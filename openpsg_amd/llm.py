@@ -262,6 +262,34 @@ def _batch_quant_route(fmt, form, N, K, rows, table=None):
     return "stream"
 
 
+# Decode steps with 33..160 rows of an fp32s engine over an UNQUANTISED matrix, engine option batch_split_gemm:
+# psg_batch_gemm_s.hip runs the split products where the steps above run the library SGEMM (generic fp32 weights) or the
+# stacked-plane fp16 product (fp16-valued weights).  A FIXED table like _BATCH_QUANT_DENSE: a listed row range sends a
+# measured loser (tools/batch_split_bench.py: the kernel's range of times not wholly below the library path's) back to
+# the library; a shape that is not listed takes the kernel.
+#   key: (form 'w16' / 'w32', N, K) -> [(rows from, rows below), ...]
+# Measured at the Llama-2-7B shapes and 40 / 80 / 160 rows = 2 / 3 / 5 x tiles (profiles/batch_split_bench.json; the row
+# ranges are those of the tile counts: 33..64, 65..96, 97..160; us per launch, median (min-max), own against library).  The
+# w32 form (against the SGEMM on fp32 W) wins by 1.05-2.0 x everywhere but q|k|v and o at 40 rows.  The w16 form meets a
+# library product that streams 2 bytes per weight as well: it keeps q|k|v and down at every row count, o at 80 rows and
+# the lm_head at 40.
+_BATCH_SPLIT_LIBRARY: dict = {
+    ("w32", 12288, 4096): [(33, 65)],                          # q|k|v, 40 rows: 49.8 (46.7-57.3) against 58.9 (55.6-69.1): overlap
+    ("w32", 4096, 4096): [(33, 65)],                           # o, 40 rows: 25.8 (25.2-26.3) against 25.3 (24.4-26.1)
+    ("w16", 4096, 4096): [(33, 65), (97, 161)],                # o: 26.6 against 25.6; 160 rows: 41.0 against 39.1
+    ("w16", 22016, 4096): [(33, 161)],                         # gate|up: 56.6 (55.0-62.3) / 74.4 / 97.1 against 56.7 / 70.3 / 92.2
+    ("w16", 32000, 4096): [(65, 161)],                         # lm_head: 88.2 / 118.3 against 84.6 / 117.5
+}
+
+
+def _batch_split_route(form, N, K, rows, table=None):
+    """'own' or 'library' for a decode projection of `rows` fp32s rows over an unquantised [N, K] matrix."""
+    for lo, hi in (_BATCH_SPLIT_LIBRARY if table is None else table).get((form, int(N), int(K)), ()):
+        if lo <= rows < hi:
+            return "library"
+    return "own"
+
+
 class QuantMatrix:
     """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
     `lm_head` hold in place of W'.  Carries the shape and dtype W' would have and the quantised parts - (q, s) for FP8,
@@ -289,14 +317,16 @@ class QuantMatrix:
 
 class LlamaDecodeEngine:
     def __init__(self, weights: dict, cfg: PSGConfig, device, dtype=torch.bfloat16, n_layers=None, resid_dtype=None,
-                 prefill_split=False, resident="all", batch_quant_stream=False):
+                 prefill_split=False, resident="all", batch_quant_stream=False, batch_split_gemm=False):
         """prefill_split (fp32 engines): the prompt pass's projections as split-fp16 products on the 16-bit matrix cores,
         `linear_split` below; the decode steps stay exact fp32 (psg_gemm_f32.hip).
         resid_dtype: storage type of the residual stream; None = `dtype` (what HF keeps for a model cast to 16
         bits), torch.float32 with a 16-bit `dtype` = mixed mode (16-bit GEMM operands, the residual stream - the sum
         of 2 x layers updates - never rounded to 16 bits; costs 160 KB more traffic per decode row kernel).
         batch_quant_stream: decode steps of 33..160 rows stream a quantised matrix's bytes (`_batch_quant`)
-        instead of reading W'."""
+        instead of reading W'.
+        batch_split_gemm (fp32s engines): decode steps of 33..160 rows run an unquantised matrix on psg_batch_gemm_s.hip
+        (`_batch_split`) instead of the library GEMM."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
         if resident not in ("all", "quantised"):
@@ -500,6 +530,11 @@ class LlamaDecodeEngine:
         if self.batch_quant_stream and not (self._w8 or self._w4):
             raise PsgHipError("batch_quant_stream streams a quantised LLM's bytes in the batched decode, and no matrix of this "
                               "model is quantised: set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint")
+        self.batch_split_gemm = bool(batch_split_gemm)
+        if self.batch_split_gemm and not self.prefill_split:
+            raise PsgHipError("batch_split_gemm runs the batched decode of an fp32s engine (dtype float32 with prefill_split) on "
+                              "split-fp16 products: the 16-bit engines run psg_batch_gemm there, the exact fp32 engine its SGEMM")
+        self.lm_head_s = None            # batch_split_gemm: the packed [wh | wl] image of a generic lm_head (below)
         # fp32 engines: are the projection weights fp16 VALUES?  The reference's LLM is the frozen Llama-2-7b-hf checkpoint
         # (fp16 on disk, configs/psg/baseline_v4_ov.py:61-65) upcast by from_pretrained (V4:99-100): if every element of
         # every projection round-trips through fp16, the decode steps stream an fp16 copy - half the HBM bytes - instead
@@ -528,6 +563,17 @@ class LlamaDecodeEngine:
                 for k in ("wqkv", "wo", "wgu", "wdown"):
                     if L[k].data_ptr() not in self._w8 and L[k].data_ptr() not in self._w4:   # (quantised: the two-plane prompt pass on `_w8h` / `_w4h`, no split copy)
                         L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
+        # batch_split_gemm: a generic fp32 lm_head has no split image (the prompt pass reads one row per pair of it, the decode
+        # steps of <= 32 rows stream the fp32 tensor), and its SGEMM is the longest launch of a 33..160-row step (288-291 us at
+        # 80 / 160 rows against 146 / 187 on the planes): keep the packed [wh | wl] image - 4 bytes per weight, 0.52 GB at
+        # 32000 x 4096, counted under `other` in resident_bytes()
+        lm = self.lm_head
+        if (self.batch_split_gemm and isinstance(lm, torch.Tensor) and lm.dtype == torch.float32 and lm.data_ptr() not in self._w16
+                and lm.data_ptr() not in self._w8 and lm.data_ptr() not in self._w4 and lm.data_ptr() not in self._int4
+                and lm.shape[0] % 16 == 0 and lm.shape[1] % 64 == 0):
+            img, inv = ops.split_f16x3(lm, weights=True)
+            self.lm_head_s = (img[:, :2 * lm.shape[1]].contiguous(), inv)
+            del img
         # row_invariant (fp32s engines): the prompt pass's projections and the language projection on psg_dense_gemm - one
         # k-ordered accumulation per output element whatever the row count of the call - instead of the library GEMM, whose
         # kernel choice follows the row count: a pair decoded in a batch of 3 (decodes DEALT over the ranks of a pair-sharded
@@ -659,8 +705,8 @@ class LlamaDecodeEngine:
             elif isinstance(o, (list, tuple)):
                 for v in o:
                     walk(v)
-        for name in ("embed", "lm_head", "final_norm", "proj_w", "proj_b", "proj_s", "layers", "rope", "_w8h", "_w4h", "_w16",
-                     "_i2_w", "_ones_cache"):
+        for name in ("embed", "lm_head", "lm_head_s", "final_norm", "proj_w", "proj_b", "proj_s", "layers", "rope", "_w8h", "_w4h",
+                     "_w16", "_i2_w", "_ones_cache"):
             walk(getattr(self, name, None))
         return dict(quantised=quant, scratch=scratch, other=other, total=quant + scratch + other)
 
@@ -767,6 +813,8 @@ class LlamaDecodeEngine:
             out = self._batch_quant(x, w, w8, w4)
             if out is not None:
                 return out
+        unquantised = (isinstance(w, torch.Tensor) and w8 is None and w4 is None and wi4 is None
+                       and w.data_ptr() not in self._int4)
         w = self._dense(w)                                    # (resident='quantised': W' expanded into the slot's scratch)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
@@ -786,6 +834,11 @@ class LlamaDecodeEngine:
             # the 16-bit prompt pass of several images (forward_batch: 2 / 4 / 8 x 960 rows): the library's pick for the
             # whole product against its column / row parts (_plan_split_mm; 7-14 % per layer at 1920-7680 rows, nothing at 960)
             return _split_mm(x, w, _plan_split_mm(x.shape[0], w, None, pool=self._w_pools.get(tuple(w.shape))), None)
+        if (self.batch_split_gemm and batch_stream and decode and self.use_skinny and self.prefill_split and unquantised
+                and 32 < x.shape[0] <= 160 and x.dtype == torch.float32):
+            out = self._batch_split(x, w, ws)
+            if out is not None:
+                return out
         if decode and x.dtype == torch.float32 and x.shape[0] > 32:
             # fp32 engines, decode steps of 33..160 rows (several images' pairs, head.forward_batch - BASELINE C5's batch of 8
             # at the reference's precision): the weight leaves HBM ONCE per step for all rows.  fp16-valued weights of an
@@ -824,6 +877,31 @@ class LlamaDecodeEngine:
             x2, inv = ops.split_f16x2(x)
             return (ops.batch_split_gemm_w8 if fmt == "fp8" else ops.batch_split_gemm_w4)(x2, inv, *args)
         return (ops.batch_gemm_w8 if fmt == "fp8" else ops.batch_gemm_w4)(x, *args)
+
+    def _batch_split(self, x, w, ws):
+        """Decode projection of 33..160 fp32s rows over an unquantised matrix on psg_batch_gemm_s.hip: fp32
+        slices for the consumers of `ops.batch_gemm`, or None where the shape does not fit the kernel, the matrix has no
+        16-bit operand or the routing table sends it to the library.  An fp16-valued matrix streams its fp16 copy (2 bytes
+        per weight, two products); a generic one the [wh | wl] planes of the prompt pass's split image in place - the
+        lm_head: of its packed image `lm_head_s` - (4 bytes per weight, three products)."""
+        rows, (N, K) = int(x.shape[0]), w.shape
+        if N % 16 or K % 64:
+            return None
+        wh = self._w16.get(w.data_ptr())
+        if wh is not None:
+            form = "w16"
+        elif ws is not None and tuple(ws[0].shape) == (N, 3 * K):
+            form = "w32"
+        elif self.lm_head_s is not None and w.data_ptr() == self.lm_head.data_ptr():
+            form, ws = "w32", self.lm_head_s
+        else:
+            return None
+        if _batch_split_route(form, N, K, rows) == "library":
+            return None
+        x2, inv = ops.split_f16x2(x)
+        if form == "w16":
+            return ops.batch_split_gemm_w16(x2, inv, wh, self._ones(N))
+        return ops.batch_split_gemm_w32(x2, inv, ws[0], ws[1], K)
 
     def decode_uses_library(self, rows) -> bool:
         """Does a decode step of `rows` rows run a library GEMM?  Above 32 rows, without the weight-streaming kernel, or

@@ -1025,7 +1025,8 @@ def batch_gemm(x, w, slab_rows=0, mode=0) -> Partials:
 
 
 def _batch_q(entry, x, planes, args, M, N, K, mode):
-    """Plan + launch of one psg_batch_*_w8 / _w4 entry: `args` = the pointers between ctx and `part`."""
+    """Plan + launch of one psg_batch_*_w8 / _w4 or psg_batch_split_gemm_w16 / _w32 entry: `args` =
+    what stands between ctx and `part`."""
     import ctypes
     lib, ctx, st = _env(x)
     s = ctypes.c_int(0)
@@ -1081,6 +1082,55 @@ def batch_split_gemm_w4(x2, inv_scale, w4, e_img, col_scale, mode=0) -> Partials
     N = _w4_args("batch_split_gemm_w4", w4, e_img, col_scale, K)
     return _batch_q("batch_split_gemm_w4", x2, True,
                     (_p(x2), _p(inv_scale), _p(w4, name="w4"), _p(e_img, name="e_img"), _p(col_scale)), M, N, K, mode)
+
+
+def _rows16_args(name, what, w, K, col_scale, min_cols):
+    """A 2-D fp16 weight in HBM whose rows are contiguous runs of >= min_cols elements (any row stride: a view is read in
+    place) and its fp32 column scale [N].  Alignment is the library's check (PSG_ERR_UNSUPPORTED)."""
+    if w.dtype != torch.float16 or w.dim() != 2 or w.shape[1] < min_cols or (w.shape[1] > 1 and w.stride(1) != 1):
+        raise PsgHipError(f"{name}: {what} must be fp16 [N, >= {min_cols}] with contiguous rows (K = {K}), got {w.dtype} "
+                          f"{tuple(w.shape)} strides {tuple(w.stride())}")
+    N = w.shape[0]
+    if col_scale.dtype != torch.float32 or tuple(col_scale.shape) != (N,):
+        raise PsgHipError(f"{name}: col_scale must be fp32 [{N}], got {col_scale.dtype} {tuple(col_scale.shape)}")
+    if not w.is_cuda:
+        raise PsgHipError(f"{name}: {what} must live in HBM (got a {w.device} tensor); this path has no CPU fallback")
+    return N
+
+
+def batch_split_gemm_w16(x2, inv_scale, w16, col_scale=None, mode=0) -> Partials:
+    """`split_gemm_w16` for 33..160 fp32 rows given as the planes of `split_f16x2`, over a weight that is an fp16 value:
+    fp32 slices [S, M, N] of (xh . w + xl . w) * inv_scale * col_scale (psg_batch_split_gemm_w16).  w16 fp16
+    [N, K], rows of any 16-byte-aligned stride (a column view is read in place); col_scale None = ones.  N % 16 == 0,
+    K % 64 == 0.  A row's slices do not depend on M or on the other rows."""
+    M, K = _x2_args("batch_split_gemm_w16", x2, inv_scale)
+    if w16.dim() == 2 and w16.shape[1] != K:
+        raise PsgHipError(f"batch_split_gemm_w16: w16 must be fp16 [N, {K}], got {tuple(w16.shape)}")
+    if col_scale is None:
+        col_scale = torch.ones(w16.shape[0], device=x2.device, dtype=torch.float32)
+    N = _rows16_args("batch_split_gemm_w16", "w16", w16, K, col_scale, K)
+    return _batch_q("batch_split_gemm_w16", x2, True,
+                    (_p(x2), _p(inv_scale), w16.data_ptr(), int(w16.stride(0)) if N > 1 else K, _p(col_scale)), M, N, K, mode)
+
+
+def batch_split_gemm_w32(x2, inv_scale, w_img, col_scale, K, lo_off=None, mode=0) -> Partials:
+    """The fp32s product of 33..160 fp32 rows (planes of `split_f16x2`) with a generic fp32 weight held as two fp16 planes
+    inside ONE image, read in place: fp32 slices [S, M, N] of (xh . wh + xh . wl + xl . wh) * inv_scale * col_scale
+    (psg_batch_split_gemm_w32).  w_img fp16 [N, row]: wh at columns 0..K, wl at lo_off..lo_off + K (default K) -
+    `split_f16x3(w, weights=True)`'s [wh | wl | wh] image as it stands, or a packed [wh | wl] image; col_scale = that split's
+    inverse row scales.  N % 16 == 0, K % 64 == 0."""
+    M, Kx = _x2_args("batch_split_gemm_w32", x2, inv_scale)
+    K = int(K)
+    lo_off = K if lo_off is None else int(lo_off)
+    if Kx != K:
+        raise PsgHipError(f"batch_split_gemm_w32: x2 has K = {Kx}, the weight image K = {K}")
+    if lo_off < K or (w_img.dim() == 2 and lo_off + K > w_img.shape[1]):
+        raise PsgHipError(f"batch_split_gemm_w32: the low plane [{lo_off}, {lo_off + K}) must lie behind the high plane "
+                          f"[0, {K}) inside a row of {tuple(w_img.shape)}")
+    N = _rows16_args("batch_split_gemm_w32", "w_img", w_img, K, col_scale, 2 * K)
+    return _batch_q("batch_split_gemm_w32", x2, True,
+                    (_p(x2), _p(inv_scale), w_img.data_ptr(), int(w_img.stride(0)) if N > 1 else w_img.shape[1], lo_off,
+                     _p(col_scale)), M, N, K, mode)
 
 
 def skinny_gemm_fused(kind, x_out, w, sync, *, inp=None, resid=None, norm_w=None, eps=0.0, attn=None, splits=None):

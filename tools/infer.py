@@ -60,6 +60,9 @@ def parser():
     ap.add_argument("--llm-batch-weight-stream", choices=["dense", "quantised"], default="dense",
                     help="quantised: decode steps of 33..160 rows (several images decoded together) stream a quantised LLM's "
                     "bytes / nibbles instead of its dense weights, and never expand them with --llm-weight-resident quantised")
+    ap.add_argument("--llm-batch-split-gemm", choices=["library", "own"], default="library",
+                    help="own (--dtype fp32s): decode steps of 33..160 rows run the unquantised LLM matrices as split-fp16 products "
+                    "on the project's weight-streaming kernel instead of the library SGEMM / stacked-plane product")
     return ap
 
 
@@ -77,7 +80,8 @@ def build_head(a, dev):
                                          on_parse_error="skip", pair_selector=a.selector,
                                          llm_weight_quant=getattr(a, "llm_weight_quant", None),
                                          llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
-                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"))
+                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
+                                         llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
     else:
@@ -87,7 +91,8 @@ def build_head(a, dev):
                                          llm_config=llm, on_parse_error="skip", pair_selector=a.selector,
                                          llm_weight_quant=getattr(a, "llm_weight_quant", None),
                                          llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
-                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"))
+                                         llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
+                                         llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
