@@ -700,9 +700,11 @@ def skinny_gemm_plan(M, N, K, dtype, device) -> int:
     return s.value
 
 
-def skinny_gemm(x, w, splits=None) -> Partials:
+def skinny_gemm(x, w, splits=None, part=None) -> Partials:
     """Decode-step projection: fp32 split-K partials of x @ w.T (x: <= 32 rows of bf16 / fp16 / fp32, w of the
-    same type); every weight byte streams from HBM once.  Hand the result to a consumer kernel or call .reduce()."""
+    same type); every weight byte streams from HBM once.  Hand the result to a consumer kernel or call .reduce().
+    part: the caller's [splits, M, N] fp32 buffer for the partials (contiguous, 16-byte aligned: the kernels store
+    float4); None = a fresh allocation."""
     lib, ctx, st = _env(x)
     M, K = x.shape
     N = w.shape[0]
@@ -714,7 +716,13 @@ def skinny_gemm(x, w, splits=None) -> Partials:
         s = ctypes.c_int(0)
         check(lib.psg_skinny_gemm_plan(ctx, M, N, K, _dt(x), ctypes.byref(s)), "psg_skinny_gemm_plan")
         splits = s.value
-    part = torch.empty((splits, M, N), device=x.device, dtype=torch.float32)
+    if part is None:
+        part = torch.empty((splits, M, N), device=x.device, dtype=torch.float32)
+    elif tuple(part.shape) != (splits, M, N) or part.device != x.device:
+        raise PsgHipError(f"skinny_gemm: part must be [{splits}, {M}, {N}] on {x.device}, got {tuple(part.shape)} on "
+                          f"{part.device}")
+    elif _p(part, torch.float32, "part") % 16:
+        raise PsgHipError("skinny_gemm: part must be 16-byte aligned")
     check(lib.psg_skinny_gemm(ctx, _p(x, name="x"), _p(w, name="w"), _p(part), M, N, K, splits, _dt(x), st),
           "psg_skinny_gemm")
     return Partials(part)

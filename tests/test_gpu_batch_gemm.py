@@ -28,6 +28,10 @@ def _check(M, N, K, dtype, bn=0, seed=0, mode=0):
     err = (got.double() - ref).abs().max().item()
     # exact products of 16-bit operands, fp32 accumulation over K terms of magnitude ~ 1 / sqrt(K)
     assert err < 2e-5 * max(1.0, ref.abs().max().item()), f"M={M} N={N} K={K} bn={bn}: max error {err:.3e}, slots {part.splits}"
+    # and per element: fp32 accumulation alone, <= 2^-20 of |x| @ |w|^T (the bound of tests/gemm_ref.py)
+    A = x.double().abs() @ w.double().abs().t()
+    worst = ((got.double() - ref).abs() / A.clamp_min(1e-300)).max().item()
+    assert worst <= 2.0 ** -20, f"M={M} N={N} K={K} bn={bn} mode={mode}: worst |err| / (|x| @ |w|^T) = {worst:.3e} > 2^-20"
     assert torch.equal(part.reduce(torch.float32), got) or (part.reduce(torch.float32) - got).abs().max() < 1e-5
     return part
 

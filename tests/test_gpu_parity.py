@@ -802,6 +802,8 @@ def _fuzz_skinny_shapes():
 @pytest.mark.parametrize("M,N,K", [(20, 4096, 4096), (20, 4096, 11008), (1, 512, 256), (32, 768, 2752), (7, 32000, 4096)]
                          + _fuzz_skinny_shapes())
 def test_skinny_gemm_vs_fp32_reference(M, N, K):
+    """A max-norm check at the workload's shapes; the kernel's anchor - float64, per element, both 16-bit types, every
+    variant - is tests/test_gpu_gemm16_ref.py."""
     from openpsg_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(M * 7 + N)
