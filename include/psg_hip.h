@@ -79,8 +79,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *        psg_batch_gemm_w4(_plan), psg_batch_split_gemm_w4(_plan) added
  *   609  group-wise INT4 LLM weights (GPTQ / AWQ): psg_split_gemm_int4(_plan), psg_skinny_gemm_int4(_plan) added
  *   610  unquantised fp32s weights in the batched decode: psg_batch_split_gemm_w16(_plan), psg_batch_split_gemm_w32(_plan)
- *        added */
-#define PSG_ABI_VERSION 610
+ *        added
+ *   611  decode over the relation-name trie only: psg_trie_greedy_step added */
+#define PSG_ABI_VERSION 611
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -656,6 +657,25 @@ int psg_tree_attn(psg_ctx*, const void* q, const void* k_cache, const void* v_ca
 int psg_token_logprobs(psg_ctx*, const void* logits, int splits, int64_t rows, int vocab, const int32_t* row_node,
                        const int64_t* row_out, const int32_t* child_off, const int32_t* child_tok, int n_nodes,
                        int n_edges, float* out, int64_t out_len, int dtype, void* stream);
+/* psg_trie_greedy_step: psg_greedy_step with the arg-max restricted to the children of each row's trie node.
+ * Logits, step, max_new, eos, tokens, done, next_ids, tok_pos, embed / x_out as psg_greedy_step; child_off[n_nodes + 1] /
+ * child_tok[n_edges] as psg_token_logprobs (node 0 = root, node 1 + i = internal node i); edge_node[n_edges] = internal
+ * node an edge leads to, -1 for an EOS leaf.  node int32 [K] is the per-row state (read and written); logp fp32 [K] (may
+ * be NULL) accumulates the path's log-probability.  For a row k with done[k] == 0 and node[k] in [0, n_nodes):
+ * a child's value is its logit summed in slice order and rounded to `dtype` (the value psg_greedy_step compares); the
+ * child with the largest value wins, ties to the lower token id, and where no child compares greater than -inf (all NaN
+ * or -inf) the child with the lowest token id.  tokens[k][step] = next_ids[k] = tok, tok_pos[k] += 1; an EOS leaf sets
+ * done[k] = 1, any other edge node[k] = edge_node[c] + 1; x_out[k] = embed[tok].  logp[k] += logit[tok] - lse, the very
+ * value psg_token_logprobs writes for this row and child (the same device function forms lse over the WHOLE vocabulary;
+ * with fp32 partials under a 16-bit `dtype` the score keeps the unrounded fp32 sum, as psg_token_logprobs does, and only
+ * the comparison rounds).  Without logp only the children's logits are read.  A row that is done, whose node lies
+ * outside the tables or whose node has no child inside the vocabulary writes tokens[k][step] = -1, leaves node / logp /
+ * done alone, and embeds EOS (next_ids[k] = eos, tok_pos[k] += 1).  Deterministic: fixed reduction order, no atomics. */
+int psg_trie_greedy_step(psg_ctx*, const void* logits, int splits, int K, int vocab, int step, int max_new, int eos,
+                         const int32_t* child_off, const int32_t* child_tok, const int32_t* edge_node, int n_nodes,
+                         int n_edges, int32_t* node, float* logp, int32_t* tokens, int32_t* done, int32_t* next_ids,
+                         int32_t* tok_pos, const void* embed, int embed_dtype, int hidden, void* x_out, int x_dtype,
+                         int dtype, void* stream);
 
 /* ---- masked-mean object pooling of the v1-v3 detectors
  * (kings_sgg/models/detectors/openseed_relation.py:453-468):

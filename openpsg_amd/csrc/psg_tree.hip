@@ -7,6 +7,11 @@
 //                       variant is exact fp32 arithmetic (no split, no 16-bit products), like psg_attn_f32.hip.
 //   psg_token_logprobs  per logit row: log-sum-exp in fp32 (one pass, running max and sum), then logit[tok] - lse for
 //                       the row's trie children (CSR lists shared by all pairs).  Fixed reduction order, no atomics.
+//
+// Decode over the same trie only:
+//   psg_trie_greedy_step  psg_greedy_step with the arg-max restricted to the children of the row's trie node; the node
+//                       advances on the device, and the path's log-probability is accumulated with the log-sum-exp code
+//                       of psg_token_logprobs (row_lse_256: one copy, both kernels call it).
 #include "psg_common.h"
 
 namespace {
@@ -114,18 +119,14 @@ __device__ __forceinline__ float logit_at(const void* logits, int S, int64_t sli
   return a;
 }
 
-// One workgroup per logit row.
+// log-sum-exp of one logit row over the whole vocabulary, by a 256-thread workgroup (every thread calls it and gets the
+// value): one pass with a running max and sum per thread, a butterfly per wave, then the 4 waves in wave order.  The one
+// copy of this arithmetic: psg_token_logprobs and psg_trie_greedy_step both call it, so their results agree bit for bit.
 template <typename T>
-__global__ void __launch_bounds__(256)
-    token_logprobs_kernel(const void* __restrict__ logits, int S, int64_t rows, int vocab,
-                          const int32_t* __restrict__ row_node, const int64_t* __restrict__ row_out,
-                          const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_tok, int n_nodes,
-                          int n_edges, float* __restrict__ out, int64_t out_len) {
+__device__ __forceinline__ float row_lse_256(const void* __restrict__ logits, int S, int64_t slice, int64_t base,
+                                             int vocab) {
   __shared__ float s_m[4], s_s[4], s_lse;
-  const int64_t r = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t slice = rows * vocab;
-  const int64_t base = r * vocab;
   float m = -INFINITY, s = 0.f;
   for (int v = tid; v < vocab; v += 256) {
     const float x = logit_at<T>(logits, S, slice, base + v);
@@ -150,17 +151,120 @@ __global__ void __launch_bounds__(256)
     s_lse = mm + logf(ss);
   }
   __syncthreads();
+  return s_lse;
+}
+
+// One workgroup per logit row.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    token_logprobs_kernel(const void* __restrict__ logits, int S, int64_t rows, int vocab,
+                          const int32_t* __restrict__ row_node, const int64_t* __restrict__ row_out,
+                          const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_tok, int n_nodes,
+                          int n_edges, float* __restrict__ out, int64_t out_len) {
+  const int64_t r = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int64_t slice = rows * vocab;
+  const int64_t base = r * vocab;
+  const float lse = row_lse_256<T>(logits, S, slice, base, vocab);
   const int nd = row_node[r];
   if (nd < 0 || nd >= n_nodes) return;
   const int c0 = child_off[nd], c1 = child_off[nd + 1];
   const int64_t o0 = row_out[r];
-  const float lse = s_lse;
   for (int c = c0 + tid; c < c1; c += 256) {
     if (c < 0 || c >= n_edges) continue;
     const int64_t oi = o0 + (c - c0);
     if (oi < 0 || oi >= out_len) continue;
     const int tok = child_tok[c];
     out[oi] = (tok >= 0 && tok < vocab) ? logit_at<T>(logits, S, slice, base + tok) - lse : NAN;
+  }
+}
+
+// Candidate of the constrained arg-max: value (rounded to the activation type, as psg_greedy_step compares), token, edge.
+struct TrieBest {
+  float val;
+  int tok, edge;
+  int low_tok, low_edge;                                                // the child with the lowest token id (fallback)
+  __device__ __forceinline__ void take(float v, int t, int e) {
+    if (v > val || (v == val && t < tok)) { val = v; tok = t; edge = e; }
+  }
+  __device__ __forceinline__ void take_low(int t, int e) {
+    if (t < low_tok) { low_tok = t; low_edge = e; }
+  }
+};
+
+// One workgroup per decode row: the greedy step of psg_greedy_step with the arg-max restricted to the children of the
+// row's trie node.  T: activation type the candidate values are rounded to; TE / TX as in greedy_step_kernel.
+template <typename T, typename TE, typename TX>
+__global__ void __launch_bounds__(256)
+    trie_greedy_step_kernel(const void* __restrict__ logits, int S, int vocab, int step, int max_new, int eos,
+                            const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_tok,
+                            const int32_t* __restrict__ edge_node, int n_nodes, int n_edges, int32_t* __restrict__ node,
+                            float* __restrict__ logp, int32_t* __restrict__ tokens, int32_t* __restrict__ done,
+                            int32_t* __restrict__ next_ids, int32_t* __restrict__ tok_pos, const TE* __restrict__ embed,
+                            int hidden, TX* __restrict__ x_out) {
+  __shared__ float s_val[4];
+  __shared__ int s_tok[4], s_edge[4], s_ltok[4], s_ledge[4];
+  __shared__ int s_emit;
+  const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t slice = (int64_t)gridDim.x * vocab;
+  const int64_t base = (int64_t)k * vocab;
+  const int nd = node[k];
+  // workgroup-uniform: a finished row, or a state outside the tables, decodes nothing and reads no table
+  const bool live = done[k] == 0 && nd >= 0 && nd < n_nodes;
+  float lse = 0.f;
+  if (logp && live) lse = row_lse_256<T>(logits, S, slice, base, vocab);
+  TrieBest b = {-INFINITY, 0x7fffffff, -1, 0x7fffffff, -1};
+  if (live) {
+    int c0 = child_off[nd], c1 = child_off[nd + 1];
+    c0 = c0 < 0 ? 0 : c0;
+    c1 = c1 > n_edges ? n_edges : c1;
+    for (int c = c0 + tid; c < c1; c += 256) {
+      const int t = child_tok[c];
+      if (t < 0 || t >= vocab) continue;                                // never a candidate: its logit does not exist
+      b.take(Act<T>::rnd(logit_at<T>(logits, S, slice, base + t)), t, c);
+      b.take_low(t, c);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(b.val, o, 64);
+    const int ot = __shfl_xor(b.tok, o, 64), oe = __shfl_xor(b.edge, o, 64);
+    const int lt = __shfl_xor(b.low_tok, o, 64), le = __shfl_xor(b.low_edge, o, 64);
+    b.take(ov, ot, oe);
+    b.take_low(lt, le);
+  }
+  if (lane == 0) { s_val[w] = b.val; s_tok[w] = b.tok; s_edge[w] = b.edge; s_ltok[w] = b.low_tok; s_ledge[w] = b.low_edge; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < 4; ++i) {
+      b.take(s_val[i], s_tok[i], s_edge[i]);
+      b.take_low(s_ltok[i], s_ledge[i]);
+    }
+    // no child compared greater than -inf (all NaN or -inf): the child with the lowest token id
+    if (b.edge < 0 || !(b.val > -INFINITY)) { b.tok = b.low_tok; b.edge = b.low_edge; }
+    int emit = (eos >= 0 && eos < vocab) ? eos : 0;                     // a row that decodes nothing embeds EOS: harmless
+    if (live && b.edge >= 0) {
+      emit = b.tok;
+      tokens[(int64_t)k * max_new + step] = emit;
+      const int nx = edge_node[b.edge];
+      if (nx < 0) done[k] = 1;
+      else node[k] = nx + 1;
+      if (logp) logp[k] += logit_at<T>(logits, S, slice, base + emit) - lse;   // psg_token_logprobs' value for this edge
+    } else {
+      tokens[(int64_t)k * max_new + step] = -1;
+    }
+    next_ids[k] = emit;
+    tok_pos[k] += 1;
+    s_emit = emit;
+  }
+  if (x_out) {                                                          // kernel-uniform
+    __syncthreads();
+    const TE* src = embed + (int64_t)s_emit * hidden;
+    for (int c = tid * 4; c < hidden; c += 256 * 4) {
+      float v[4];
+      Act<TE>::ld4(src, c, v);
+      Act<TX>::st4(x_out, (int64_t)k * hidden + c, v);
+    }
   }
 }
 
@@ -211,5 +315,39 @@ extern "C" int psg_token_logprobs(psg_ctx* ctx_, const void* logits, int splits,
                          logits, splits, rows, vocab, row_node, row_out, child_off, child_tok, n_nodes, n_edges, out,
                          out_len)));
   PSG_CHECK_LAUNCH("psg_token_logprobs");
+  return PSG_OK;
+}
+
+extern "C" int psg_trie_greedy_step(psg_ctx* ctx_, const void* logits, int splits, int K, int vocab, int step, int max_new,
+                                    int eos, const int32_t* child_off, const int32_t* child_tok, const int32_t* edge_node,
+                                    int n_nodes, int n_edges, int32_t* node, float* logp, int32_t* tokens, int32_t* done,
+                                    int32_t* next_ids, int32_t* tok_pos, const void* embed, int embed_dtype, int hidden,
+                                    void* x_out, int x_dtype, int dtype, void* stream) {
+  PSG_REQUIRE(ctx_ && logits && tokens && done && next_ids && tok_pos && node, PSG_ERR_INVALID,
+              "psg_trie_greedy_step: NULL argument");
+  PSG_REQUIRE(child_off && child_tok && edge_node, PSG_ERR_INVALID, "psg_trie_greedy_step: NULL trie table");
+  PSG_REQUIRE(n_nodes >= 1 && n_edges >= 0, PSG_ERR_INVALID, "psg_trie_greedy_step: n_nodes=%d n_edges=%d", n_nodes,
+              n_edges);
+  PSG_REQUIRE(K > 0 && vocab > 0 && step >= 0 && step < max_new && splits >= 0 && splits <= 64, PSG_ERR_INVALID,
+              "psg_trie_greedy_step: K=%d vocab=%d step=%d max_new=%d splits=%d", K, vocab, step, max_new, splits);
+  PSG_REQUIRE(!x_out || (embed && hidden > 0 && hidden % 4 == 0), PSG_ERR_INVALID,
+              "psg_trie_greedy_step: x_out needs the embedding table and hidden %% 4 == 0 (hidden=%d)", hidden);
+  hipStream_t st = (hipStream_t)stream;
+#define TGS(TE_, TX_)                                                                                                 \
+  PSG_DISPATCH_DTYPE(dtype, "psg_trie_greedy_step",                                                                   \
+                     (trie_greedy_step_kernel<T, TE_, TX_><<<K, 256, 0, st>>>(                                        \
+                         logits, splits, vocab, step, max_new, eos, child_off, child_tok, edge_node, n_nodes, n_edges, \
+                         node, logp, tokens, done, next_ids, tok_pos, (const TE_*)embed, hidden, (TX_*)x_out)))
+  if (!x_out || (embed_dtype == PSG_F32 && x_dtype == PSG_F32)) TGS(float, float);
+  else if (embed_dtype == PSG_BF16 && x_dtype == PSG_BF16) TGS(bf16_t, bf16_t);
+  else if (embed_dtype == PSG_BF16 && x_dtype == PSG_F32) TGS(bf16_t, float);
+  else if (embed_dtype == PSG_F16 && x_dtype == PSG_F16) TGS(f16_t, f16_t);
+  else if (embed_dtype == PSG_F16 && x_dtype == PSG_F32) TGS(f16_t, float);
+  else {
+    psg_set_error("psg_trie_greedy_step: embedding dtype %d -> residual dtype %d unsupported", embed_dtype, x_dtype);
+    return PSG_ERR_UNSUPPORTED;
+  }
+#undef TGS
+  PSG_CHECK_LAUNCH("psg_trie_greedy_step");
   return PSG_OK;
 }

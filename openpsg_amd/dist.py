@@ -89,6 +89,9 @@ class HipBackend:
         if getattr(head, "llm_rel_scores", "constant") != "constant":
             raise PsgHipError("pair-sharded pipelines score LLM triples with the constant 1 only; "
                               "llm_rel_scores='likelihood' runs on one GPU (head.forward / submit)")
+        if getattr(head, "llm_decode", "greedy") != "greedy":
+            raise PsgHipError("pair-sharded pipelines run the free greedy decode only; llm_decode='constrained' runs on one "
+                              "GPU (head.forward / submit / forward_batch)")
         self.head = head
         # the same object truncation (V4:136) and selector options as head.forward, so sharded == single GPU
         self._ids = lambda scene: [int(i) for i in scene["object_id_list"][:head.max_object_num]]

@@ -77,6 +77,8 @@ class _Pending:
                 out["selected_host"] = sel.cpu().numpy()
                 if out.get("rel_logscores") is not None:
                     out["logscores_host"] = out["rel_logscores"].cpu().numpy()
+                if out.get("path_logp") is not None:
+                    out["path_logp_host"] = out["path_logp"].cpu().numpy()
             if h.has_multiclass:
                 out["mc_host"] = self.rq["mc_topk"].cpu().numpy()
         self.rq.update(out)
@@ -229,6 +231,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # the decoder's probability of emitting the relation name and stopping
                  num_llm_ranked_triples=0,     # 'likelihood': the N best remaining (pair, class) triples of the selected
                                                # pairs follow the generated ones (at most 4096)
+                 llm_decode='greedy',          # 'greedy' = free greedy decode, parse keeps what is a class name (V4:305-321) |
+                                               # 'constrained' = every step's arg-max runs over the relation-name trie only:
+                                               # each selected pair yields exactly one valid relation in max_depth + 1
+                                               # steps, and with 'likelihood' its score comes out of the same launches
+                                               # 
                  llm_weight_quant=None,        # None | 'fp8': the LLM's q/k/v/o/gate/up/down matrices as OCP e4m3fn bytes with one
                                                # fp32 scale per output row (weights.quantize_fp8_rows): decode
                                                # steps of <= 32 rows stream 1 byte per weight.  The model IS the quantised one
@@ -321,6 +328,18 @@ class RelationTransformerHeadV4(nn.Module):
         if llm_rel_scores == "likelihood" and not implicit_bos:
             raise PsgHipError("llm_rel_scores='likelihood' needs implicit_bos=True: a candidate is what generate emits after "
                               "the prompt, and with implicit_bos=False parse reads nothing from a text without '<s>'")
+        if llm_decode not in ("greedy", "constrained"):
+            raise PsgHipError(f"llm_decode must be 'greedy' or 'constrained', got {llm_decode!r}")
+        if llm_decode == "constrained" and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_decode='constrained' constrains the LLM's decode; rel_cls_type={rel_cls_type!r} has no LLM "
+                              "stage")
+        if llm_decode == "constrained" and not implicit_bos:
+            raise PsgHipError("llm_decode='constrained' needs implicit_bos=True: a candidate is what generate emits after the "
+                              "prompt, and with implicit_bos=False parse reads nothing from a text without '<s>'")
+        if llm_decode == "constrained" and suppress_eos:
+            raise PsgHipError("llm_decode='constrained' cannot run with suppress_eos=True: a constrained sequence is a relation "
+                              "name followed by EOS by definition")
+        self.llm_decode = llm_decode
         # 'binary': existence head -> top-20 pairs -> LLM decode (V4:206-209, 235-237).  'multiclass' in the type: one
         # sigmoid score per (pair, relation class) from multiclass_rel_cls_pred, the diagonal zeroed, the top
         # `num_multiclass_triples` (pair, class) scores returned behind the LLM triples (V4:238-257, 355-356)
@@ -432,7 +451,7 @@ class RelationTransformerHeadV4(nn.Module):
             self.relation_qformer_tokenizer, self.llm_tokenizer = tokenizers
         self.llm_tokenizer.pad_token = self.llm_tokenizer.unk_token        # V4:105
         self._rel_trie = self._rel_trie_tok = None
-        if self.llm_rel_scores == "likelihood":
+        if self.llm_rel_scores == "likelihood" or self.llm_decode == "constrained":
             self.relation_trie()                                            # checks the candidates now: fails early
         self.last = {}
         self._gather_cache = {}
@@ -1093,7 +1112,8 @@ class RelationTransformerHeadV4(nn.Module):
                     extra = 4 - Xall.shape[0] % 4                        # graphs few (copies of the last pair, cut below)
                     Xall = torch.cat([Xall, Xall[-1:].expand(extra, -1, -1)])
                     pall = torch.cat([pall, pall[-1:].expand(extra)])
-                tokens = self.llm_engine.generate(Xall, pall, suppress_eos=self.suppress_eos, slot=gslot)
+                tokens = self.llm_engine.generate(Xall, pall, suppress_eos=self.suppress_eos, slot=gslot,
+                                                  constraint=self._constraint())
         return _PendingBatch(self, st, items, results, tokens, mcs).result()
 
     def image_constants(self, feat, meta, obj_ids, pan):
@@ -1448,9 +1468,13 @@ class RelationTransformerHeadV4(nn.Module):
         # deferring leaves later chunks un-enqueued when the next image's front half starts: only when the decode steps
         # hold own kernels alone (library GEMMs of two streams side by side were seen to hang, `submit`)
         defer = bool(defer) and eng.use_skinny and sel_in.numel() <= 32 and not eng.decode_uses_library(sel_in.numel())
-        trie = self.relation_trie() if self.llm_rel_scores == "likelihood" else None
+        con = self._constraint()
+        scored = self.llm_rel_scores == "likelihood"
+        # a constrained decode scores the triple it emits itself: the trie pass (and its cache slots) is needed only for
+        # the ranked triples behind it
+        trie = self.relation_trie() if scored and (con is None or self.num_llm_ranked_triples > 0) else None
         res = eng.generate(X, plen, suppress_eos=self.suppress_eos, return_first_logits=True, slot=slot, gate=gate,
-                           defer=defer, trie=trie)
+                           defer=defer, trie=trie, constraint=con, path_logp=scored and con is not None)
         out = dict(llm_inputs=X[:K], prompt_len=plen[:K])
 
         def finish():
@@ -1458,6 +1482,8 @@ class RelationTransformerHeadV4(nn.Module):
             out["tokens"], out["first_logits"] = r[0][:K], r[1][:K]
             if trie is not None:                                # padding copies of the threshold selector are cut here
                 out["rel_logscores"] = r[2][:K]
+            if scored and con is not None:
+                out["path_logp"] = r[-1][:K]
         if defer:
             out["_finish"] = finish
             return out
@@ -1466,10 +1492,19 @@ class RelationTransformerHeadV4(nn.Module):
             out["tokens_host"], out["selected_host"] = out["tokens"].cpu().numpy(), sel.cpu().numpy()
             if trie is not None:
                 out["logscores_host"] = out["rel_logscores"].cpu().numpy()
+            if out.get("path_logp") is not None:
+                out["path_logp_host"] = out["path_logp"].cpu().numpy()
         return out
+
+    def _constraint(self):
+        """The trie the decode is constrained to (llm_decode='constrained'), or None."""
+        return self.relation_trie() if self.llm_decode == "constrained" else None
 
     def _parse_out(self, out, N):
         """rel_pred / rel_score of the LLM stage from a decode's host copies."""
+        if out.get("path_logp_host") is not None:
+            return self.parse_path_scored(out["tokens_host"], out["selected_host"], N, out["path_logp_host"],
+                                          out.get("logscores_host"))
         if self.llm_rel_scores == "likelihood":
             return self.parse_scored(out["tokens_host"], out["selected_host"], N, out["logscores_host"])
         return self.parse(out["tokens_host"], out["selected_host"], N)
@@ -1527,6 +1562,17 @@ class RelationTransformerHeadV4(nn.Module):
         return assemble(self._parse_pairs(tokens_host, selected_host, object_num), log_scores, selected_host, object_num,
                         self.num_llm_ranked_triples)
 
+    def parse_path_scored(self, tokens_host, selected_host, object_num, path_logp, log_scores=None):
+        """`parse` of a constrained decode with llm_rel_scores='likelihood': pair k's triple scored exp(path_logp[k]), the
+        probability the decode steps themselves gave its candidate (s(p, r) of DESIGN 11 without the trie pass).
+        log_scores [K, R] (the trie pass, num_llm_ranked_triples > 0): the ranked triples follow as in `parse_scored`."""
+        pairs = self._parse_pairs(tokens_host, selected_host, object_num)
+        own = [float(np.exp(np.float64(path_logp[k]))) for k, _ in pairs]
+        if log_scores is None:
+            return [list(t) for _, t in pairs], own
+        rel_pred, rel_score = assemble(pairs, log_scores, selected_host, object_num, self.num_llm_ranked_triples)
+        return rel_pred, own + rel_score[len(own):]
+
     def relation_trie(self):
         """The token trie of the relation classes' candidate sequences under the current LLM tokenizer (rel_scores.py),
         built and checked at construction and again whenever `llm_tokenizer` is replaced."""
@@ -1543,4 +1589,8 @@ class RelationTransformerHeadV4(nn.Module):
             self._rel_trie = build_relation_trie(tok, list(relation_categories), self.cfg.llm.eos, self.cfg.llm.vocab,
                                                  parse_classes)
             self._rel_trie_tok = tok
+            if self.llm_decode == "constrained" and self.cfg.max_new_tokens < self._rel_trie.max_depth + 1:
+                need, self._rel_trie = self._rel_trie.max_depth + 1, None
+                raise PsgHipError(f"llm_decode='constrained': max_new_tokens={self.cfg.max_new_tokens} is below the relation "
+                                  f"trie's depth + 1 = {need}: the longest class name could not finish")
         return self._rel_trie

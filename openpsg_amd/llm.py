@@ -1315,7 +1315,7 @@ class LlamaDecodeEngine:
 
     @torch.no_grad()
     def generate(self, X, prompt_len, max_new_tokens=None, suppress_eos=False, return_first_logits=False, slot=0,
-                 gate=None, defer=False, trie=None):
+                 gate=None, defer=False, trie=None, constraint=None, path_logp=False):
         """Batched greedy decode.  X [K, 32+Tp, D]; prompt_len int32 [K] (# of prompt tokens).
         Returns tokens int32 [K, max_new] (device; -1 after a pair's EOS) and optionally the
         first-step logits [K, vocab].
@@ -1336,18 +1336,36 @@ class LlamaDecodeEngine:
         returns what the direct call returns.  `head.submit` hands it to the pending result, so that `result()` stays
         the only host wait of an image in flight.
         trie (`rel_scores.RelationTrie`): the relation-likelihood pass runs inside the prompt-pass graph (`_rank_pass`)
-        and the result gains a third entry, the log scores [K, R] (fp32) - returned as (tokens, first_logits, scores)."""
+        and the result gains a third entry, the log scores [K, R] (fp32) - returned as (tokens, first_logits, scores).
+        constraint (`rel_scores.RelationTrie`): decode over the trie only - every step's arg-max runs over the
+        children of the pair's trie node (`ops.trie_greedy_step`), so every pair emits exactly one candidate (a class name
+        + EOS) in constraint.max_depth + 1 greedy steps: ONE graph, no early-exit chunks and no read-back.  path_logp: the
+        log-probability of each pair's emitted sequence, fp32 [K], is appended to the result (behind the scores of
+        `trie`, if any)."""
         max_new = self.cfg.max_new_tokens if max_new_tokens is None else max_new_tokens
+        n_steps = max_new
+        if constraint is not None:
+            n_steps = constraint.max_depth + 1
+            if max_new < n_steps:
+                raise PsgHipError(f"constrained decode: max_new_tokens={max_new} is below the trie's depth + 1 = {n_steps}: "
+                                  "the longest candidate could not finish, and a truncated one parses to nothing")
+            if suppress_eos:
+                raise PsgHipError("constrained decode: a constrained sequence ends in EOS by definition (suppress_eos=True)")
+        elif path_logp:
+            raise PsgHipError("path_logp is the log-probability of a constrained decode's path: it needs constraint=")
         if not self.use_graph:
             outs = self._finish(self._generate_eager(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot,
-                                                     trie=trie), return_first_logits)
+                                                     trie=trie, constraint=constraint, path_logp=path_logp),
+                                return_first_logits)
             return (lambda: outs) if defer else outs
-        chunk = 0 if suppress_eos else int(self.early_exit_chunk)
-        split = gate is not None and max_new > 1
+        chunk = 0 if suppress_eos or constraint is not None else int(self.early_exit_chunk)
+        split = gate is not None and n_steps > 1
         key = (tuple(X.shape), max_new, bool(suppress_eos), bool(return_first_logits), chunk, int(slot), split,
                bool(self.row_invariant))
         if trie is not None:
             key = key + (trie.key,)
+        if constraint is not None:
+            key = key + ("constraint", constraint.key, bool(path_logp))
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)
@@ -1363,12 +1381,13 @@ class LlamaDecodeEngine:
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):                      # warm-up: lazy library init must not be captured
-                self._generate_eager(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
+                self._generate_eager(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
+                                     constraint=constraint, path_logp=path_logp)
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
             if self.persistent_layer:
                 self._dl_host_buf = pinned
-            bounds = [max_new] if chunk <= 0 else list(range(chunk, max_new, chunk)) + [max_new]
+            bounds = [n_steps] if chunk <= 0 else list(range(chunk, max_new, chunk)) + [max_new]
             if split:                                          # the gate sits right behind the prompt pass + first token
                 bounds = [1] + bounds
             bounds = sorted(set(bounds))
@@ -1377,7 +1396,8 @@ class LlamaDecodeEngine:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=graphs[0][0].pool() if graphs else None):
                     if st is None:
-                        st = self._prefill(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
+                        st = self._prefill(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
+                                           constraint=constraint, path_logp=path_logp)
                         self._steps(st, 1, hi)
                     else:
                         self._steps(st, lo, hi)
@@ -1415,6 +1435,8 @@ class LlamaDecodeEngine:
             outs = (st["tokens"].clone(), None if fl is None else fl.clone())
             if st.get("rank") is not None:
                 outs = outs + (st["rank"].clone(),)
+            if st.get("logp") is not None:
+                outs = outs + (st["logp"].clone(),)
             return self._finish(outs, return_first_logits)
         if defer and chunk > 0:
             advance(2 if split else 1)                          # prompt pass (+ gate) + the first chunk of steps: no host wait
@@ -1437,16 +1459,26 @@ class LlamaDecodeEngine:
                 raise PsgHipError("psg_decode_layer: a hand-off poll timed out (cnt[PSG_DL_TIMEOUT] set); the tokens of this "
                                   "generation are invalid - disable option decode_persistent")
 
-    def _generate_eager(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None):
-        st = self._prefill(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie)
-        self._steps(st, 1, max_new)
+    def _generate_eager(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None,
+                        constraint=None, path_logp=False):
+        st = self._prefill(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
+                           constraint=constraint, path_logp=path_logp)
+        self._steps(st, 1, max_new if constraint is None else constraint.max_depth + 1)
         if not torch.cuda.is_current_stream_capturing():
             self._check_persistent(st)
+            # every path of the trie ends in an EOS leaf within max_depth + 1 edges: checked once, never inside a capture
+            if constraint is not None and not bool(st["done"].all().item()):
+                raise PsgHipError("constrained decode: a pair did not reach an EOS leaf of the trie in max_depth + 1 steps "
+                                  "(trie tables and decode state disagree)")
+        outs = (st["tokens"], st["first_logits"])
         if trie is not None:
-            return st["tokens"], st["first_logits"], st["rank"]
-        return st["tokens"], st["first_logits"]
+            outs = outs + (st["rank"],)
+        if st["logp"] is not None:
+            outs = outs + (st["logp"],)
+        return outs
 
-    def _prefill(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None):
+    def _prefill(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None, constraint=None,
+                 path_logp=False):
         """Prompt pass + first greedy token (+ the relation-likelihood pass over `trie`, whose rows own the cache slots
         behind the decode region).  Returns the decode state (KV caches, token / flag buffers)."""
         m = self.cfg.llm
@@ -1480,9 +1512,18 @@ class LlamaDecodeEngine:
         sup = m.eos if suppress_eos else -1
         x = torch.empty((K, D), device=dev, dtype=self.resid_dtype)   # residual stream of the decode rows
         # the greedy step also writes the chosen token's embedding row into x: the next step's input, no gather launch
-        ops.greedy_step(logits, 0, max_new, m.eos, sup, tokens, done, next_ids, dec_pos,
-                        dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed, x_out=x)
-        return dict(kc=kc, vc=vc, ctx_len=ctx_len, tokens=tokens, done=done, next_ids=next_ids, dec_pos=dec_pos,
+        node = logp = ctab = None
+        if constraint is not None:                              # the same launch slot, the arg-max over the root's children
+            ctab = constraint.device(dev)
+            node = torch.zeros(K, device=dev, dtype=torch.int32)
+            logp = torch.zeros(K, device=dev, dtype=torch.float32) if path_logp else None
+            ops.trie_greedy_step(logits, 0, max_new, m.eos, ctab, node, tokens, done, next_ids, dec_pos, logp=logp,
+                                 dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed, x_out=x)
+        else:
+            ops.greedy_step(logits, 0, max_new, m.eos, sup, tokens, done, next_ids, dec_pos,
+                            dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed, x_out=x)
+        return dict(node=node, logp=logp, con_trie=constraint, con_tables=ctab,     # kept alive with the graph, as rank_trie
+                    kc=kc, vc=vc, ctx_len=ctx_len, tokens=tokens, done=done, next_ids=next_ids, dec_pos=dec_pos,
                     dec_pair=dec_pair, sup=sup, x=x, max_new=max_new, first_logits=first_logits, slot=int(slot), rank=rank,
                     # a captured graph reads the trie's device tables by address: the decode state (which the graph entry
                     # holds) keeps the trie and its tables alive as long as the graph, whatever becomes of the head's trie
@@ -1561,6 +1602,12 @@ class LlamaDecodeEngine:
             else:
                 h = self._forward(st["x"], st["dec_pair"], st["dec_pos"], st["kc"], st["vc"], st["ctx_len"], decode=True)
                 logits = self.logits(h)
+            if st.get("con_tables") is not None:
+                ops.trie_greedy_step(logits, step, st["max_new"], m.eos, st["con_tables"], st["node"], st["tokens"],
+                                     st["done"], st["next_ids"], st["dec_pos"], logp=st["logp"],
+                                     dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed,
+                                     x_out=st["x"])
+                continue
             ops.greedy_step(logits, step, st["max_new"], m.eos, st["sup"], st["tokens"], st["done"], st["next_ids"],
                             st["dec_pos"], dtype=torch.float32 if self.exact_argmax else self.dtype, embed=self.embed,
                             x_out=st["x"])

@@ -688,6 +688,31 @@ def greedy_step(logits, step, max_new, eos, suppress_token, tokens, done, next_i
                               _p(tok_pos, torch.int32), ep, ed, hid, xp, xd, dt, st), "psg_greedy_step")
 
 
+def trie_greedy_step(logits, step, max_new, eos, tables, node, tokens, done, next_ids, tok_pos, logp=None, dtype=None,
+                     embed=None, x_out=None):
+    """`greedy_step` over the children of each row's trie node only (psg_trie_greedy_step).  tables: the device dict of a
+    `rel_scores.RelationTrie` (child_off, child_tok, edge_node); node int32 [K]: the rows' trie nodes, advanced in place;
+    logp fp32 [K] or None: gains logit[tok] - logsumexp(row) of the chosen edge, bit-equal to `token_logprobs`."""
+    lib, ctx, st = _env(tokens)
+    K, vocab = logits.shape
+    if isinstance(logits, Partials):
+        lp, ls, dt = _p(logits.t), logits.splits, _DT[dtype or torch.bfloat16]
+    else:
+        lp, ls, dt = _p(logits), 0, _dt(logits)
+    if x_out is not None:
+        assert embed is not None and x_out.shape == (K, embed.shape[1])
+        ep, ed, hid, xp, xd = _p(embed), _dt(embed), embed.shape[1], _p(x_out), _dt(x_out)
+    else:
+        ep, ed, hid, xp, xd = None, 0, 0, None, 0
+    co, ct, en = tables["child_off"], tables["child_tok"], tables["edge_node"]
+    assert node.numel() == K and en.numel() == ct.numel() and (logp is None or logp.numel() == K)
+    check(lib.psg_trie_greedy_step(ctx, lp, ls, K, vocab, int(step), int(max_new), int(eos), _p(co, torch.int32),
+                                   _p(ct, torch.int32), _p(en, torch.int32), co.numel() - 1, ct.numel(),
+                                   _p(node, torch.int32), None if logp is None else _p(logp, torch.float32),
+                                   _p(tokens, torch.int32), _p(done, torch.int32), _p(next_ids, torch.int32),
+                                   _p(tok_pos, torch.int32), ep, ed, hid, xp, xd, dt, st), "psg_trie_greedy_step")
+
+
 def skinny_gemm_plan(M, N, K, dtype, device) -> int:
     """Split count psg_skinny_gemm would use for x [M, K] of `dtype` against w [N, K]; raises PsgHipError where the kernel
     does not take the shape (psg_skinny_gemm_plan: row count, divisibility, the fp32 kernel's LDS bound)."""

@@ -121,6 +121,7 @@ class RelationTrie:
             t = lambda a, dt=torch.int32: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)  # noqa: E731
             ent = self._dev[dev] = dict(node_tok=t(self.node_tok), node_depth=t(self.node_depth), anc=t(self.anc),
                                         child_off=t(self.child_off), child_tok=t(self.child_tok),
+                                        edge_node=t(self.edge_node),
                                         path=t(self.path, torch.int64))
         return ent
 
