@@ -80,8 +80,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   609  group-wise INT4 LLM weights (GPTQ / AWQ): psg_split_gemm_int4(_plan), psg_skinny_gemm_int4(_plan) added
  *   610  unquantised fp32s weights in the batched decode: psg_batch_split_gemm_w16(_plan), psg_batch_split_gemm_w32(_plan)
  *        added
- *   611  decode over the relation-name trie only: psg_trie_greedy_step added */
-#define PSG_ABI_VERSION 611
+ *   611  decode over the relation-name trie only: psg_trie_greedy_step added
+ *   612  bf16-valued LLM weights streamed as bf16 in the fp32s decode steps: psg_split_b16x3, psg_rmsnorm_split_b16x3,
+ *        psg_silu_mul_split_b16x3, psg_split_gemm_wb16(_plan) added */
+#define PSG_ABI_VERSION 612
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -363,6 +365,29 @@ int psg_rmsnorm_split2(psg_ctx*, float* resid, const float* delta, int delta_spl
 int psg_split_gemm_w16_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
 int psg_split_gemm_w16(psg_ctx*, const void* x2, const float* inv_scale, const void* w_f16, float* part, int M, int N, int K,
                        int slots, int mode, void* stream);
+/* Weights that are bf16 VALUES (a bf16 checkpoint upcast on load) in the fp32s decode steps.  An fp32 number is
+ * exactly the sum of three bf16 numbers, x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1) (round to nearest even;
+ * both differences exact), and bf16 has fp32's exponent range: no row scale.
+ *   psg_split_b16x3           fp32 rows (row_stride elements apart, K % 4 == 0) -> bf16 planes out3 [3][rows][K]
+ *   psg_rmsnorm_split_b16x3   psg_rmsnorm_split2's contract with the result as those planes: bit-identical to psg_rmsnorm
+ *                             followed by psg_split_b16x3
+ *   psg_silu_mul_split_b16x3  psg_silu_mul's contract on fp32 gate|up (splits fp32 slices summed in slice order, 0 = dense
+ *                             rows) with the result as the planes [3][rows][inter]: bit-identical to psg_silu_mul followed
+ *                             by psg_split_b16x3
+ *   psg_split_gemm_wb16       x3 bf16 [3][M][K], w bf16 [N][K] streamed ONCE -> fp32 slices part[slots][M][N] for the
+ *                             consumers of psg_skinny_gemm: k-ordered, no atomics, unused slots zero-filled.  Every product is
+ *                             exact in fp32; per slice and plane p one k-ordered fp32 accumulation acc[p], stored as
+ *                             (acc[2] + acc[1]) + acc[0].  M <= 32, N % 16 == 0, K % 64 == 0, 16-byte aligned operands
+ *                             (else PSG_ERR_UNSUPPORTED before any launch); slots must equal the plan's (<= 16); mode 1 / 2:
+ *                             slab-aligned / stream-K ranges, 0 = the library's estimate.  psg_batch_gemm's kernel with three
+ *                             x tiles. */
+int psg_split_b16x3(psg_ctx*, const float* x, int64_t rows, int K, int64_t row_stride, void* out3, void* stream);
+int psg_rmsnorm_split_b16x3(psg_ctx*, float* resid, const float* delta, int delta_splits, const float* w, float eps,
+                            int64_t rows, int hidden, void* out3, void* stream);
+int psg_silu_mul_split_b16x3(psg_ctx*, const float* gate_up, int splits, int64_t rows, int inter, void* out3, void* stream);
+int psg_split_gemm_wb16_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_split_gemm_wb16(psg_ctx*, const void* x3, const void* w_bf16, float* part, int M, int N, int K, int slots, int mode,
+                        void* stream);
 /* The decode-step projections over an FP8-quantised weight: the model's weight is W'[n][k] = e4m3(w8[n][k]) *
  * col_scale[n] (OCP e4m3fn bytes [N][K], fp32 per-row scales [N]; openpsg_amd/weights.py quantize_fp8_rows).  w8 streams
  * from HBM ONCE per call as one byte per weight, is widened exactly to the x operand's 16-bit type in registers and

@@ -41,12 +41,16 @@ constexpr int bg_nst(int) { return 3; }
 // activations, [2][M][K] - staged as x tiles 0 and 1; every wave owns both tiles and ONE weight tile (8 waves along the
 // weight rows), the two accumulators are added at the flush and multiplied by the row's inverse power-of-two scale:
 // part[slot][m][n] = (xh . w + xl . w) 2^-t, M rows.
-template <typename E, int MT, int TJ, int WM = 2, bool PAIR = false>
+// PAIR = 3 (psg_split_gemm_wb16): x holds the THREE bf16 planes [3][M][K] of psg_split_b16.h (x = x0 + x1 + x2 exactly), w is
+// a bf16 value: three x tiles, three accumulators - acc[p] is the k-ordered sum of plane p's (exact) products alone - added
+// at the flush from the smallest plane up, part[slot][m][n] = (acc[2] + acc[1]) + acc[0]; no row scale.
+template <typename E, int MT, int TJ, int WM = 2, int PAIR = 0>
 __global__ void __launch_bounds__(BG_WAVES * 64, 1)
 batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, float* __restrict__ part, int M, int N,
                   int K, int S, int S_al, int var, const float* __restrict__ row_scale, int wt) {
   using v8 = typename E::v8;
-  static_assert(!PAIR || (MT == 2 && WM == 1 && TJ == 1), "the pair form is two x tiles, one weight tile per wave");
+  static_assert(PAIR == 0 || PAIR == 2 || PAIR == 3, "plain, two fp16 planes or three bf16 planes");
+  static_assert(!PAIR || (MT == PAIR && WM == 1 && TJ == 1), "the plane forms are one x tile per plane, one weight tile per wave");
   constexpr int WN = BG_WAVES / WM, TI = (MT + WM - 1) / WM, BM = MT * 32, BN = WN * TJ * 32;
   constexpr int STAGE = (BM + BN) * 128;                     // one unit: [x: BM rows | w: BN rows] x 128 B
   constexpr int NST = bg_nst(STAGE);
@@ -76,7 +80,7 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
     if (idx < XI) {
       if (var == 3 && kt > 0) return;
       int gr = r < M ? r : M - 1;
-      if (PAIR) gr = (r >> 5) * M + ((r & 31) < M ? (r & 31) : M - 1);      // plane r >> 5, row r & 31 of [2][M][K]
+      if (PAIR) gr = (r >> 5) * M + ((r & 31) < M ? (r & 31) : M - 1);      // plane r >> 5, row r & 31 of [PAIR][M][K]
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(x + (int64_t)gr * K + kt * BG_BK + piece * 8),
           (__attribute__((address_space(3))) void*)(sb + idx * 1024), 16, 0, 0);
@@ -207,7 +211,7 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
       // D[m][n]: register r of a lane = row 8 (r >> 2) + 4 hi + (r & 3) of the tile, column lane & 31.  Row pointers are
       // wave-uniform (scalar), the lane adds ONE 32-bit offset: no per-store address registers
       const int lane_off = 4 * hi * N + l31;
-      if constexpr (PAIR) {
+      if constexpr (PAIR != 0) {
         for (int s_ = slot; s_ < nslots; ++s_) {
           float* ps = part + (int64_t)s_ * M * N;
           const bool real = s_ == slot;
@@ -218,7 +222,9 @@ batch_gemm_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w
               const int mrow = 8 * (r >> 2) + (r & 3);
               float* rowp = ps + (int64_t)mrow * N + n0;
               if (mrow + 4 * hi < M) {
-                const float val = real ? (acc[0][0][r] + acc[1][0][r]) * row_scale[mrow + 4 * hi] : 0.f;
+                float val = 0.f;
+                if constexpr (PAIR == 3) val = real ? (acc[2][0][r] + acc[1][0][r]) + acc[0][0][r] : 0.f;
+                else val = real ? (acc[0][0][r] + acc[1][0][r]) * row_scale[mrow + 4 * hi] : 0.f;
                 if (wt)                                      // option wt_stores: agent-scope store = written through the L2
                   __hip_atomic_store(reinterpret_cast<unsigned*>(rowp + lane_off), __float_as_uint(val), __ATOMIC_RELAXED,
                                      __HIP_MEMORY_SCOPE_AGENT);
@@ -267,10 +273,12 @@ struct bg_plan {
 
 // Candidates: BN = 256 / 128 weight rows per slab x psg_sk_make_plan's {aligned slices, stream-K}, the cheapest estimate.
 // The unit's cost: L2 -> LDS staging of both tiles at ~40 B/clk/CU, or the unit's share of the HBM stream.
-static bg_plan bg_make_plan(const psg_ctx* ctx, int64_t M, int N, int K, int bn, int mode_, bool pair = false) {
+// planes: 0 = psg_batch_gemm, 2 / 3 = the plane forms of <= 32 rows (psg_split_gemm_w16 / psg_split_gemm_wb16)
+static bg_plan bg_make_plan(const psg_ctx* ctx, int64_t M, int N, int K, int bn, int mode_, int planes = 0) {
+  const bool pair = planes != 0;
   bg_plan best{0, 0, 0, 0, 0};
   double best_t = 1e300;
-  const int mt = (pair || M <= 64) ? 2 : M <= 96 ? 3 : 5;
+  const int mt = pair ? planes : M <= 64 ? 2 : M <= 96 ? 3 : 5;
   int G = ctx->num_cu;
   if (G > BG_GRID_MAX) G = BG_GRID_MAX;
   if (ctx->opt.batch_gemm_grid > 0 && ctx->opt.batch_gemm_grid < G) G = ctx->opt.batch_gemm_grid;
@@ -306,7 +314,7 @@ extern "C" int psg_batch_gemm_plan(psg_ctx* ctx, int64_t M, int N, int K, int dt
   return PSG_OK;
 }
 
-template <typename E, int MT, int TJ, int WM = 2, bool PAIR = false>
+template <typename E, int MT, int TJ, int WM = 2, int PAIR = 0>
 static int bg_launch(const bg_plan& p, const void* x, const void* w, float* part, int M, int N, int K, int var,
                      void* stream, const float* row_scale = nullptr, int wt = 0) {
   constexpr int STAGE = (MT * 32 + (BG_WAVES / WM) * TJ * 32) * 128;
@@ -346,7 +354,7 @@ extern "C" int psg_split_gemm_w16_plan(psg_ctx* ctx, int M, int N, int K, int mo
   PSG_REQUIRE(M >= 1 && M <= 32 && N >= 16 && N % 16 == 0 && K >= BG_BK && K % BG_BK == 0 && mode >= 0 && mode <= 2,
               PSG_ERR_UNSUPPORTED, "psg_split_gemm_w16: M=%d (1..32), N=%d (multiple of 16), K=%d (multiple of %d), mode=%d", M,
               N, K, BG_BK, mode);
-  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, true);
+  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, 2);
   PSG_REQUIRE(p.grid > 0 && p.slots <= PSG_MAX_SPLITS, PSG_ERR_UNSUPPORTED,
               "psg_split_gemm_w16_plan: no plan with <= %d slices for M=%d N=%d K=%d", PSG_MAX_SPLITS, M, N, K);
   *slots = p.slots;
@@ -361,7 +369,39 @@ extern "C" int psg_split_gemm_w16(psg_ctx* ctx, const void* x2, const float* inv
   if (rc != PSG_OK) return rc;
   PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "psg_split_gemm_w16: slots=%d, the plan for M=%d N=%d K=%d writes %d", slots, M,
               N, K, want);
-  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, true);
-  return bg_launch<EF16, 2, 1, 1, true>(p, x2, w16, part, M, N, K, ctx->opt.batch_gemm_var, stream, inv_scale,
-                                        (ctx->opt.wt_stores >> 1) & 1);
+  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, 2);
+  return bg_launch<EF16, 2, 1, 1, 2>(p, x2, w16, part, M, N, K, ctx->opt.batch_gemm_var, stream, inv_scale,
+                                     (ctx->opt.wt_stores >> 1) & 1);
+}
+
+// ---- fp32 activations x weights that are bf16 values, as THREE bf16 products on the 16-bit matrix cores ----------------
+// x = x0 + x1 + x2 exactly (psg_split_b16x3: planes [3][M][K], no scale), w exactly bf16 (a bf16 checkpoint - Mistral-7B,
+// Llama-3 - that the reference upcasts on load): x . w = x0 . w + x1 . w + x2 . w with every product exact in fp32 and NO
+// split residual - what differs from the fp32 product is the order of the fp32 sums alone.  M <= 32 rows.  The unit is
+// (96 + 256) rows x 128 B = 44 KB, the ring of three 132 KB of the 160 KB LDS; 12 MFMAs per wave and K step.
+extern "C" int psg_split_gemm_wb16_plan(psg_ctx* ctx, int M, int N, int K, int mode, int* slots) {
+  PSG_REQUIRE(ctx && slots, PSG_ERR_INVALID, "psg_split_gemm_wb16_plan: NULL argument");
+  PSG_REQUIRE(M >= 1 && M <= 32 && N >= 16 && N % 16 == 0 && K >= BG_BK && K % BG_BK == 0 && mode >= 0 && mode <= 2,
+              PSG_ERR_UNSUPPORTED, "psg_split_gemm_wb16: M=%d (1..32), N=%d (multiple of 16), K=%d (multiple of %d), mode=%d", M,
+              N, K, BG_BK, mode);
+  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, 3);
+  PSG_REQUIRE(p.grid > 0 && p.slots <= PSG_MAX_SPLITS, PSG_ERR_UNSUPPORTED,
+              "psg_split_gemm_wb16_plan: no plan with <= %d slices for M=%d N=%d K=%d", PSG_MAX_SPLITS, M, N, K);
+  *slots = p.slots;
+  return PSG_OK;
+}
+
+extern "C" int psg_split_gemm_wb16(psg_ctx* ctx, const void* x3, const void* wb16, float* part, int M, int N, int K, int slots,
+                                   int mode, void* stream) {
+  PSG_REQUIRE(ctx && x3 && wb16 && part, PSG_ERR_INVALID, "psg_split_gemm_wb16: NULL argument");
+  int want = 0;
+  const int rc = psg_split_gemm_wb16_plan(ctx, M, N, K, mode, &want);
+  if (rc != PSG_OK) return rc;
+  PSG_REQUIRE(slots == want, PSG_ERR_INVALID, "psg_split_gemm_wb16: slots=%d, the plan for M=%d N=%d K=%d writes %d", slots, M,
+              N, K, want);
+  PSG_REQUIRE(((uintptr_t)x3 | (uintptr_t)wb16 | (uintptr_t)part) % 16 == 0, PSG_ERR_UNSUPPORTED,
+              "psg_split_gemm_wb16: x3, w and part must be 16-byte aligned (16-byte DMA loads)");
+  const bg_plan p = bg_make_plan(ctx, M, N, K, 0, mode, 3);
+  return bg_launch<EBf16, 3, 1, 1, 3>(p, x3, wb16, part, M, N, K, ctx->opt.batch_gemm_var, stream, nullptr,
+                                      (ctx->opt.wt_stores >> 1) & 1);
 }

@@ -12,6 +12,7 @@
 
 #include "psg_common.h"
 #include "psg_decode_math.h"
+#include "psg_split_b16.h"
 
 // ---- LayerNorm over a row held in registers ---------------------------------------------------
 template <int NCH>
@@ -858,7 +859,9 @@ extern "C" int psg_rope_kvwrite_gqa(psg_ctx* ctx_, const void* qkv, int qkv_spli
 }
 
 // ---- SwiGLU gate ------------------------------------------------------------------------------
-template <typename T>
+// P3 (psg_silu_mul_split_b16x3, T = float): the fp32 result goes out as the three bf16 planes [3][rows][inter] of
+// psg_split_b16.h instead of fp32 rows - `out` is the planes' base
+template <typename T, bool P3 = false>
 __global__ void __launch_bounds__(256) silu_mul_kernel(const void* __restrict__ gu, int S, int64_t rows, int inter, T* __restrict__ out,
                                                        int wt = 0) {
   const int64_t n4 = rows * inter / 4;
@@ -882,6 +885,11 @@ __global__ void __launch_bounds__(256) silu_mul_kernel(const void* __restrict__ 
       float s = g[e] / (1.0f + expf(-g[e]));
       s = Act<T>::rnd(s);  // HF rounds act_fn(gate) before the product
       o[e] = s * u[e];
+    }
+    if constexpr (P3) {
+      uint16_t* o0 = reinterpret_cast<uint16_t*>(out) + r * inter;
+      sp_store3(o0, o0 + rows * inter, o0 + 2 * rows * inter, c, o, wt);
+      continue;
     }
     if constexpr (std::is_same<T, float>::value) {
       if (wt) {
@@ -937,6 +945,24 @@ extern "C" int psg_silu_mul(psg_ctx* ctx, const void* gate_up, int splits, int64
                      (silu_mul_kernel<T><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(
                          gate_up, splits, rows, inter, (T*)out, ((ctx->opt.wt_stores & 1) && rows <= 64) ? 1 : 0)));
   PSG_CHECK_LAUNCH("psg_silu_mul");
+  return PSG_OK;
+}
+
+// psg_silu_mul on fp32 split-K slices followed by psg_split_b16x3, bit for bit, in one launch (element-wise: no row
+// reduction, so the SwiGLU gate needs no split launch of its own on the bf16 route)
+extern "C" int psg_silu_mul_split_b16x3(psg_ctx* ctx, const float* gate_up, int splits, int64_t rows, int inter, void* out3,
+                                        void* stream) {
+  PSG_REQUIRE(ctx && gate_up && out3, PSG_ERR_INVALID, "psg_silu_mul_split_b16x3: NULL argument");
+  PSG_REQUIRE(inter > 0 && inter % 4 == 0 && rows >= 0 && rows < (1ll << 31), PSG_ERR_INVALID,
+              "psg_silu_mul_split_b16x3: inter=%d must be a multiple of 4", inter);
+  PSG_REQUIRE(splits >= 0 && splits <= PSG_MAX_SPLITS, PSG_ERR_INVALID,
+              "psg_silu_mul_split_b16x3: splits=%d (0: dense fp32 gate|up rows, else fp32 split-K slices)", splits);
+  if (rows == 0) return PSG_OK;
+  int64_t blocks = (rows * inter / 4 + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  silu_mul_kernel<float, true><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(
+      gate_up, splits, rows, inter, (float*)out3, (rows <= 64) ? (ctx->opt.wt_stores >> 2) & 1 : 0);
+  PSG_CHECK_LAUNCH("psg_silu_mul_split_b16x3");
   return PSG_OK;
 }
 

@@ -18,6 +18,7 @@
 // element down to 2^-13 of the row's maximum (below that the absolute error is bounded by fp16's subnormal spacing,
 // 2^-24 x the row scale).  inv_scale[row] = 2^-t undoes it after the GEMM (psg_scale_rows_cols), exactly.
 #include "psg_common.h"
+#include "psg_split_b16.h"
 
 #define SP_ORDER_HHL 0   // activations: [xh | xh | xl]
 #define SP_ORDER_HLH 1   // weights:     [wh | wl | wh]
@@ -532,7 +533,9 @@ __device__ __forceinline__ void sp_store2(uint16_t* oh, uint16_t* ol, int c, con
 }
 
 // rmsnorm_kernel<float, NCH, float> (psg_rowops.hip: nthr threads per row, the same loads, sums and roundings) + the split
-template <int NCH>
+// PL = 2: the fp16 planes of psg_split_f16x2 + the row's inverse scale; PL = 3: the bf16 planes of psg_split_b16x3 (no row
+// maximum, no scale: inv_scale is not touched)
+template <int NCH, int PL = 2>
 __global__ void __launch_bounds__(1024) rmsnorm_split2_kernel(float* __restrict__ resid, const void* __restrict__ delta,
                                                               int dsplits, int64_t dslice, const float* __restrict__ w,
                                                               float eps, int hidden, int64_t rows,
@@ -587,9 +590,15 @@ __global__ void __launch_bounds__(1024) rmsnorm_split2_kernel(float* __restrict_
       }
       o[c][0] = g[c].x * (v[c][0] * inv); o[c][1] = g[c].y * (v[c][1] * inv);
       o[c][2] = g[c].z * (v[c][2] * inv); o[c][3] = g[c].w * (v[c][3] * inv);
+      if constexpr (PL == 3) {
+        sp_store3(out2 + row * (int64_t)hidden, out2 + (rows + row) * (int64_t)hidden,
+                  out2 + (2 * rows + row) * (int64_t)hidden, col, o[c], wt);
+        continue;
+      }
       mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o[c][0]), fabsf(o[c][1]))), fmaxf(fabsf(o[c][2]), fabsf(o[c][3])));
     }
   }
+  if constexpr (PL == 3) return;
   mx = wave_max(mx);
   if (lane == 0) s_max[wid] = mx;
   __syncthreads();
@@ -605,20 +614,21 @@ __global__ void __launch_bounds__(1024) rmsnorm_split2_kernel(float* __restrict_
   }
 }
 
-extern "C" int psg_rmsnorm_split2(psg_ctx* ctx, float* resid, const float* delta, int delta_splits, const float* w, float eps,
-                                  int64_t rows, int hidden, void* out2, float* inv_scale, void* stream) {
-  PSG_REQUIRE(ctx && resid && w && out2 && inv_scale, PSG_ERR_INVALID, "psg_rmsnorm_split2: NULL argument");
+template <int PL>
+static int rmsnorm_split_planes(const char* name, psg_ctx* ctx, float* resid, const float* delta, int delta_splits, const float* w,
+                                float eps, int64_t rows, int hidden, void* out, float* inv_scale, void* stream) {
+  PSG_REQUIRE(ctx && resid && w && out && (inv_scale || PL == 3), PSG_ERR_INVALID, "%s: NULL argument", name);
   PSG_REQUIRE(hidden % 4 == 0 && hidden > 0 && hidden <= 8192 && rows >= 0 && rows < (1ll << 31), PSG_ERR_UNSUPPORTED,
-              "psg_rmsnorm_split2: hidden=%d (multiple of 4, <= 8192)", hidden);
+              "%s: hidden=%d (multiple of 4, <= 8192)", name, hidden);
   PSG_REQUIRE(delta_splits >= 0 && delta_splits <= PSG_MAX_SPLITS && (!delta || delta_splits >= 1), PSG_ERR_INVALID,
-              "psg_rmsnorm_split2: delta_splits=%d (fp32 split-K slices)", delta_splits);
+              "%s: delta_splits=%d (fp32 split-K slices)", name, delta_splits);
   if (rows == 0) return PSG_OK;
   const int nthr = (rows <= 64 && hidden >= 4096) ? 1024 : 256;       // psg_rmsnorm's choice: the same summation tree
   const int nch = (hidden + 4 * nthr - 1) / (4 * nthr);
   hipStream_t st = (hipStream_t)stream;
-#define RS2(N)                                                                                                          \
-  rmsnorm_split2_kernel<N><<<(unsigned)rows, nthr, 0, st>>>(resid, delta, delta_splits, rows * (int64_t)hidden, w, eps, \
-                                                            hidden, rows, (uint16_t*)out2, inv_scale, (ctx->opt.wt_stores >> 2) & 1)
+#define RS2(N)                                                                                                              \
+  rmsnorm_split2_kernel<N, PL><<<(unsigned)rows, nthr, 0, st>>>(resid, delta, delta_splits, rows * (int64_t)hidden, w, eps, \
+                                                                hidden, rows, (uint16_t*)out, inv_scale, (ctx->opt.wt_stores >> 2) & 1)
   switch (nch) {
     case 1: RS2(1); break;
     case 2: RS2(2); break;
@@ -630,6 +640,50 @@ extern "C" int psg_rmsnorm_split2(psg_ctx* ctx, float* resid, const float* delta
     default: RS2(8); break;
   }
 #undef RS2
-  PSG_CHECK_LAUNCH("psg_rmsnorm_split2");
+  PSG_CHECK_LAUNCH(name);
   return PSG_OK;
+}
+
+extern "C" int psg_rmsnorm_split2(psg_ctx* ctx, float* resid, const float* delta, int delta_splits, const float* w, float eps,
+                                  int64_t rows, int hidden, void* out2, float* inv_scale, void* stream) {
+  return rmsnorm_split_planes<2>("psg_rmsnorm_split2", ctx, resid, delta, delta_splits, w, eps, rows, hidden, out2, inv_scale,
+                                 stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Decode steps of the fp32s mode over bf16-valued weights (psg_split_gemm_wb16): fp32 rows as the three bf16 planes
+// [3][rows][K] of psg_split_b16.h - exact, element-wise, no row scale.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) split_b16x3_kernel(const float* __restrict__ x, int64_t row_stride, int K, int64_t rows,
+                                                          uint16_t* __restrict__ out, int wt) {
+  const int k4 = K / 4;
+  const int64_t n4 = rows * k4, plane = rows * (int64_t)K;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / k4;
+    const int c = (int)(i - r * k4) * 4;
+    const float4 t = *reinterpret_cast<const float4*>(x + r * row_stride + c);
+    const float v[4] = {t.x, t.y, t.z, t.w};
+    uint16_t* o0 = out + r * (int64_t)K;
+    sp_store3(o0, o0 + plane, o0 + 2 * plane, c, v, wt);
+  }
+}
+
+extern "C" int psg_split_b16x3(psg_ctx* ctx, const float* x, int64_t rows, int K, int64_t row_stride, void* out3, void* stream) {
+  PSG_REQUIRE(ctx && x && out3, PSG_ERR_INVALID, "psg_split_b16x3: NULL argument");
+  PSG_REQUIRE(rows >= 0 && K > 0 && K % 4 == 0 && row_stride >= K && row_stride % 4 == 0 && rows < (1ll << 31),
+              PSG_ERR_INVALID, "psg_split_b16x3: rows=%lld K=%d stride=%lld", (long long)rows, K, (long long)row_stride);
+  if (rows == 0) return PSG_OK;
+  int64_t blocks = (rows * (K / 4) + 255) / 256;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  split_b16x3_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, row_stride, K, rows, (uint16_t*)out3,
+                                                                        (rows <= 64) ? (ctx->opt.wt_stores >> 2) & 1 : 0);
+  PSG_CHECK_LAUNCH("psg_split_b16x3");
+  return PSG_OK;
+}
+
+// psg_rmsnorm (fp32 rows, fp32 split-K slices summed in slice order) followed by psg_split_b16x3, bit for bit, in one launch
+extern "C" int psg_rmsnorm_split_b16x3(psg_ctx* ctx, float* resid, const float* delta, int delta_splits, const float* w,
+                                       float eps, int64_t rows, int hidden, void* out3, void* stream) {
+  return rmsnorm_split_planes<3>("psg_rmsnorm_split_b16x3", ctx, resid, delta, delta_splits, w, eps, rows, hidden, out3, nullptr,
+                                 stream);
 }

@@ -262,6 +262,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # the SGEMM / the stacked-plane fp16 product (today's launches).  'own':
                                                # psg_batch_gemm_s.hip - two fp16 products over an fp16-valued weight, three
                                                # over the prompt pass's split image of a generic one (4 bytes per weight)
+                 llm_bf16_value_stream=False,  # True: an fp32s head whose LLM matrices are bf16 VALUES (a bf16 checkpoint -
+                                               # Mistral-7B, Llama-3 - upcast on load; verified per tensor) streams bf16
+                                               # copies in the decode steps of <= 32 rows (psg_split_gemm_wb16: 2 bytes per
+                                               # weight, three exact bf16 products).  A model whose matrices are not
+                                               # bf16 values runs exactly as with False (`llm_engine.bf16_stream_active`)
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -300,6 +305,20 @@ class RelationTransformerHeadV4(nn.Module):
                               "the 16-bit modes already run psg_batch_gemm there, and the exact 'fp32' mode keeps its exact SGEMM "
                               "- use dtype='fp32s' or llm_batch_split_gemm='library'")
         self.llm_batch_split_gemm = llm_batch_split_gemm
+        if not isinstance(llm_bf16_value_stream, bool):
+            raise PsgHipError(f"llm_bf16_value_stream must be True or False, got {llm_bf16_value_stream!r}")
+        if llm_bf16_value_stream and "binary" not in rel_cls_type:
+            raise PsgHipError(f"llm_bf16_value_stream=True is about the LLM's decode steps; rel_cls_type={rel_cls_type!r} has "
+                              "no LLM stage")
+        if llm_bf16_value_stream and dtype != "fp32s":
+            raise PsgHipError(f"llm_bf16_value_stream=True streams bf16-valued weights under the fp32s decode steps; "
+                              f"dtype={dtype!r}: the 16-bit modes already stream 2 bytes per weight, and the exact 'fp32' mode "
+                              "keeps its fp32 products - use dtype='fp32s' or llm_bf16_value_stream=False")
+        if llm_bf16_value_stream and llm_weight_quant is not None:
+            raise PsgHipError(f"llm_bf16_value_stream=True streams the UNQUANTISED bf16 values of the LLM; with "
+                              f"llm_weight_quant={llm_weight_quant!r} the decode steps stream the quantised bytes - set one of "
+                              "the two")
+        self.llm_bf16_value_stream = llm_bf16_value_stream
         if llm_quantize_lm_head and llm_weight_quant is None:
             raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4' or 'int4g'")
         # group-wise INT4 has the decode kernels of <= 32 rows only: no expand kernel, no 33..160-row kernel
@@ -551,7 +570,8 @@ class RelationTransformerHeadV4(nn.Module):
                                              resid_dtype=self.resid_dtype, prefill_split=self.prefill_split,
                                              resident=self.llm_weight_resident,
                                              batch_quant_stream=self.llm_batch_weight_stream == "quantised",
-                                             batch_split_gemm=self.llm_batch_split_gemm == "own")
+                                             batch_split_gemm=self.llm_batch_split_gemm == "own",
+                                             bf16_value_stream=self.llm_bf16_value_stream)
         return self
 
     def quantize_llm_weights(self, weights: dict) -> dict:

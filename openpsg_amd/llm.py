@@ -290,6 +290,18 @@ def _batch_split_route(form, N, K, rows, table=None):
     return "own"
 
 
+# fp32s decode steps of <= 32 rows over bf16-VALUED matrices, engine option bf16_value_stream: psg_split_gemm_wb16
+# streams the bf16 copy (2 bytes per weight, three bf16 products) where the steps above stream the fp32 tensor on
+# psg_skinny_gemm (4 bytes per weight).  A FIXED table like INT4_STREAM_OFF: a listed (N, K) is a measured loser
+# (tools/bf16_stream_bench.py at 20 rows: the kernel's range of times not wholly below the fp32 kernel's) and switches the
+# route off for a model that has a decoder matrix of that shape; a shape that is not listed takes the route.
+# Measured (profiles/bf16_stream_bench.json; us per launch, median (min-max), bf16 stream against the fp32 kernel): q|k|v 24.7
+# (23.7-28.3) against 39.1 (37.7-44.2), o 11.0 (10.6-11.6) against 15.0 (14.9-15.1), gate|up 38.0 (37.2-39.3) against 65.0
+# (63.8-71.4), down 21.0 (20.8-21.3) against 35.3 (35.0-36.4), lm_head 64.1 (62.9-64.3) against 99.4 (97.0-100.0): every
+# Llama-2-7B shape lies wholly below its yardstick, nothing is listed.
+WB16_STREAM_OFF: frozenset = frozenset()
+
+
 class QuantMatrix:
     """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
     `lm_head` hold in place of W'.  Carries the shape and dtype W' would have and the quantised parts - (q, s) for FP8,
@@ -317,7 +329,8 @@ class QuantMatrix:
 
 class LlamaDecodeEngine:
     def __init__(self, weights: dict, cfg: PSGConfig, device, dtype=torch.bfloat16, n_layers=None, resid_dtype=None,
-                 prefill_split=False, resident="all", batch_quant_stream=False, batch_split_gemm=False):
+                 prefill_split=False, resident="all", batch_quant_stream=False, batch_split_gemm=False,
+                 bf16_value_stream=False):
         """prefill_split (fp32 engines): the prompt pass's projections as split-fp16 products on the 16-bit matrix cores,
         `linear_split` below; the decode steps stay exact fp32 (psg_gemm_f32.hip).
         resid_dtype: storage type of the residual stream; None = `dtype` (what HF keeps for a model cast to 16
@@ -326,7 +339,10 @@ class LlamaDecodeEngine:
         batch_quant_stream: decode steps of 33..160 rows stream a quantised matrix's bytes (`_batch_quant`)
         instead of reading W'.
         batch_split_gemm (fp32s engines): decode steps of 33..160 rows run an unquantised matrix on psg_batch_gemm_s.hip
-        (`_batch_split`) instead of the library GEMM."""
+        (`_batch_split`) instead of the library GEMM.
+        bf16_value_stream (fp32s engines): decoder matrices and an lm_head that are bf16 VALUES (a bf16 checkpoint upcast on
+        load; verified per tensor) keep a bf16 copy, and the decode steps of <= 32 rows stream it on psg_split_gemm_wb16
+        (`_decode_step_wb16`) instead of the fp32 tensor."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
         if resident not in ("all", "quantised"):
@@ -556,6 +572,22 @@ class LlamaDecodeEngine:
                 if torch.equal(h.float(), t):
                     self._w16[t.data_ptr()] = h
             self._w16_all = len(self._w16) == len(tensors)      # the fused decode step / two-plane prompt pass need all of them
+        # bf16_value_stream: the same question for bf16 - Mistral-7B, Llama-3 and most current Llama-family checkpoints are
+        # bf16 on disk, and a bf16 value below fp16's subnormal grid (0.02 % of an N(0, 0.02) matrix) fails the round trip
+        # above.  Per tensor again: a matrix that is neither quantised nor in `_w16` and round-trips through bf16 keeps a
+        # bf16 copy (2 bytes per weight beside the fp32 tensor and its split image, which the prompt pass still reads)
+        if not isinstance(bf16_value_stream, bool):
+            raise PsgHipError(f"bf16_value_stream must be a bool, got {bf16_value_stream!r}")
+        self.bf16_value_stream = bf16_value_stream
+        self._wb16 = {}
+        if bf16_value_stream and dtype == torch.float32:
+            for t in [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]:
+                if (not isinstance(t, torch.Tensor) or t.data_ptr() in self._w16 or t.data_ptr() in self._w8
+                        or t.data_ptr() in self._w4 or t.data_ptr() in self._int4):
+                    continue
+                b = t.bfloat16()
+                if torch.equal(b.float(), t):
+                    self._wb16[t.data_ptr()] = b
         if self.prefill_split:
             # [wh | wl | wh] fp16 + the per-row power of two that undoes the row scaling, per projection (3 x 2 bytes per
             # weight next to the fp32 copy the decode steps stream: 40 GB + 27 GB for Llama-2-7B, of 288 GB)
@@ -706,7 +738,7 @@ class LlamaDecodeEngine:
                 for v in o:
                     walk(v)
         for name in ("embed", "lm_head", "lm_head_s", "final_norm", "proj_w", "proj_b", "proj_s", "layers", "rope", "_w8h", "_w4h",
-                     "_w16", "_i2_w", "_ones_cache"):
+                     "_w16", "_wb16", "_i2_w", "_ones_cache"):
             walk(getattr(self, name, None))
         return dict(quantised=quant, scratch=scratch, other=other, total=quant + scratch + other)
 
@@ -912,6 +944,9 @@ class LlamaDecodeEngine:
             return True
         if self._can_w16(rows) or self._can_w8(rows) or self._can_w4(rows):   # psg_split_gemm_w16 / _w8 / _w4 for every projection
             return False
+        if self._can_wb16(rows):                               # psg_split_gemm_wb16 for every decoder projection; the lm_head
+            head = self.lm_head                                # follows the stream its tensor has
+            return not (head.data_ptr() in self._wb16 or head.data_ptr() in self._w16 or self._streams(rows, head, self.dtype))
         L = self.layers[0] if self.layers else None
         ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
         return not all(self._streams(rows, w, self.dtype) for w in ws)
@@ -1144,6 +1179,52 @@ class LlamaDecodeEngine:
             a2, inv = ops.rmsnorm_split2(x, d, nxt, m.rms_eps)
         return ops.split_gemm_w16(a2, inv, wh[self.lm_head.data_ptr()])
 
+    @property
+    def bf16_stream_active(self):
+        """Does a decode step of this engine stream bf16 copies (`bf16_value_stream` set AND the model qualifies)?"""
+        return self._can_wb16(1)
+
+    def _can_wb16(self, rows):
+        """fp32s decode steps over bf16-valued decoder layers (option bf16_value_stream): every projection as
+        psg_split_gemm_wb16, the row kernels writing its three-plane operand directly (`_decode_step_wb16`)."""
+        if not self._wb16:
+            return False
+        m = self.cfg.llm
+        ws = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
+        return (all(w.data_ptr() in self._wb16 for w in ws) and self.prefill_split and self.use_skinny and rows <= 32
+                and self.dtype == torch.float32 and m.hidden % 64 == 0 and m.inter % 64 == 0 and m.hidden <= 8192
+                and self.qkv_width % 16 == 0 and not any(tuple(w.shape) in WB16_STREAM_OFF for w in ws))
+
+    def _decode_step_wb16(self, st):
+        """One decode step of the fp32s mode when the decoder matrices are bf16 values (`self._wb16`): 2 bytes per weight from
+        HBM, three bf16 products per projection (the exact three-plane form of the fp32 rows) on the 16-bit matrix cores.
+        RMSNorm and SwiGLU write the planes themselves (element-wise: no row maximum), the attention output has a split
+        launch of its own.  The lm_head runs on the stream ITS tensor has: bf16 values, fp16 values or fp32."""
+        m = self.cfg.llm
+        x, wb = st["x"], self._wb16
+        K, D = x.shape
+        att = torch.empty((K, D), device=self.device, dtype=torch.float32)
+        a3 = ops.rmsnorm_split_b16x3(x, None, self.layers[0]["ln1"], m.rms_eps)
+        for l, L in enumerate(self.layers):
+            qkv = ops.split_gemm_wb16(a3, wb[L["wqkv"].data_ptr()])
+            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
+                            st["vc"][l], att, kv_heads=self.kv)
+            o = ops.split_gemm_wb16(ops.split_b16x3(att), wb[L["wo"].data_ptr()])
+            a3 = ops.rmsnorm_split_b16x3(x, o, L["ln2"], m.rms_eps)
+            gu = ops.split_gemm_wb16(a3, wb[L["wgu"].data_ptr()])
+            d = ops.split_gemm_wb16(ops.silu_mul_split_b16x3(gu), wb[L["wdown"].data_ptr()])
+            if l + 1 < len(self.layers):
+                a3 = ops.rmsnorm_split_b16x3(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
+        head = self.lm_head.data_ptr()
+        if head in wb and m.vocab % 16 == 0:
+            return ops.split_gemm_wb16(ops.rmsnorm_split_b16x3(x, d, self.final_norm, m.rms_eps), wb[head])
+        if head in self._w16 and m.vocab % 16 == 0:
+            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
+            return ops.split_gemm_w16(a2, inv, self._w16[head])
+        n = torch.empty_like(x)
+        ops.rmsnorm(x, d, self.final_norm, m.rms_eps, n)
+        return self.logits(n)
+
     def _can_w8(self, rows):
         """fp32s decode steps over FP8-quantised decoder layers: every projection as psg_split_gemm_w8, the row kernels
         writing its two-plane operand directly (`_decode_step_w8`)."""
@@ -1366,6 +1447,8 @@ class LlamaDecodeEngine:
             key = key + (trie.key,)
         if constraint is not None:
             key = key + ("constraint", constraint.key, bool(path_logp))
+        if self.bf16_value_stream:
+            key = key + ("bf16_value_stream",)
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)
@@ -1571,8 +1654,9 @@ class LlamaDecodeEngine:
         """Decode steps lo .. hi-1 (step s writes tokens[:, s])."""
         m = self.cfg.llm
         self._slot = int(st.get("slot", 0))
-        persist = hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
-        w16 = not persist and self._can_w16(st["x"].shape[0])
+        wb16 = self._can_wb16(st["x"].shape[0])               # option bf16_value_stream: the user asked for the stream
+        persist = not wb16 and hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
+        w16 = not wb16 and not persist and self._can_w16(st["x"].shape[0])
         w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])
         w4 = not persist and not w16 and not w8 and self._can_w4(st["x"].shape[0])
         i4 = not persist and not w16 and not w8 and not w4 and self._can_int4(st["x"].shape[0])
@@ -1587,7 +1671,9 @@ class LlamaDecodeEngine:
             per_step = 2 * (4 * len(self.layers) + 1)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
         for step in range(lo, hi):
-            if persist:
+            if wb16:
+                logits = self._decode_step_wb16(st)
+            elif persist:
                 logits = self._decode_step_persistent(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             elif w16:
                 logits = self._decode_step_w16(st)

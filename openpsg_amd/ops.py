@@ -815,6 +815,100 @@ def split_gemm_w16(x2, inv_scale, w16, mode=0) -> Partials:
     return Partials(part)
 
 
+def _rows_f32(name, x):
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1):
+        raise PsgHipError(f"{name}: x must be fp32 [rows, K] with contiguous rows, got "
+                          f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    return x.shape
+
+
+def split_b16x3(x):
+    """fp32 rows -> bf16 planes [3, rows, K] with x == x0 + x1 + x2 EXACTLY (x0 = bf16(x), x1 = bf16(x - x0), x2 =
+    bf16(x - x0 - x1), round to nearest even; no row scale) - the operand of `split_gemm_wb16` (psg_split_b16x3)."""
+    rows, K = _rows_f32("split_b16x3", x)
+    lib, ctx, st = _env(x)
+    if K % 4 or x.stride(0) % 4 or x.data_ptr() % 16:
+        raise PsgHipError(f"split_b16x3: K={K} and the row stride {x.stride(0)} must be multiples of 4, x 16-byte aligned")
+    out = torch.empty((3, rows, K), device=x.device, dtype=torch.bfloat16)
+    check(lib.psg_split_b16x3(ctx, x.data_ptr(), rows, K, x.stride(0), _p(out), st), "psg_split_b16x3")
+    return out
+
+
+def rmsnorm_split_b16x3(resid, delta, w, eps):
+    """resid (fp32) += delta (Partials or None); RMSNorm(resid) * w as the three bf16 planes of `split_b16x3`, bf16
+    [3, rows, hidden] - psg_rmsnorm + psg_split_b16x3 in one launch, bit-identical (psg_rmsnorm_split_b16x3)."""
+    rows, hidden = _rows_f32("rmsnorm_split_b16x3", resid)
+    lib, ctx, st = _env(resid)
+    if not resid.is_contiguous() or not (delta is None or isinstance(delta, Partials)):
+        raise PsgHipError("rmsnorm_split_b16x3: resid must be contiguous and delta a Partials (fp32 split-K slices) or None")
+    if delta is not None and tuple(delta.t.shape[1:]) != (rows, hidden):
+        raise PsgHipError(f"rmsnorm_split_b16x3: delta slices {tuple(delta.t.shape)} do not match resid [{rows}, {hidden}]")
+    if w.numel() != hidden:
+        raise PsgHipError(f"rmsnorm_split_b16x3: w has {w.numel()} elements, hidden is {hidden}")
+    out = torch.empty((3, rows, hidden), device=resid.device, dtype=torch.bfloat16)
+    dp, ds = (None, 0) if delta is None else (_p(delta.t, torch.float32), delta.splits)
+    check(lib.psg_rmsnorm_split_b16x3(ctx, _p(resid), dp, ds, _p(w, torch.float32), float(eps), rows, hidden, _p(out), st),
+          "psg_rmsnorm_split_b16x3")
+    return out
+
+
+def silu_mul_split_b16x3(gate_up):
+    """silu(gate) * up of a gate|up projection result [rows, 2 inter] - Partials (fp32 split-K slices, summed in slice order)
+    or a dense fp32 tensor - as the three bf16 planes of `split_b16x3`, bf16 [3, rows, inter]: `silu_mul` into fp32 rows +
+    psg_split_b16x3 in one launch, bit-identical (psg_silu_mul_split_b16x3)."""
+    t = gate_up.t if isinstance(gate_up, Partials) else gate_up
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+            and t.dim() == (3 if isinstance(gate_up, Partials) else 2) and t.shape[-1] % 8 == 0):
+        raise PsgHipError("silu_mul_split_b16x3: gate_up must be fp32 split-K slices [S, rows, 2 inter] (Partials) or dense "
+                          f"fp32 rows [rows, 2 inter] with inter a multiple of 4, got {getattr(t, 'dtype', type(t))} "
+                          f"{tuple(getattr(t, 'shape', ()))}")
+    lib, ctx, st = _env(t)
+    rows, inter = t.shape[-2], t.shape[-1] // 2
+    out = torch.empty((3, rows, inter), device=t.device, dtype=torch.bfloat16)
+    splits = gate_up.splits if isinstance(gate_up, Partials) else 0
+    check(lib.psg_silu_mul_split_b16x3(ctx, _p(t), splits, rows, inter, _p(out), st), "psg_silu_mul_split_b16x3")
+    return out
+
+
+def split_gemm_wb16_plan(M, N, K, device, mode=0) -> int:
+    """Slices `split_gemm_wb16` writes for x3 [3, M, K] against w [N, K]; raises where the kernel does not take the shape."""
+    import ctypes
+    lib = _lib.load()
+    dev = torch.device(device)
+    s = ctypes.c_int(0)
+    check(lib.psg_split_gemm_wb16_plan(_lib.ctx(dev.index or 0), int(M), int(N), int(K), int(mode), ctypes.byref(s)),
+          "psg_split_gemm_wb16_plan")
+    return s.value
+
+
+def split_gemm_wb16(x3, wb16, mode=0, part=None) -> Partials:
+    """Decode-step projection of fp32 rows against a weight that is a bf16 value (a bf16 checkpoint upcast on load): three
+    bf16 products (the planes of `split_b16x3`, x0 + x1 + x2 == x exactly) on the 16-bit matrix cores, fp32 slices
+    [S, M, N] like `skinny_gemm`'s.  Every product is exact in fp32: only the fp32 accumulation separates the result from
+    the exact one (psg_split_gemm_wb16).  M <= 32, N % 16 == 0, K % 64 == 0, 16-byte aligned operands.
+    part: the caller's [S, M, N] fp32 buffer (S = `split_gemm_wb16_plan`); None = a fresh allocation."""
+    if not (isinstance(x3, torch.Tensor) and x3.dim() == 3 and x3.shape[0] == 3 and x3.dtype == torch.bfloat16
+            and x3.is_contiguous()):
+        raise PsgHipError("split_gemm_wb16: x3 must be the contiguous bf16 planes [3, M, K] of split_b16x3, got "
+                          f"{getattr(x3, 'dtype', type(x3))} {tuple(getattr(x3, 'shape', ()))}")
+    _, M, K = x3.shape
+    if not (isinstance(wb16, torch.Tensor) and wb16.dim() == 2 and wb16.dtype == torch.bfloat16 and wb16.shape[1] == K
+            and wb16.is_contiguous() and wb16.device == x3.device):
+        raise PsgHipError(f"split_gemm_wb16: w must be contiguous bf16 [N, {K}] on {x3.device}, got "
+                          f"{getattr(wb16, 'dtype', type(wb16))} {tuple(getattr(wb16, 'shape', ()))}")
+    lib, ctx, st = _env(x3)
+    N = wb16.shape[0]
+    S = split_gemm_wb16_plan(M, N, K, x3.device, mode)
+    if part is None:
+        part = torch.empty((S, M, N), device=x3.device, dtype=torch.float32)
+    elif (tuple(part.shape) != (S, M, N) or part.dtype != torch.float32 or part.device != x3.device
+          or not part.is_contiguous()):
+        raise PsgHipError(f"split_gemm_wb16: part must be contiguous fp32 [{S}, {M}, {N}] on {x3.device} (slots = the plan's), "
+                          f"got {part.dtype} {tuple(part.shape)}")
+    check(lib.psg_split_gemm_wb16(ctx, _p(x3), _p(wb16), _p(part), M, N, K, S, int(mode), st), "psg_split_gemm_wb16")
+    return Partials(part)
+
+
 def _w8_args(name, w8, col_scale, K):
     if w8.dtype not in (torch.uint8, torch.float8_e4m3fn) or w8.dim() != 2 or w8.shape[1] != K:
         raise PsgHipError(f"{name}: w8 must be e4m3fn bytes [N, {K}] (uint8 / float8_e4m3fn), got {w8.dtype} {tuple(w8.shape)}")

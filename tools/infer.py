@@ -63,6 +63,9 @@ def parser():
     ap.add_argument("--llm-batch-split-gemm", choices=["library", "own"], default="library",
                     help="own (--dtype fp32s): decode steps of 33..160 rows run the unquantised LLM matrices as split-fp16 products "
                     "on the project's weight-streaming kernel instead of the library SGEMM / stacked-plane product")
+    ap.add_argument("--llm-bf16-value-stream", action="store_true",
+                    help="(--dtype fp32s) stream LLM matrices that are bf16 values - a bf16 checkpoint such as Mistral-7B or "
+                    "Llama-3 - as bf16 in the decode steps: 2 bytes per weight, three exact bf16 products")
     ap.add_argument("--llm-decode", choices=["greedy", "constrained"], default="greedy",
                     help="constrained: every decode step's arg-max runs over the relation-name trie only - one valid relation "
                     "per selected pair in max_depth + 1 steps instead of 16")
@@ -85,6 +88,7 @@ def build_head(a, dev):
                                          llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
+                                         llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
                                          llm_decode=getattr(a, "llm_decode", "greedy"))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
@@ -97,6 +101,7 @@ def build_head(a, dev):
                                          llm_weight_resident=getattr(a, "llm_weight_resident", "all"),
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
+                                         llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
                                          llm_decode=getattr(a, "llm_decode", "greedy"))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
