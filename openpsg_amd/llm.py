@@ -301,6 +301,13 @@ def _batch_split_route(form, N, K, rows, table=None):
 # Llama-2-7B shape lies wholly below its yardstick, nothing is listed.
 WB16_STREAM_OFF: frozenset = frozenset()
 
+_LAYER_MATRICES = ("wqkv", "wo", "wgu", "wdown")                  # a decoder layer's projections, by their key in `layers`
+# The streams a matrix can have in a decode step of <= 32 rows (`LlamaDecodeEngine._stream`), each also the name of the step
+# route on which every decoder matrix has it (`_decode_route`) and the suffix of its pair-form entry ops.split_gemm_<kind>:
+# kind -> the planes of the fp32 rows that entry reads (two fp16 planes + a row scale, or three bf16 planes)
+_STREAM_PLANES = {"w16": 2, "w8": 2, "w4": 2, "int4": 2, "wb16": 3}
+_QUANT_STREAMS = {"w8": "fp8", "w4": "mxfp4", "int4": "int4"}      # ... of a quantised matrix -> the format it streams
+
 
 class QuantMatrix:
     """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
@@ -342,7 +349,7 @@ class LlamaDecodeEngine:
         (`_batch_split`) instead of the library GEMM.
         bf16_value_stream (fp32s engines): decoder matrices and an lm_head that are bf16 VALUES (a bf16 checkpoint upcast on
         load; verified per tensor) keep a bf16 copy, and the decode steps of <= 32 rows stream it on psg_split_gemm_wb16
-        (`_decode_step_wb16`) instead of the fp32 tensor."""
+        (`_decode_step_split` on the 'wb16' route) instead of the fp32 tensor."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
         if resident not in ("all", "quantised"):
@@ -403,10 +410,10 @@ class LlamaDecodeEngine:
                                   f"{dense[0]}): set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint, or use "
                                   "resident='all'")
 
-        def lean_matrix(keys):
-            """resident='quantised': the matrix of `keys` as a `QuantMatrix`.  A key's parts are read together, one key
-            after the other (the loader quantises a matrix when it is asked for and keeps none, head.load_llm_weights)."""
-            name = keys[0].rsplit(".", 2)[0] + "." + "|".join(k.split(".")[-2] for k in keys)
+        def quant_parts(keys):
+            """(q, s, e) of the FP8 / MXFP4 matrix of `keys`, row-concatenated and validated: the bytes, the fp32 row scales
+            and the block exponents (None for FP8).  A key's parts are read together, one key after the other (the loader
+            quantises a matrix when it is asked for and keeps none, head.load_llm_weights)."""
             qs, scs, es = [], [], []
             for k in keys:
                 qs.append(weights[k].to(self.device).view(torch.uint8))
@@ -414,12 +421,26 @@ class LlamaDecodeEngine:
                 es.append(weights[k + BEXP_SUFFIX].to(self.device) if k + BEXP_SUFFIX in weights else None)
             if any(e is None for e in es) and not all(e is None for e in es):
                 raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
-            q = (torch.cat(qs, 0) if len(qs) > 1 else qs[0]).contiguous()
-            sc = (torch.cat(scs, 0) if len(scs) > 1 else scs[0]).contiguous()
+            # (resident='quantised' keeps a single part as it came: no second copy of the largest matrix during the load)
+            cat = lambda ts: (torch.cat(ts, 0) if len(ts) > 1 or not lean else ts[0]).contiguous()   # noqa: E731
+            q, sc = cat(qs), cat(scs)
             del qs, scs
             if sc.numel() != q.shape[0]:
                 raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
             if es[0] is None:
+                return q, sc, None
+            e = cat(es)
+            N, K = q.shape[0], 2 * q.shape[1]
+            if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
+                raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
+                                  "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
+            return q, sc, e
+
+        def lean_matrix(keys):
+            """resident='quantised': the matrix of `keys` as a `QuantMatrix`."""
+            name = keys[0].rsplit(".", 2)[0] + "." + "|".join(k.split(".")[-2] for k in keys)
+            q, sc, e = quant_parts(keys)
+            if e is None:
                 N, K = q.shape
                 if N % 16 or K % 128:
                     raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the FP8 byte-stream kernels of the "
@@ -428,11 +449,7 @@ class LlamaDecodeEngine:
                 w = QuantMatrix(name, "fp8", (N, K), dtype, q, sc)
                 self._w8[w.data_ptr()] = (q, sc)
                 return w
-            e = (torch.cat(es, 0) if len(es) > 1 else es[0]).contiguous()
             N, K = q.shape[0], 2 * q.shape[1]
-            if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
-                raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
-                                  "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
             if N % 16 or K % 256:
                 raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the MXFP4 nibble-stream kernels of the "
                                   "decode steps (N % 16 == 0, K % 256 == 0), and there is no W' to fall back on: "
@@ -480,17 +497,9 @@ class LlamaDecodeEngine:
                         and (N, K) not in INT4_STREAM_OFF["pair" if dtype == torch.float32 else "single"]):
                     self._wi4[w.data_ptr()] = (ops.int4_q_image(q), ops.int4_group_image(gs, gz))
                 return w
-            q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
-            sc = torch.cat([weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1) for k in keys], 0)
-            if sc.numel() != q.shape[0]:
-                raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
-            if fmts == {"mxfp4"}:
-                e = torch.cat([weights[k + BEXP_SUFFIX].to(self.device) for k in keys], 0).contiguous()
+            q, sc, e = quant_parts(keys)
+            if e is not None:
                 N, K = q.shape[0], 2 * q.shape[1]
-                if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
-                    raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
-                                      "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
-                sc = sc.contiguous()
                 w = dequantize_mxfp4_rows(q, e, sc, dtype).contiguous()
                 self._w4[w.data_ptr()] = (q, ops.mxfp4_exp_image(e) if K % 256 == 0 else None, sc)
                 if prefill_split and dtype == torch.float32:
@@ -499,7 +508,7 @@ class LlamaDecodeEngine:
                     self._w8[w.data_ptr()] = mxfp4_as_fp8_rows(q, e, sc)
                 return w
             w = dequantize_fp8_rows(q, sc, dtype).contiguous()
-            self._w8[w.data_ptr()] = (q, sc.contiguous())
+            self._w8[w.data_ptr()] = (q, sc)
             if prefill_split and dtype == torch.float32:
                 self._w8h[w.data_ptr()] = q.view(torch.float8_e4m3fn).to(torch.float16)
             return w
@@ -525,7 +534,7 @@ class LlamaDecodeEngine:
                 wgu=matrix(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
                 wdown=matrix(p + "mlp.down_proj.weight"),
                 ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
-        layer_w = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
+        layer_w = self._layer_matrices()
         n_q4 = sum(t.data_ptr() in self._w4 for t in layer_w)
         n_qi = sum(t.data_ptr() in self._int4 for t in layer_w)
         if n_qi and (n_qi < len(layer_w) or self._w8 or self._w4):
@@ -564,9 +573,9 @@ class LlamaDecodeEngine:
         from . import _lib
         dev_i = self.device.index or 0
         if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
-            tensors = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
+            tensors = self._layer_matrices() + [self.lm_head]
             for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
-                if t.data_ptr() in self._w8 or t.data_ptr() in self._w4 or t.data_ptr() in self._int4:   # (has its byte stream: never counted, `_w16_all` stays false)
+                if self._quantised(t):                          # (has its byte stream: never counted, `_w16_all` stays false)
                     continue
                 h = t.half()
                 if torch.equal(h.float(), t):
@@ -581,9 +590,8 @@ class LlamaDecodeEngine:
         self.bf16_value_stream = bf16_value_stream
         self._wb16 = {}
         if bf16_value_stream and dtype == torch.float32:
-            for t in [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]:
-                if (not isinstance(t, torch.Tensor) or t.data_ptr() in self._w16 or t.data_ptr() in self._w8
-                        or t.data_ptr() in self._w4 or t.data_ptr() in self._int4):
+            for t in self._layer_matrices() + [self.lm_head]:
+                if not isinstance(t, torch.Tensor) or t.data_ptr() in self._w16 or self._quantised(t):
                     continue
                 b = t.bfloat16()
                 if torch.equal(b.float(), t):
@@ -592,7 +600,7 @@ class LlamaDecodeEngine:
             # [wh | wl | wh] fp16 + the per-row power of two that undoes the row scaling, per projection (3 x 2 bytes per
             # weight next to the fp32 copy the decode steps stream: 40 GB + 27 GB for Llama-2-7B, of 288 GB)
             for L in self.layers:
-                for k in ("wqkv", "wo", "wgu", "wdown"):
+                for k in _LAYER_MATRICES:
                     if L[k].data_ptr() not in self._w8 and L[k].data_ptr() not in self._w4:   # (quantised: the two-plane prompt pass on `_w8h` / `_w4h`, no split copy)
                         L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
         # batch_split_gemm: a generic fp32 lm_head has no split image (the prompt pass reads one row per pair of it, the decode
@@ -601,8 +609,7 @@ class LlamaDecodeEngine:
         # 32000 x 4096, counted under `other` in resident_bytes()
         lm = self.lm_head
         if (self.batch_split_gemm and isinstance(lm, torch.Tensor) and lm.dtype == torch.float32 and lm.data_ptr() not in self._w16
-                and lm.data_ptr() not in self._w8 and lm.data_ptr() not in self._w4 and lm.data_ptr() not in self._int4
-                and lm.shape[0] % 16 == 0 and lm.shape[1] % 64 == 0):
+                and not self._quantised(lm) and lm.shape[0] % 16 == 0 and lm.shape[1] % 64 == 0):
             img, inv = ops.split_f16x3(lm, weights=True)
             self.lm_head_s = (img[:, :2 * lm.shape[1]].contiguous(), inv)
             del img
@@ -639,12 +646,9 @@ class LlamaDecodeEngine:
         # decode steps of 33..160 rows: psg_batch_gemm where it beats the library (option decode_batch_gemm)
         self.batch_gemm = bool(_lib.get_option(dev_i, "decode_batch_gemm"))
         self._w_pools = {}
-        for L in self.layers:
-            for k in ("wqkv", "wo", "wgu", "wdown"):
-                if not isinstance(L[k], QuantMatrix):          # (pools time dense tensors in rotation, PSG_PLAN=measure)
-                    self._w_pools.setdefault(tuple(L[k].shape), []).append(L[k])
-        if not isinstance(self.lm_head, QuantMatrix):
-            self._w_pools.setdefault(tuple(self.lm_head.shape), []).append(self.lm_head)
+        for w in self._layer_matrices() + [self.lm_head]:
+            if not isinstance(w, QuantMatrix):                 # (pools time dense tensors in rotation, PSG_PLAN=measure)
+                self._w_pools.setdefault(tuple(w.shape), []).append(w)
         # resident='quantised': one scratch buffer per slot (`head.submit` runs two streams), as large as the largest
         # quantised matrix in the engine's dtype - the widest form `_dense` makes (the unscaled fp16 operand of the fp32s
         # prompt pass uses its head).  Allocated once, outside any graph: captured graphs replay against its address
@@ -680,8 +684,38 @@ class LlamaDecodeEngine:
 
     def _quant_matrices(self):
         """The `QuantMatrix` handles of an engine with resident='quantised' (none otherwise)."""
-        ws = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")] + [self.lm_head]
-        return [w for w in ws if isinstance(w, QuantMatrix)]
+        return [w for w in self._layer_matrices() + [self.lm_head] if isinstance(w, QuantMatrix)]
+
+    def _layer_matrices(self):
+        """Every decoder-layer projection matrix, layer after layer."""
+        return [L[k] for L in self.layers for k in _LAYER_MATRICES]
+
+    def _quantised(self, w):
+        """Has `w` a byte stream of its own (FP8, MXFP4) or is it an INT4 matrix?"""
+        p = w.data_ptr()
+        return p in self._w8 or p in self._w4 or p in self._int4
+
+    def _stream(self, w):
+        """The stream the matrix `w` has in a decode step of <= 32 rows, as (kind, the arguments of ops.split_gemm_<kind> /
+        ops.skinny_gemm_<kind> behind the rows), or None where it has none and runs on its dense tensor.  THE place that says
+        when a table entry is usable.  An FP8 image comes before the nibbles (that is what makes a W4_STREAM_AS_FP8 shape
+        stream as bytes); a quantised matrix has neither 16-bit copy, an fp16-valued one no bf16 copy."""
+        p, (N, K) = w.data_ptr(), w.shape
+        w8 = self._w8.get(p)
+        if w8 is not None and N % 16 == 0 and K % 128 == 0:
+            return "w8", w8
+        w4 = self._w4.get(p)
+        if w4 is not None and w4[1] is not None and N % 16 == 0:      # (K % 256 == 0 or there is no exponent image)
+            return "w4", w4
+        # (an INT4 image exists only for G = 128, K % 256 == 0, N % 16 == 0 and shapes outside INT4_STREAM_OFF)
+        wi4 = self._wi4.get(p)
+        if wi4 is not None:
+            return "int4", wi4
+        if p in self._w16:
+            return "w16", (self._w16[p],)
+        if p in self._wb16:
+            return "wb16", (self._wb16[p],)
+        return None
 
     def _scratch_for(self, slot):
         buf = self._scratch.get(slot)
@@ -814,39 +848,23 @@ class LlamaDecodeEngine:
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
         psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm) - or, with
         batch_quant_stream, over a quantised matrix's bytes (`_batch_quant`; batch_stream=False: the caller keeps W')."""
-        w8 = self._w8.get(w.data_ptr()) if self._w8 else None
-        if (w8 is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and w.shape[0] % 16 == 0
-                and w.shape[1] % 128 == 0 and (self.prefill_split or x.dtype != torch.float32)):
-            # FP8-quantised matrix, <= 32 rows: one byte per weight (psg_gemm_w8.hip).  The exact fp32 mode, other shapes
-            # and more rows run the paths below on W'
-            if x.dtype == torch.float32:
-                x2, inv = ops.split_f16x2(x)
-                return ops.split_gemm_w8(x2, inv, *w8)
-            return ops.skinny_gemm_w8(x, *w8)
-        w4 = self._w4.get(w.data_ptr()) if self._w4 else None
-        if (w4 is not None and w4[1] is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
-                and w.shape[0] % 16 == 0 and (self.prefill_split or x.dtype != torch.float32)):
-            # MXFP4-quantised matrix, <= 32 rows: 4.25 bits per weight (psg_gemm_w4.hip; K % 256 == 0 or there is no image)
-            if x.dtype == torch.float32:
-                x2, inv = ops.split_f16x2(x)
-                return ops.split_gemm_w4(x2, inv, *w4)
-            return ops.skinny_gemm_w4(x, *w4)
-        wi4 = self._wi4.get(w.data_ptr()) if self._wi4 else None
-        if (wi4 is not None and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
+        stream = self._stream(w)
+        kind = stream[0] if stream is not None else None
+        if (kind in _QUANT_STREAMS and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
                 and (self.prefill_split or x.dtype != torch.float32)):
-            # group-wise INT4 matrix, <= 32 rows: 4.25 bits per weight (psg_gemm_int4.hip; an image exists only for G = 128,
-            # K % 256 == 0, N % 16 == 0 and shapes outside INT4_STREAM_OFF)
+            # quantised matrix, <= 32 rows: one byte (FP8, psg_gemm_w8.hip) or 4.25 bits (MXFP4, psg_gemm_w4.hip; group-wise INT4,
+            # psg_gemm_int4.hip) per weight.  The exact fp32 mode, shapes `_stream` does not accept and more rows run the paths
+            # below on W'
             if x.dtype == torch.float32:
                 x2, inv = ops.split_f16x2(x)
-                return ops.split_gemm_int4(x2, inv, *wi4)
-            return ops.skinny_gemm_int4(x, *wi4)
+                return getattr(ops, "split_gemm_" + kind)(x2, inv, *stream[1])
+            return getattr(ops, "skinny_gemm_" + kind)(x, *stream[1])
         if (self.batch_quant_stream and batch_stream and decode and self.use_skinny and 32 < x.shape[0] <= 160 and x.dtype == w.dtype
-                and (w8 is not None or w4 is not None) and (self.prefill_split or x.dtype != torch.float32)):
-            out = self._batch_quant(x, w, w8, w4)
+                and kind in ("w8", "w4") and (self.prefill_split or x.dtype != torch.float32)):   # (no such kernel for INT4)
+            out = self._batch_quant(x, w)
             if out is not None:
                 return out
-        unquantised = (isinstance(w, torch.Tensor) and w8 is None and w4 is None and wi4 is None
-                       and w.data_ptr() not in self._int4)
+        unquantised = isinstance(w, torch.Tensor) and not self._quantised(w)
         w = self._dense(w)                                    # (resident='quantised': W' expanded into the slot's scratch)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
             wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
@@ -888,27 +906,22 @@ class LlamaDecodeEngine:
             return self.linear_split(x, ws, w)
         return F.linear(x, w)
 
-    def _batch_quant(self, x, w, w8, w4):
+    def _batch_quant(self, x, w):
         """Decode projection of 33..160 rows over a quantised matrix on its byte / nibble stream (psg_batch_gemm_q.hip,
         DESIGN 16): fp32 slices for the consumers of `ops.batch_gemm`, or None where the shape does not fit the kernels or
         the routing table sends it to the dense path.  fp32s rows go through `split_f16x2` and the pair form, 16-bit rows
-        take the single form.  A matrix with an FP8 image (FP8 itself, or a W4_STREAM_AS_FP8 shape) streams that, as below
-        33 rows."""
+        take the single form.  The stream is the one the matrix has below 33 rows (`_stream`: a matrix with an FP8 image -
+        FP8 itself, or a W4_STREAM_AS_FP8 shape - streams that)."""
         rows, (N, K) = int(x.shape[0]), w.shape
-        if w8 is not None and K % 128 == 0:
-            fmt, args = "fp8", w8
-        elif w4 is not None and w4[1] is not None:
-            fmt, args = "mxfp4", w4
-        else:
-            return None
+        kind, args = self._stream(w)
         pair = x.dtype == torch.float32
-        if N % 16 or (self.resident != "quantised"
-                      and _batch_quant_route(fmt, "pair" if pair else "single", N, K, rows) == "dense"):
+        if (self.resident != "quantised"
+                and _batch_quant_route(_QUANT_STREAMS[kind], "pair" if pair else "single", N, K, rows) == "dense"):
             return None
         if pair:
             x2, inv = ops.split_f16x2(x)
-            return (ops.batch_split_gemm_w8 if fmt == "fp8" else ops.batch_split_gemm_w4)(x2, inv, *args)
-        return (ops.batch_gemm_w8 if fmt == "fp8" else ops.batch_gemm_w4)(x, *args)
+            return getattr(ops, "batch_split_gemm_" + kind)(x2, inv, *args)
+        return getattr(ops, "batch_gemm_" + kind)(x, *args)
 
     def _batch_split(self, x, w, ws):
         """Decode projection of 33..160 fp32s rows over an unquantised matrix on psg_batch_gemm_s.hip: fp32
@@ -942,13 +955,15 @@ class LlamaDecodeEngine:
         rows = int(rows)
         if not self.use_skinny or rows > 32:
             return True
-        if self._can_w16(rows) or self._can_w8(rows) or self._can_w4(rows):   # psg_split_gemm_w16 / _w8 / _w4 for every projection
-            return False
-        if self._can_wb16(rows):                               # psg_split_gemm_wb16 for every decoder projection; the lm_head
+        # (the persistent layer and the fused step run the chain's own weight-streaming kernels: answered as the chain)
+        route = self._decode_route(rows, per_call=False)
+        if route == "wb16":                                    # psg_split_gemm_wb16 for every decoder projection; the lm_head
             head = self.lm_head                                # follows the stream its tensor has
             return not (head.data_ptr() in self._wb16 or head.data_ptr() in self._w16 or self._streams(rows, head, self.dtype))
+        if route is not None:                                  # psg_split_gemm_w16 / _w8 / _w4 / _int4 for every projection
+            return False
         L = self.layers[0] if self.layers else None
-        ws = ([L[k] for k in ("wqkv", "wo", "wgu", "wdown")] if L is not None else []) + [self.lm_head]
+        ws = ([L[k] for k in _LAYER_MATRICES] if L is not None else []) + [self.lm_head]
         return not all(self._streams(rows, w, self.dtype) for w in ws)
 
     def logits(self, h, batch_stream=True):
@@ -1144,40 +1159,35 @@ class LlamaDecodeEngine:
         ops.rmsnorm(x, delta, self.final_norm, m.rms_eps, n)
         return self.logits(n)
 
-    def _can_w16(self, rows):
-        """fp32s decode steps over fp16-valued weights: every projection as psg_split_gemm_w16, the row kernels writing
-        its two-plane operand directly (`_decode_step_w16`)."""
+    def _can_pair(self, rows, every_layer, k_multiple):
+        """fp32s decode steps of <= 32 rows with every projection on the two-plane entry of ONE stream (`every_layer`: every
+        decoder matrix has it), the row kernels writing that operand directly (`_decode_step_split`).  k_multiple: the K step
+        of the stream's kernel."""
         m = self.cfg.llm
-        return (self._w16_all and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
-                and self.dtype == torch.float32 and m.hidden % 64 == 0 and m.inter % 64 == 0 and m.inter <= 16384
+        return (every_layer and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
+                and self.dtype == torch.float32 and m.hidden % k_multiple == 0 and m.inter % k_multiple == 0 and m.inter <= 16384
                 and m.hidden <= 8192 and m.vocab % 16 == 0)
 
-    def _decode_step_w16(self, st):
-        """One decode step of the fp32s mode when the LLM's matrices are fp16 values (`self._w16`): 2 bytes per weight
-        from HBM, two fp16 products per projection (high and low part of the fp32 rows) on the 16-bit matrix cores."""
-        m = self.cfg.llm
-        x, wh = st["x"], self._w16
-        K, D = x.shape
-        att = torch.empty((K, D), device=self.device, dtype=torch.float32)
-        a2, inv = ops.rmsnorm_split2(x, None, self.layers[0]["ln1"], m.rms_eps)
-        for l, L in enumerate(self.layers):
-            qkv = ops.split_gemm_w16(a2, inv, wh[L["wqkv"].data_ptr()])
-            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
-                            st["vc"][l], att, kv_heads=self.kv)
-            # a row's maximum spans all heads / 11 008 columns: a split launch of its own behind attention and SwiGLU.  Folding
-            # it into the producers needs a rendezvous of the row's 32 / 11 workgroups - built and measured in round 6
-            # (profiles/r06_split2_rendezvous_ab.txt): inside a graph the launch costs 2.6 / 3.5 us, the rendezvous 9.3 / 3.4
-            a2o, invo = ops.split_f16x2(att)
-            o = ops.split_gemm_w16(a2o, invo, wh[L["wo"].data_ptr()])
-            a2, inv = ops.rmsnorm_split2(x, o, L["ln2"], m.rms_eps)
-            gu = ops.split_gemm_w16(a2, inv, wh[L["wgu"].data_ptr()])
-            act = torch.empty((K, m.inter), device=self.device, dtype=torch.float32)
-            ops.silu_mul(gu, act)
-            a2a, inva = ops.split_f16x2(act)
-            d = ops.split_gemm_w16(a2a, inva, wh[L["wdown"].data_ptr()])
-            nxt = self.layers[l + 1]["ln1"] if l + 1 < len(self.layers) else self.final_norm
-            a2, inv = ops.rmsnorm_split2(x, d, nxt, m.rms_eps)
-        return ops.split_gemm_w16(a2, inv, wh[self.lm_head.data_ptr()])
+    def _can_w16(self, rows):
+        """`_can_pair` over fp16-valued weights (`self._w16`): psg_split_gemm_w16, 2 bytes per weight from HBM, two fp16 products per
+        projection (high and low part of the fp32 rows) on the 16-bit matrix cores."""
+        return self._can_pair(rows, self._w16_all, 64)
+
+    def _can_w8(self, rows):
+        """`_can_pair` over FP8-quantised decoder layers: psg_split_gemm_w8, 1 byte per weight, the same two fp16 products on the exactly
+        widened bytes, the per-row weight scale applied in fp32 where a slice is stored."""
+        return self._can_pair(rows, self._w8_layers, 128)
+
+    def _can_w4(self, rows):
+        """`_can_pair` over MXFP4-quantised decoder layers: psg_split_gemm_w4 - or, for a shape of W4_STREAM_AS_FP8, psg_split_gemm_w8 on
+        its exact FP8 image - 4.25 bits per weight, nibbles and block scale widened exactly to fp16 in registers."""
+        return self._can_pair(rows, self._w4_layers, 256)
+
+    def _can_int4(self, rows):
+        """`_can_pair` over group-wise INT4 decoder layers, every one of which has its code stream (groups of 128, K % 256 == 0, none in
+        INT4_STREAM_OFF): psg_split_gemm_int4, 4.25 bits per weight, the codes widened to the exact integers q - z in fp16,
+        each group's sum scaled in fp32."""
+        return self._can_pair(rows, self._wi4_layers, 256)
 
     @property
     def bf16_stream_active(self):
@@ -1186,128 +1196,94 @@ class LlamaDecodeEngine:
 
     def _can_wb16(self, rows):
         """fp32s decode steps over bf16-valued decoder layers (option bf16_value_stream): every projection as
-        psg_split_gemm_wb16, the row kernels writing its three-plane operand directly (`_decode_step_wb16`)."""
+        psg_split_gemm_wb16 - 2 bytes per weight, three bf16 products (the exact three-plane form of the fp32 rows) - the row
+        kernels writing its three-plane operand directly (`_decode_step_split`)."""
         if not self._wb16:
             return False
         m = self.cfg.llm
-        ws = [L[k] for L in self.layers for k in ("wqkv", "wo", "wgu", "wdown")]
+        ws = self._layer_matrices()
         return (all(w.data_ptr() in self._wb16 for w in ws) and self.prefill_split and self.use_skinny and rows <= 32
                 and self.dtype == torch.float32 and m.hidden % 64 == 0 and m.inter % 64 == 0 and m.hidden <= 8192
                 and self.qkv_width % 16 == 0 and not any(tuple(w.shape) in WB16_STREAM_OFF for w in ws))
 
-    def _decode_step_wb16(self, st):
-        """One decode step of the fp32s mode when the decoder matrices are bf16 values (`self._wb16`): 2 bytes per weight from
-        HBM, three bf16 products per projection (the exact three-plane form of the fp32 rows) on the 16-bit matrix cores.
-        RMSNorm and SwiGLU write the planes themselves (element-wise: no row maximum), the attention output has a split
-        launch of its own.  The lm_head runs on the stream ITS tensor has: bf16 values, fp16 values or fp32."""
+    def _decode_route(self, rows, slot=0, per_call=True):
+        """THE route of a decode step of `rows` rows: a key of `_STREAM_PLANES` (`_decode_step_split`), 'persist'
+        (`_decode_step_persistent`), 'fused' (`_decode_step_fused`) or None - the launch chain of `_forward`.  The first
+        that is possible, in this order.  per_call=False leaves out the two routes that need state made per `_steps` call
+        (their counter blocks), which a call of no steps does not make."""
+        if self._can_wb16(rows):                               # option bf16_value_stream: the user asked for the stream
+            return "wb16"
+        if per_call and self._can_persist(rows, slot):
+            return "persist"
+        for kind, can in (("w16", self._can_w16), ("w8", self._can_w8), ("w4", self._can_w4), ("int4", self._can_int4)):
+            if can(rows):
+                return kind
+        return "fused" if per_call and self._can_fuse(rows) else None
+
+    def _operand_form(self, planes, rows):
+        """The row kernels that write the operand of the ops.split_gemm_* entries of `planes` planes directly:
+        (norm(x, delta, ln), split(att), swiglu(gate|up)).  Each returns the operand as the tuple of arguments the entry
+        takes before its weight.
+        Two planes: (fp16 planes, row scale).  A row's maximum spans all heads / all `inter` columns, so attention and SwiGLU
+        have a split launch of their own behind them; folding it into the producers needs a rendezvous of the row's 32 / 11
+        workgroups - built and measured in round 6 (profiles/r06_split2_rendezvous_ab.txt): inside a graph the launch costs
+        2.6 / 3.5 us, the rendezvous 9.3 / 3.4.
+        Three planes: (bf16 planes,).  Element-wise, no row maximum: RMSNorm and SwiGLU write the planes themselves."""
         m = self.cfg.llm
-        x, wb = st["x"], self._wb16
-        K, D = x.shape
-        att = torch.empty((K, D), device=self.device, dtype=torch.float32)
-        a3 = ops.rmsnorm_split_b16x3(x, None, self.layers[0]["ln1"], m.rms_eps)
-        for l, L in enumerate(self.layers):
-            qkv = ops.split_gemm_wb16(a3, wb[L["wqkv"].data_ptr()])
-            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
-                            st["vc"][l], att, kv_heads=self.kv)
-            o = ops.split_gemm_wb16(ops.split_b16x3(att), wb[L["wo"].data_ptr()])
-            a3 = ops.rmsnorm_split_b16x3(x, o, L["ln2"], m.rms_eps)
-            gu = ops.split_gemm_wb16(a3, wb[L["wgu"].data_ptr()])
-            d = ops.split_gemm_wb16(ops.silu_mul_split_b16x3(gu), wb[L["wdown"].data_ptr()])
-            if l + 1 < len(self.layers):
-                a3 = ops.rmsnorm_split_b16x3(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
-        head = self.lm_head.data_ptr()
-        if head in wb and m.vocab % 16 == 0:
-            return ops.split_gemm_wb16(ops.rmsnorm_split_b16x3(x, d, self.final_norm, m.rms_eps), wb[head])
-        if head in self._w16 and m.vocab % 16 == 0:
-            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
-            return ops.split_gemm_w16(a2, inv, self._w16[head])
-        n = torch.empty_like(x)
-        ops.rmsnorm(x, d, self.final_norm, m.rms_eps, n)
-        return self.logits(n)
+        if planes == 3:
+            return (lambda x, delta, ln: (ops.rmsnorm_split_b16x3(x, delta, ln, m.rms_eps),),
+                    lambda att: (ops.split_b16x3(att),),
+                    lambda gu: (ops.silu_mul_split_b16x3(gu),))
 
-    def _can_w8(self, rows):
-        """fp32s decode steps over FP8-quantised decoder layers: every projection as psg_split_gemm_w8, the row kernels
-        writing its two-plane operand directly (`_decode_step_w8`)."""
-        m = self.cfg.llm
-        return (self._w8_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
-                and self.dtype == torch.float32 and m.hidden % 128 == 0 and m.inter % 128 == 0 and m.inter <= 16384
-                and m.hidden <= 8192 and m.vocab % 16 == 0)
-
-    def _decode_step_w8(self, st):
-        """`_decode_step_w16` over FP8-quantised decoder layers: 1 byte per weight from HBM, the same two fp16 products per
-        projection on the exactly widened bytes, the per-row weight scale applied in fp32 where a slice is stored.  The
-        lm_head runs on the stream ITS tensor has: bytes, fp16 values or fp32."""
-        return self._decode_step_wq(st)
-
-    def _can_w4(self, rows):
-        """fp32s decode steps over MXFP4-quantised decoder layers: every projection as psg_split_gemm_w4 - or, for a shape
-        of W4_STREAM_AS_FP8, as psg_split_gemm_w8 on its exact FP8 image - the row kernels writing the two-plane operand
-        directly (`_decode_step_w4`)."""
-        m = self.cfg.llm
-        return (self._w4_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
-                and self.dtype == torch.float32 and m.hidden % 256 == 0 and m.inter % 256 == 0 and m.inter <= 16384
-                and m.hidden <= 8192 and m.vocab % 16 == 0)
-
-    def _decode_step_w4(self, st):
-        """`_decode_step_w8` over MXFP4-quantised decoder layers: 4.25 bits per weight from HBM, nibbles and block scale
-        widened exactly to fp16 in registers, the same two fp16 products per projection."""
-        return self._decode_step_wq(st)
-
-    def _can_int4(self, rows):
-        """fp32s decode steps over group-wise INT4 decoder layers, every one of which has its code stream (groups of 128, K %
-        256 == 0, none in INT4_STREAM_OFF): every projection as psg_split_gemm_int4, the row kernels writing the two-plane
-        operand directly (`_decode_step_int4`)."""
-        m = self.cfg.llm
-        return (self._wi4_layers and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
-                and self.dtype == torch.float32 and m.hidden % 256 == 0 and m.inter % 256 == 0 and m.inter <= 16384
-                and m.hidden <= 8192 and m.vocab % 16 == 0)
-
-    def _decode_step_int4(self, st):
-        """`_decode_step_w4` over group-wise INT4 decoder layers: 4.25 bits per weight from HBM, the codes widened to the
-        exact integers q - z in fp16, the same two fp16 products per projection, each group's sum scaled in fp32."""
-        return self._decode_step_wq(st)
-
-    def _split_mm_q(self, a2, inv, w):
-        """The pair-form projection of a quantised matrix on the stream it has: FP8 bytes (an FP8 matrix, or the exact FP8
-        image of an MXFP4 shape that streams faster so), MXFP4 nibbles or INT4 codes."""
-        w8 = self._w8.get(w.data_ptr())
-        if w8 is not None:
-            return ops.split_gemm_w8(a2, inv, *w8)
-        wi4 = self._wi4.get(w.data_ptr())
-        if wi4 is not None:
-            return ops.split_gemm_int4(a2, inv, *wi4)
-        return ops.split_gemm_w4(a2, inv, *self._w4[w.data_ptr()])
-
-    def _decode_step_wq(self, st):
-        m = self.cfg.llm
-        x, mm = st["x"], self._split_mm_q
-        K, D = x.shape
-        att = torch.empty((K, D), device=self.device, dtype=torch.float32)
-        a2, inv = ops.rmsnorm_split2(x, None, self.layers[0]["ln1"], m.rms_eps)
-        for l, L in enumerate(self.layers):
-            qkv = mm(a2, inv, L["wqkv"])
-            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
-                            st["vc"][l], att, kv_heads=self.kv)
-            a2o, invo = ops.split_f16x2(att)
-            o = mm(a2o, invo, L["wo"])
-            a2, inv = ops.rmsnorm_split2(x, o, L["ln2"], m.rms_eps)
-            gu = mm(a2, inv, L["wgu"])
-            act = torch.empty((K, m.inter), device=self.device, dtype=torch.float32)
+        def swiglu(gu):
+            act = torch.empty((rows, m.inter), device=self.device, dtype=torch.float32)
             ops.silu_mul(gu, act)
-            a2a, inva = ops.split_f16x2(act)
-            d = mm(a2a, inva, L["wdown"])
+            return ops.split_f16x2(act)
+        return (lambda x, delta, ln: ops.rmsnorm_split2(x, delta, ln, m.rms_eps)), ops.split_f16x2, swiglu
+
+    def _split_gemm(self, planes, operand, w):
+        """The projection of a split operand of `planes` planes over `w` on the stream it has: ops.split_gemm_<kind>, looked
+        up when it is called."""
+        stream = self._stream(w)
+        if stream is None or _STREAM_PLANES[stream[0]] != planes:
+            raise PsgHipError(f"decode step: the matrix {tuple(w.shape)} has no stream that reads a {planes}-plane operand")
+        return getattr(ops, "split_gemm_" + stream[0])(*operand, *stream[1])
+
+    def _decode_step_split(self, st, kind):
+        """One fp32s decode step of <= 32 rows on the route `kind` (a key of `_STREAM_PLANES`): every decoder projection as
+        ops.split_gemm_<the stream its matrix has>, the row kernels writing that entry's split operand directly."""
+        m = self.cfg.llm
+        x = st["x"]
+        rows, D = x.shape
+        planes = _STREAM_PLANES[kind]
+        norm, split, swiglu = self._operand_form(planes, rows)
+        att = torch.empty((rows, D), device=self.device, dtype=torch.float32)
+        a = norm(x, None, self.layers[0]["ln1"])
+        for l, L in enumerate(self.layers):
+            qkv = self._split_gemm(planes, a, L["wqkv"])
+            ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
+                            st["vc"][l], att, kv_heads=self.kv)
+            o = self._split_gemm(planes, split(att), L["wo"])
+            gu = self._split_gemm(planes, norm(x, o, L["ln2"]), L["wgu"])
+            d = self._split_gemm(planes, swiglu(gu), L["wdown"])
             if l + 1 < len(self.layers):
-                a2, inv = ops.rmsnorm_split2(x, d, self.layers[l + 1]["ln1"], m.rms_eps)
-        head = self.lm_head.data_ptr()
-        if ((head in self._w8 and self.lm_head.shape[1] % 128 == 0)
-                or (head in self._w4 and self._w4[head][1] is not None) or head in self._wi4):
-            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
-            return mm(a2, inv, self.lm_head)
-        if head in self._w16:
-            a2, inv = ops.rmsnorm_split2(x, d, self.final_norm, m.rms_eps)
-            return ops.split_gemm_w16(a2, inv, self._w16[head])
+                a = norm(x, d, self.layers[l + 1]["ln1"])
+        return self._lm_head_tail(x, d, planes)
+
+    def _lm_head_tail(self, x, delta, planes):
+        """The final norm and the lm_head behind the last layer of `_decode_step_split`.  The lm_head runs on the stream ITS
+        tensor has, the norm writing that stream's operand - where the stream takes the operand form of the step's route
+        (`planes`), or is the fp16 copy.  Every other head runs as in the launch chain (fp32 rows, `logits`): one without a
+        stream on its fp32 tensor, a quantised lm_head under bf16-valued layers on its own stream behind a split launch, and
+        the bf16 copy of an lm_head under quantised layers is not streamed."""
+        m = self.cfg.llm
+        stream = self._stream(self.lm_head)
+        if stream is not None and m.vocab % 16 == 0 and (_STREAM_PLANES[stream[0]] == planes or stream[0] == "w16"):
+            planes = _STREAM_PLANES[stream[0]]
+            norm = self._operand_form(planes, x.shape[0])[0]
+            return self._split_gemm(planes, norm(x, delta, self.final_norm), self.lm_head)
         n = torch.empty_like(x)
-        ops.rmsnorm(x, d, self.final_norm, m.rms_eps, n)
+        ops.rmsnorm(x, delta, self.final_norm, m.rms_eps, n)
         return self.logits(n)
 
     def _can_fuse(self, rows):
@@ -1654,36 +1630,22 @@ class LlamaDecodeEngine:
         """Decode steps lo .. hi-1 (step s writes tokens[:, s])."""
         m = self.cfg.llm
         self._slot = int(st.get("slot", 0))
-        wb16 = self._can_wb16(st["x"].shape[0])               # option bf16_value_stream: the user asked for the stream
-        persist = not wb16 and hi > lo and self._can_persist(st["x"].shape[0], st.get("slot", 0))
-        w16 = not wb16 and not persist and self._can_w16(st["x"].shape[0])
-        w8 = not persist and not w16 and self._can_w8(st["x"].shape[0])
-        w4 = not persist and not w16 and not w8 and self._can_w4(st["x"].shape[0])
-        i4 = not persist and not w16 and not w8 and not w4 and self._can_int4(st["x"].shape[0])
-        fused = not persist and not w16 and not w8 and not w4 and not i4 and self._can_fuse(st["x"].shape[0]) and hi > lo
-        if persist:                                            # one counter block per layer launch, zeroed once per call
+        route = self._decode_route(st["x"].shape[0], st.get("slot", 0), hi > lo)
+        if route == "persist":                                 # one counter block per layer launch, zeroed once per call
             per_step = ops.decode_layer_counters(self.device) * len(self.layers)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
             # kept in the decode state: a hand-off poll that gave up reports through the block's time-out word, which
             # `generate` reads back with the tokens (`_check_persistent`) - a dead producer must not yield silent garbage
             st.setdefault("dl_counters", []).append(sync)
-        if fused:                                              # two counter words per fused launch, zeroed once per call
+        if route == "fused":                                   # two counter words per fused launch, zeroed once per call
             per_step = 2 * (4 * len(self.layers) + 1)
             sync = torch.zeros((hi - lo) * per_step, device=self.device, dtype=torch.int32)
         for step in range(lo, hi):
-            if wb16:
-                logits = self._decode_step_wb16(st)
-            elif persist:
+            if route in _STREAM_PLANES:
+                logits = self._decode_step_split(st, route)
+            elif route == "persist":
                 logits = self._decode_step_persistent(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
-            elif w16:
-                logits = self._decode_step_w16(st)
-            elif w8:
-                logits = self._decode_step_w8(st)
-            elif w4:
-                logits = self._decode_step_w4(st)
-            elif i4:
-                logits = self._decode_step_int4(st)
-            elif fused:
+            elif route == "fused":
                 logits = self._decode_step_fused(st, sync[(step - lo) * per_step:(step - lo + 1) * per_step])
             else:
                 h = self._forward(st["x"], st["dec_pair"], st["dec_pos"], st["kc"], st["vc"], st["ctx_len"], decode=True)

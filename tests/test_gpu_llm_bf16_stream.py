@@ -118,10 +118,10 @@ def _names(log):
 
 
 def _step_logits(eng, dec, sup):
-    """One decode step from ONE post-prefill state on both routes: (`_decode_step_wb16`, the option-off chain) fp32 logits."""
+    """One decode step from ONE post-prefill state on both routes: (`_decode_step_split` on 'wb16', the option-off chain) fp32 logits."""
     st = eng._prefill(dec["llm_inputs"], dec["prompt_len"], eng.cfg.max_new_tokens, sup, False)
     x0 = st["x"].clone()                                                     # (a step adds its deltas to the residual rows)
-    a = eng._decode_step_wb16(st).reduce(torch.float32)
+    a = eng._decode_step_split(st, "wb16").reduce(torch.float32)
     st["x"].copy_(x0)
     h = eng._forward(st["x"], st["dec_pair"], st["dec_pos"], st["kc"], st["vc"], st["ctx_len"], decode=True)
     b = eng.logits(h)

@@ -146,7 +146,7 @@ def test_a_constrained_decode_on_the_quantised_stream(case, dtype, fmt, lm_head,
         assert not eng._can_wb16(20) and not eng._can_persist(20, 0) and not eng._can_w16(20) and not eng._can_fuse(20)
     else:
         assert not any(f(20) for f in (eng._can_w8, eng._can_w4, eng._can_int4, eng._can_wb16, eng._can_w16, eng._can_fuse))
-    if pair and fmt != "int4g":                                        # (`decode_uses_library` does not name the INT4 route)
+    if pair:
         assert not eng.decode_uses_library(20)
     _reset(calls, steps)
     r_con = con(inp)
