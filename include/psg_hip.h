@@ -82,8 +82,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *        added
  *   611  decode over the relation-name trie only: psg_trie_greedy_step added
  *   612  bf16-valued LLM weights streamed as bf16 in the fp32s decode steps: psg_split_b16x3, psg_rmsnorm_split_b16x3,
- *        psg_silu_mul_split_b16x3, psg_split_gemm_wb16(_plan) added */
-#define PSG_ABI_VERSION 612
+ *        psg_silu_mul_split_b16x3, psg_split_gemm_wb16(_plan) added
+ *   613  the prompt pass's library products with a pinned algorithm: psg_lt_gemm_init, psg_lt_gemm_candidates, psg_lt_gemm
+ *        added */
+#define PSG_ABI_VERSION 613
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -815,6 +817,29 @@ int psg_train_bf16_attn_bwd(psg_ctx*, const void* q, const void* k, const void* 
  * outputs of the two Linear layers in their natural [B][N][R*C] layout.  Exact fp32 (f32 matrix cores). */
 int psg_bilinear_scores(psg_ctx*, const float* sub, const float* obj, int B, int N, int R, int C, float* pred,
                         void* stream);
+
+/* ---- the library product (hipBLASLt) with a pinned algorithm (csrc/psg_lt_gemm.hip):
+ *   y[b][rows][N] fp32 = a[b][rows][K] fp16 . w[b][N][K]^T fp16, fp32 accumulation, row-major with leading dimensions
+ *   lda / ldw (>= K) and ldy (>= N, so a column part can land inside a wider y); `batch` products `stride_*` ELEMENTS apart
+ *   (batch 1: strides ignored).  No kernel of this library runs: the product is the GEMM library's, called through the C
+ *   entry points of the copy the process has ALREADY loaded (PyTorch's) - never a second copy.
+ * psg_lt_gemm_init: resolves those entry points and creates the ONE library handle of the context (idempotent); writes the
+ *   library's version number.  PSG_ERR_UNSUPPORTED when no copy is loaded or a symbol is missing: stay on torch.mm.  Not
+ *   capturable; every other entry needs it to have succeeded.
+ * psg_lt_gemm_candidates: the heuristic's candidates (up to 64, the library's order, first = its first choice) for the
+ *   problem within max_ws_bytes of workspace: their solution indices and required workspace bytes; *count of them written
+ *   (<= max_count).
+ * psg_lt_gemm: algo -1 = the first choice; otherwise the candidate whose solution index equals algo - if none of the
+ *   candidates that fit workspace_bytes matches, the first choice runs and *fell_back (may be NULL) is 1, else 0.  The
+ *   workspace is the caller's device buffer (16-byte aligned; may be NULL with 0 bytes).  Runs on `stream`, capturable: no
+ *   allocation on the device, no host wait, no handle creation; the descriptors of a problem are built once and cached. */
+int psg_lt_gemm_init(psg_ctx*, int* lib_version);
+int psg_lt_gemm_candidates(psg_ctx*, int rows, int N, int K, int64_t lda, int64_t ldw, int64_t ldy, int batch,
+                           int64_t stride_a, int64_t stride_w, int64_t stride_y, int64_t max_ws_bytes, int max_count,
+                           int* indices, int64_t* ws_bytes, int* count);
+int psg_lt_gemm(psg_ctx*, const void* a, const void* w, float* y, int rows, int N, int K, int64_t lda, int64_t ldw,
+                int64_t ldy, int batch, int64_t stride_a, int64_t stride_w, int64_t stride_y, int algo, void* workspace,
+                int64_t workspace_bytes, int* fell_back, void* stream);
 
 #ifdef __cplusplus
 }

@@ -73,7 +73,10 @@ struct psg_ctx {
   int64_t trace_words = 0;
   int trace_kind = 0;           // PSG_TRACE_*
   size_t skinny_lds_configured = 0;
+  void* lt = nullptr;           // psg_lt_gemm.hip: the library handle of this context and its resolved plans (psg_lt_gemm_init)
 };
+
+void psg_lt_release(psg_ctx* ctx);   // psg_lt_gemm.hip: frees ctx->lt (psg_destroy)
 
 void psg_set_error(const char* fmt, ...);
 

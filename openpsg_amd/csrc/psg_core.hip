@@ -117,6 +117,7 @@ extern "C" int psg_create(int device, psg_ctx** out) {
 }
 
 extern "C" int psg_destroy(psg_ctx* ctx) {
+  if (ctx) psg_lt_release(ctx);
   delete ctx;
   return PSG_OK;
 }

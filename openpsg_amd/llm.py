@@ -64,6 +64,8 @@ def _split_mm(a3, w3, plan=None, out_dtype=torch.float32):
     kw = {} if out_dtype is None else {"out_dtype": out_dtype}
     if plan is None or plan[0] == "whole":
         return torch.mm(a3, w3.t(), **kw)
+    if plan[0] == "lt":                                        # the library called natively, algorithm pinned (`_LtRoute`)
+        return plan[3].mm(a3, w3, plan)
     if plan[0] == "kseg":                                      # P segments of K' as ONE batched product: [P, rows, N] slices
         rows, N, P = a3.shape[0], w3.shape[0], plan[1]
         K = a3.shape[1] // P
@@ -80,6 +82,93 @@ def _split_mm(a3, w3, plan=None, out_dtype=torch.float32):
         for r0 in range(0, rows, h):
             torch.mm(a3[r0:r0 + h], w3.t(), out=y[r0:r0 + h], **kw)
     return y
+
+
+# WHICH library kernel runs a split-fp16 product of the prompt pass.  torch.mm / torch.bmm take the library's first
+# heuristic choice for a shape, and the table above steers that heuristic by re-cutting the product; psg_lt_gemm calls the
+# library natively with the algorithm PINNED by its solution index instead (ops.lt_gemm).  A line is a measured
+# winner of tools/lt_gemm_tune.py: it enters only when the candidate's range of times lies wholly below the range of what
+# the shape runs today (the acceptance rule of DESIGN 14 / 17) and its result was bit-identical over 10 repeats.  A solution
+# index means something only within one library version: a line whose version is not the running library's is ignored (the
+# shape keeps its `_SPLIT_PLAN_TABLE` route) and `lt_gemm_pinned` says so.  Like the table above, a pure function of the
+# shape: no process measures anything.
+#   key: (N, K', planes of the operand, the reader sums [P, rows, N] slices)
+#        ->  [(rows from, rows below, solution index, library version, layout, workspace bytes), ...]  (a line holds for
+#        the row count it was tuned at: which solutions the library lists, and how they rank, changes with the rows)
+#   layout: ("whole",) one [rows, N] result (a split-K algorithm sums through the workspace); ("cols", P) P column parts
+#   written in place (ldy = N); ("kseg", P) P segments of K' as one batched product, [P, rows, N] slices for the reader
+# profiles/lt_gemm_tune.txt (library version 100000; eight shapes, up to 64 candidates per layout, two runs - a line is kept
+# only when BOTH accepted it): q|k|v and down keep their `_SPLIT_PLAN_TABLE` route (the first choice is the fastest whole
+# q|k|v, nothing beats down's six segments), and so does every two-plane shape (fp16-valued weights, 1920 rows)
+_LT_ALGO_TABLE: dict = {
+    # fp32s prompt pass, generic fp32 weights, 960 rows at BASELINE C3 (us: range of the candidate against the incumbent's)
+    (22016, 12288, 3, False): [(960, 961, 625805, 100000, ("cols", 2), 0)],      # gate|up: 435-470 against 474-514 (two halves)
+    (4096, 12288, 3, True): [(960, 961, 625813, 100000, ("kseg", 2), 0)],        # o: 96-105 against 105-113 (whole)
+}
+
+
+class _LtRoute:
+    """The lines of `_LT_ALGO_TABLE` that hold for the library this process runs, and the one workspace their algorithms
+    share (allocated here, once, outside any graph: captured launches replay against its address)."""
+
+    def __init__(self, device, table=None):
+        self.device = torch.device(device)
+        self.lines, self.stale, self.fell_back = {}, [], []
+        table = _LT_ALGO_TABLE if table is None else table
+        self.version = ops.lt_gemm_version(self.device) if table and self.device.type == "cuda" else None
+        self.error = None if self.version is not None or not table else (ops.lt_gemm_error(self.device) or "no GPU")
+        ws = 0
+        for key, rules in table.items():
+            for lo, hi, index, version, layout, ws_bytes in rules:
+                if self.version is None:
+                    continue
+                if version != self.version:
+                    self.stale.append((key, version))
+                    continue
+                self.lines.setdefault(key, []).append((lo, hi, int(index), tuple(layout)))
+                ws = max(ws, int(ws_bytes))
+        self.workspace = torch.empty(ws, device=self.device, dtype=torch.uint8) if ws else None
+
+    def plan(self, rows, N, K, planes, k3):
+        """("lt", solution index, layout, self) - a plan of `_split_mm` - for a shape the table pins, else None."""
+        for lo, hi, index, layout in self.lines.get((int(N), int(K), int(planes), bool(k3)), ()):
+            if lo <= rows < hi:
+                return ("lt", index, layout, self)
+        return None
+
+    def mm(self, a3, w3, plan):
+        """a3 [rows, K'] . w3 [N, K']^T -> fp32 [rows, N] (or [P, rows, N] slices) on the pinned algorithm."""
+        _, index, layout, _ = plan
+        rows, N = a3.shape[0], w3.shape[0]
+        if layout[0] == "kseg":
+            P = layout[1]
+            K = a3.shape[1] // P
+            y = torch.empty((P, rows, N), device=a3.device, dtype=torch.float32)
+            fb = ops.lt_gemm(a3.view(rows, P, K).permute(1, 0, 2), w3.view(N, P, K).permute(1, 0, 2), y, index, self.workspace)
+        else:
+            y = torch.empty((rows, N), device=a3.device, dtype=torch.float32)
+            parts = layout[1] if layout[0] == "cols" else 1
+            h = N // parts
+            fb = False
+            for p_ in range(parts):
+                fb |= ops.lt_gemm(a3, w3[p_ * h:(p_ + 1) * h], y[:, p_ * h:(p_ + 1) * h], index, self.workspace)
+        if fb and (N, a3.shape[1], index) not in self.fell_back:
+            self.fell_back.append((N, a3.shape[1], index))
+        return y
+
+    @property
+    def pinned(self):
+        """(table lines in force, why the others are not - '' when every line is)."""
+        why = []
+        if self.error:
+            why.append(f"library not usable: {self.error}")
+        if self.stale:
+            why.append(f"{len(self.stale)} line(s) tuned for another library version than {self.version}: "
+                       + ", ".join(f"{k} @ {v}" for k, v in self.stale))
+        if self.fell_back:
+            why.append("solution not among the library's candidates, its first choice ran: "
+                       + ", ".join(f"(N={n}, K'={k}) #{i}" for n, k, i in self.fell_back))
+        return sum(len(v) for v in self.lines.values()), "; ".join(why)
 
 
 # MXFP4 shapes (N, K) that stream as their exact FP8 image instead of as nibbles (DESIGN 14, acceptance rule): a shape goes
@@ -643,6 +732,8 @@ class LlamaDecodeEngine:
         self.fuse_split = bool(_lib.get_option(dev_i, "llm_fuse_split"))
         # fp32s prompt pass: run each library product whole or in the column / row parts measured fastest (_plan_split_mm)
         self.plan_split = True
+        # ... and on the library algorithm `_LT_ALGO_TABLE` pins for the shape (psg_lt_gemm), where a line of it holds
+        self._lt = _LtRoute(self.device)
         # decode steps of 33..160 rows: psg_batch_gemm where it beats the library (option decode_batch_gemm)
         self.batch_gemm = bool(_lib.get_option(dev_i, "decode_batch_gemm"))
         self._w_pools = {}
@@ -1073,8 +1164,13 @@ class LlamaDecodeEngine:
         left is the row's."""
         m = self.cfg.llm
         rows, D = resid.shape
-        plan = _plan_split_mm if self.plan_split else (lambda r, w, k3=False: None)
         planes = 2 if self._w16_all or self._w8_layers or self._w4_layers else 3
+
+        def plan(r, w, k3=False):                              # a pinned library algorithm, else the shape's table form
+            if not self.plan_split:
+                return None
+            lt = None if _plan_measuring() else self._lt.plan(r, w.shape[0], w.shape[1], planes, k3)
+            return lt or _plan_split_mm(r, w, k3=k3)
         if planes == 3:
             weight = lambda L, k: L[k + "_s"]                                               # noqa: E731
             mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
@@ -1124,6 +1220,12 @@ class LlamaDecodeEngine:
             else:
                 a, inv_r = ops.rmsnorm_split(resid, d, self.layers[l + 1]["ln1"], m.rms_eps, planes=planes)
         return n
+
+    @property
+    def lt_gemm_pinned(self):
+        """(lines of `_LT_ALGO_TABLE` in force for this engine, the reason the others are not): a table tuned for another
+        library version, or a solution the library no longer offers, is visible here instead of silently falling back."""
+        return self._lt.pinned
 
     def _can_persist(self, rows, slot):
         m = self.cfg.llm

@@ -1532,3 +1532,79 @@ def silu_mul_split(gate_up, inter, planes=3):
     check(lib.psg_silu_mul_split(ctx, _p(gate_up.y), _p(gate_up.row_scale, torch.float32), _p(gate_up.col_scale, torch.float32),
                                  nsl, rows, inter, _p(out), _p(inv), int(planes), st), "psg_silu_mul_split")
     return out, inv
+
+
+# ---- the library product with a pinned algorithm (psg_lt_gemm) -------------------------------------------------
+_LT_VERSION: dict = {}                                             # device index -> library version (int) or the error text
+
+
+def lt_gemm_version(device):
+    """The version number of the GEMM library copy this process runs (psg_lt_gemm_init: resolves its entry points and
+    creates the context's handle on first use), or None when it cannot be used - `lt_gemm_error` then says why."""
+    import ctypes
+    dev_i = torch.device(device).index or 0
+    if dev_i not in _LT_VERSION:
+        try:
+            v = ctypes.c_int(0)
+            check(_lib.load().psg_lt_gemm_init(_lib.ctx(dev_i), ctypes.byref(v)), "psg_lt_gemm_init")
+            _LT_VERSION[dev_i] = int(v.value)
+        except PsgHipError as e:
+            _LT_VERSION[dev_i] = str(e)
+    v = _LT_VERSION[dev_i]
+    return v if isinstance(v, int) else None
+
+
+def lt_gemm_error(device):
+    v = _LT_VERSION.get(torch.device(device).index or 0)
+    return v if isinstance(v, str) else None
+
+
+def _lt_operand(t, inner, name):
+    """(batch, batch stride, leading dimension) of a [rows, inner] or [batch, rows, inner] view with unit inner stride."""
+    assert t.dim() in (2, 3) and t.shape[-1] == inner and (t.stride(-1) == 1 or inner == 1), f"{name}: {t.shape} {t.stride()}"
+    return (1, 0, t.stride(0)) if t.dim() == 2 else (t.shape[0], t.stride(0), t.stride(1))
+
+
+def _lt_problem(a, w, y):
+    rows, K = a.shape[-2:]
+    N = w.shape[-2]
+    assert w.shape[-1] == K and a.dtype == w.dtype == torch.float16, (a.shape, w.shape, a.dtype, w.dtype)
+    (ba, sa, lda), (bw, sw, ldw) = _lt_operand(a, K, "a"), _lt_operand(w, K, "w")
+    assert ba == bw
+    if y is None:
+        by, sy, ldy = ba, rows * N, N
+    else:
+        assert y.dtype == torch.float32 and y.shape[-2] == rows
+        by, sy, ldy = _lt_operand(y, N, "y")
+        assert by == ba
+    return (int(rows), int(N), int(K), int(lda), int(ldw), int(ldy), int(ba), int(sa), int(sw), int(sy))
+
+
+def lt_gemm_candidates(a, w, y=None, max_ws_bytes=0):
+    """[(solution index, workspace bytes), ...] the library's heuristic lists for y = a . w^T (the operands' shapes and
+    strides only; the first entry is its first choice) within max_ws_bytes of workspace."""
+    import ctypes
+    lib, ctx, _ = _env(a)
+    if lt_gemm_version(a.device) is None:
+        raise PsgHipError(lt_gemm_error(a.device))
+    idx, ws, n = (ctypes.c_int * 64)(), (ctypes.c_int64 * 64)(), ctypes.c_int(0)
+    check(lib.psg_lt_gemm_candidates(ctx, *_lt_problem(a, w, y), int(max_ws_bytes), 64, idx, ws, ctypes.byref(n)),
+          "psg_lt_gemm_candidates")
+    return [(int(idx[i]), int(ws[i])) for i in range(n.value)]
+
+
+def lt_gemm(a, w, y, algo=-1, workspace=None):
+    """y (fp32 [rows, N] or [batch, rows, N], any leading dimension >= N) = a (fp16 [.., rows, K]) . w (fp16 [.., N, K])^T on
+    the library's algorithm with solution index `algo` (-1: its first choice).  Views are taken as they are (unit inner
+    stride), so a column part of a wider y or the K segments of one operand as a batch need no copy.  workspace: a uint8
+    device buffer, or None.  Returns True when `algo` was not among the candidates and the first choice ran instead."""
+    import ctypes
+    lib, ctx, st = _env(a)
+    if lt_gemm_version(a.device) is None:
+        raise PsgHipError(lt_gemm_error(a.device))
+    assert w.is_cuda and y.is_cuda
+    fb = ctypes.c_int(0)
+    wsp, wsb = (None, 0) if workspace is None else (workspace.data_ptr(), workspace.numel() * workspace.element_size())
+    check(lib.psg_lt_gemm(ctx, a.data_ptr(), w.data_ptr(), y.data_ptr(), *_lt_problem(a, w, y), int(algo), wsp, wsb,
+                          ctypes.byref(fb), st), "psg_lt_gemm")
+    return bool(fb.value)
