@@ -84,8 +84,9 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *   612  bf16-valued LLM weights streamed as bf16 in the fp32s decode steps: psg_split_b16x3, psg_rmsnorm_split_b16x3,
  *        psg_silu_mul_split_b16x3, psg_split_gemm_wb16(_plan) added
  *   613  the prompt pass's library products with a pinned algorithm: psg_lt_gemm_init, psg_lt_gemm_candidates, psg_lt_gemm
- *        added */
-#define PSG_ABI_VERSION 613
+ *        added
+ *   614  beam decode over the relation-name trie: psg_trie_beam_step added */
+#define PSG_ABI_VERSION 614
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -703,6 +704,27 @@ int psg_trie_greedy_step(psg_ctx*, const void* logits, int splits, int K, int vo
                          int n_edges, int32_t* node, float* logp, int32_t* tokens, int32_t* done, int32_t* next_ids,
                          int32_t* tok_pos, const void* embed, int embed_dtype, int hidden, void* x_out, int x_dtype,
                          int dtype, void* stream);
+/* psg_trie_beam_step: one level of a beam of width B over the same trie.  One 256-thread workgroup per pair.
+ * Logits [K * beams_in][vocab] of `dtype`, or fp32 partials [splits][K * beams_in][vocab] summed in slice order;
+ * beams_in = 1 (level 0: the pair's root row, state entry k * B) or B.  The per-row state node int32 [K * B] (CSR node, -1
+ * = dead) / logp fp32 [K * B] and the finished lists fin_class int32 [K][B] (-1 padded) / fin_logp fp32 [K][B] are read
+ * and written.  For every live input beam b and every edge c of its node: t = logit_b[child_tok[c]] - lse_b (lse over the
+ * WHOLE vocabulary: the value psg_token_logprobs writes for that row and child), v = logp_b + t.  Dropped: v NaN, token
+ * outside the vocabulary, t = -inf.  edge_node[c] >= 0: live pool; else finish pool with class edge_class[c] (>= 0).
+ * New live list = first B of the live pool by v descending, ties to the lower beam, then the lower edge; new finished list
+ * = first B of (old finished list + finish pool) by v descending, ties to the lower class.  Comparisons are on fp32 v.
+ * For row k * B + b: node = edge_node + 1, logp = v, row_node = the internal index, tok_pos = trie_base + row_node,
+ * rope_pos = seq_len[k] + node_depth - 1, x_out = embed[node_tok]; a dead row (fewer than B live candidates): node = -1,
+ * logp = -inf, row_node = tok_pos = -1, rope_pos = 0, x_out = embed[eos].  max_children bounds the children of a node
+ * (more are not read); B * max_children <= PSG_BEAM_MAX_CAND.  Ranked by counting: no atomics, bit-reproducible. */
+#define PSG_BEAM_MAX_WIDTH 8
+#define PSG_BEAM_MAX_CAND 2048
+int psg_trie_beam_step(psg_ctx*, const void* logits, int splits, int K, int B, int beams_in, int vocab, int eos,
+                       const int32_t* child_off, const int32_t* child_tok, const int32_t* edge_node,
+                       const int32_t* edge_class, const int32_t* node_tok, const int32_t* node_depth, int n_nodes,
+                       int n_edges, int max_children, int trie_base, const int32_t* seq_len, int32_t* node, float* logp,
+                       int32_t* fin_class, float* fin_logp, int32_t* row_node, int32_t* tok_pos, int32_t* rope_pos,
+                       const void* embed, int embed_dtype, int hidden, void* x_out, int x_dtype, int dtype, void* stream);
 
 /* ---- masked-mean object pooling of the v1-v3 detectors
  * (kings_sgg/models/detectors/openseed_relation.py:453-468):

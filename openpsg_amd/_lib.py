@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpsg_hip.so")
 
-PSG_ABI_VERSION = 613           # include/psg_hip.h; checked against psg_version() of the loaded library
+PSG_ABI_VERSION = 614           # include/psg_hip.h; checked against psg_version() of the loaded library
 PSG_F32, PSG_BF16, PSG_F16 = 0, 1, 2
 PSG_EMPTY_UNIFORM, PSG_EMPTY_UNMASKED = 0, 1
 PSG_XATTN_MFMA, PSG_XATTN_SIMPLE, PSG_XATTN_MFMA_V1 = 0, 1, 2
@@ -175,6 +175,8 @@ SIGNATURES = {
     "psg_token_logprobs": [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i64, _i, _vp],
     "psg_trie_greedy_step": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
                              _i, _vp, _i, _i, _vp],
+    "psg_trie_beam_step": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp],
     "psg_lt_gemm_init": [_vp, C.POINTER(_i)],
     "psg_lt_gemm_candidates": [_vp, _i, _i, _i, _i64, _i64, _i64, _i, _i64, _i64, _i64, _i64, _i, C.POINTER(_i), C.POINTER(_i64),
                                C.POINTER(_i)],

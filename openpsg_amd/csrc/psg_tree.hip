@@ -12,6 +12,12 @@
 //   psg_trie_greedy_step  psg_greedy_step with the arg-max restricted to the children of the row's trie node; the node
 //                       advances on the device, and the path's log-probability is accumulated with the log-sum-exp code
 //                       of psg_token_logprobs (row_lse_256: one copy, both kernels call it).
+//
+// Beam decode over the same trie:
+//   psg_trie_beam_step  one level of a width-B beam: per pair, every edge of every live hypothesis scored score + logit -
+//                       lse (row_lse_256 again), the B best non-leaf edges become the next level's rows and the B best of
+//                       (finished list + this level's EOS edges) the new finished list.  Ranked by counting under a total
+//                       order: no atomics, bit-reproducible.
 #include "psg_common.h"
 
 namespace {
@@ -268,6 +274,142 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// One workgroup per PAIR: one level of the beam.  Candidate slot i = s_off[beam] + (edge - first edge of the
+// beam's node), so the slot order is (beam, edge) ascending - the live pool's tie order; the B entries of the old finished
+// list follow the edges.  s_cls: -2 = no candidate, -1 = live pool, >= 0 = finish pool (the class).
+template <typename T, typename TE, typename TX>
+__global__ void __launch_bounds__(256)
+    trie_beam_step_kernel(const void* __restrict__ logits, int S, int vocab, int B, int beams_in, int eos,
+                          const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_tok,
+                          const int32_t* __restrict__ edge_node, const int32_t* __restrict__ edge_class,
+                          const int32_t* __restrict__ node_tok, const int32_t* __restrict__ node_depth, int n_nodes,
+                          int n_edges, int max_children, int trie_base, const int32_t* __restrict__ seq_len,
+                          int32_t* __restrict__ node, float* __restrict__ logp, int32_t* __restrict__ fin_class,
+                          float* __restrict__ fin_logp, int32_t* __restrict__ row_node, int32_t* __restrict__ tok_pos,
+                          int32_t* __restrict__ rope_pos, const TE* __restrict__ embed, int hidden,
+                          TX* __restrict__ x_out) {
+  __shared__ float s_v[PSG_BEAM_MAX_CAND + PSG_BEAM_MAX_WIDTH];
+  __shared__ int s_edge[PSG_BEAM_MAX_CAND + PSG_BEAM_MAX_WIDTH], s_cls[PSG_BEAM_MAX_CAND + PSG_BEAM_MAX_WIDTH];
+  __shared__ float s_score[PSG_BEAM_MAX_WIDTH];
+  __shared__ int s_c0[PSG_BEAM_MAX_WIDTH], s_cnt[PSG_BEAM_MAX_WIDTH], s_off[PSG_BEAM_MAX_WIDTH + 1];
+  __shared__ int s_live[PSG_BEAM_MAX_WIDTH], s_fin[PSG_BEAM_MAX_WIDTH], s_emit[PSG_BEAM_MAX_WIDTH];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  const int n_int = n_nodes - 1;
+  const int64_t slice = (int64_t)gridDim.x * beams_in * vocab;
+  if (tid < B) {
+    const int nd = tid < beams_in ? node[(int64_t)k * B + tid] : -1;
+    int c0 = 0, cnt = 0;
+    if (nd >= 0 && nd < n_nodes) {
+      c0 = child_off[nd];
+      int c1 = child_off[nd + 1];
+      c0 = c0 < 0 ? 0 : c0;
+      c1 = c1 > n_edges ? n_edges : c1;
+      cnt = c1 - c0;
+      cnt = cnt < 0 ? 0 : (cnt > max_children ? max_children : cnt);   // the host keeps B * max_children <= MAX_CAND
+    }
+    s_c0[tid] = c0;
+    s_cnt[tid] = cnt;
+    s_score[tid] = tid < beams_in ? logp[(int64_t)k * B + tid] : 0.f;
+    s_live[tid] = -1;
+    s_fin[tid] = -1;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int o = 0;
+    for (int b = 0; b < B; ++b) { s_off[b] = o; o += s_cnt[b]; }
+    s_off[B] = o;
+  }
+  __syncthreads();
+  const int n_cand = s_off[B];
+  for (int b = 0; b < beams_in; ++b) {
+    const int cnt = s_cnt[b];
+    if (cnt == 0) continue;                                             // workgroup-uniform: a dead beam reads no logit
+    const int64_t base = ((int64_t)k * beams_in + b) * vocab;
+    const float lse = row_lse_256<T>(logits, S, slice, base, vocab);
+    const float score = s_score[b];
+    for (int j = tid; j < cnt; j += 256) {
+      const int c = s_c0[b] + j, tok = child_tok[c];
+      float v = 0.f;
+      int cls = -2;
+      if (tok >= 0 && tok < vocab) {
+        const float t = logit_at<T>(logits, S, slice, base + tok) - lse;   // psg_token_logprobs' value for this row and child
+        v = score + t;
+        if (!(v != v) && t != -INFINITY) {
+          const int nx = edge_node[c];
+          if (nx >= 0) cls = nx < n_int ? -1 : -2;
+          else {
+            const int r = edge_class[c];
+            cls = r >= 0 ? r : -2;
+          }
+        }
+      }
+      s_v[s_off[b] + j] = v;
+      s_edge[s_off[b] + j] = c;
+      s_cls[s_off[b] + j] = cls;
+    }
+  }
+  if (tid < B) {                                                        // the old finished list: behind the edges
+    const float v = fin_logp[(int64_t)k * B + tid];
+    const int r = fin_class[(int64_t)k * B + tid];
+    s_v[n_cand + tid] = v;
+    s_edge[n_cand + tid] = -1;
+    s_cls[n_cand + tid] = (r >= 0 && !(v != v)) ? r : -2;
+  }
+  __syncthreads();
+  const int total = n_cand + B;
+  for (int i = tid; i < total; i += 256) {
+    const int ci = s_cls[i];
+    if (ci == -2) continue;
+    const float vi = s_v[i];
+    int rank = 0;
+    for (int j = 0; j < total && rank < B; ++j) {
+      const int cj = s_cls[j];
+      if (cj == -2 || (cj < 0) != (ci < 0)) continue;                   // the other pool
+      const float vj = s_v[j];
+      // live pool: v descending, then (beam, edge) = slot ascending; finish pool: v descending, then class, then slot
+      const bool first = vj > vi || (vj == vi && (ci < 0 ? j < i : (cj < ci || (cj == ci && j < i))));
+      rank += first ? 1 : 0;
+    }
+    if (rank < B) (ci < 0 ? s_live : s_fin)[rank] = i;                  // a total order: one slot per rank
+  }
+  __syncthreads();
+  if (tid < B) {
+    const int64_t r = (int64_t)k * B + tid;
+    const int li = s_live[tid], fi = s_fin[tid];
+    int emit = (eos >= 0 && eos < vocab) ? eos : 0;                     // a dead row embeds EOS, as a finished greedy row
+    if (li >= 0) {
+      const int ni = edge_node[s_edge[li]];                             // in [0, n_int): checked when the slot was written
+      const int tk = node_tok[ni];
+      node[r] = ni + 1;
+      logp[r] = s_v[li];
+      row_node[r] = ni;
+      tok_pos[r] = trie_base + ni;
+      rope_pos[r] = seq_len[k] + node_depth[ni] - 1;
+      if (tk >= 0 && tk < vocab) emit = tk;
+    } else {
+      node[r] = -1;
+      logp[r] = -INFINITY;
+      row_node[r] = -1;
+      tok_pos[r] = -1;
+      rope_pos[r] = 0;
+    }
+    fin_class[r] = fi >= 0 ? s_cls[fi] : -1;
+    fin_logp[r] = fi >= 0 ? s_v[fi] : -INFINITY;
+    s_emit[tid] = emit;
+  }
+  if (x_out) {                                                          // kernel-uniform
+    __syncthreads();
+    for (int b = 0; b < B; ++b) {
+      const TE* src = embed + (int64_t)s_emit[b] * hidden;
+      for (int c = tid * 4; c < hidden; c += 256 * 4) {
+        float v[4];
+        Act<TE>::ld4(src, c, v);
+        Act<TX>::st4(x_out, ((int64_t)k * B + b) * hidden + c, v);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int psg_tree_attn(psg_ctx* ctx_, const void* q, const void* k_cache, const void* v_cache,
@@ -349,5 +491,49 @@ extern "C" int psg_trie_greedy_step(psg_ctx* ctx_, const void* logits, int split
   }
 #undef TGS
   PSG_CHECK_LAUNCH("psg_trie_greedy_step");
+  return PSG_OK;
+}
+
+extern "C" int psg_trie_beam_step(psg_ctx* ctx_, const void* logits, int splits, int K, int B, int beams_in, int vocab,
+                                  int eos, const int32_t* child_off, const int32_t* child_tok, const int32_t* edge_node,
+                                  const int32_t* edge_class, const int32_t* node_tok, const int32_t* node_depth,
+                                  int n_nodes, int n_edges, int max_children, int trie_base, const int32_t* seq_len,
+                                  int32_t* node, float* logp, int32_t* fin_class, float* fin_logp, int32_t* row_node,
+                                  int32_t* tok_pos, int32_t* rope_pos, const void* embed, int embed_dtype, int hidden,
+                                  void* x_out, int x_dtype, int dtype, void* stream) {
+  PSG_REQUIRE(B >= 1 && B <= PSG_BEAM_MAX_WIDTH, PSG_ERR_INVALID, "psg_trie_beam_step: beam width B=%d (1..%d)", B,
+              PSG_BEAM_MAX_WIDTH);
+  PSG_REQUIRE(beams_in == 1 || beams_in == B, PSG_ERR_INVALID, "psg_trie_beam_step: beams_in=%d (1 or B=%d)", beams_in, B);
+  PSG_REQUIRE(child_off && child_tok && edge_node && edge_class && node_tok && node_depth, PSG_ERR_INVALID,
+              "psg_trie_beam_step: NULL trie table");
+  PSG_REQUIRE(ctx_ && logits && seq_len && node && logp && fin_class && fin_logp && row_node && tok_pos && rope_pos,
+              PSG_ERR_INVALID, "psg_trie_beam_step: NULL argument");
+  PSG_REQUIRE(n_nodes >= 1 && n_edges >= 0, PSG_ERR_INVALID, "psg_trie_beam_step: n_nodes=%d n_edges=%d", n_nodes, n_edges);
+  PSG_REQUIRE(!x_out || (embed && hidden > 0 && hidden % 4 == 0), PSG_ERR_INVALID,
+              "psg_trie_beam_step: x_out needs the embedding table and hidden %% 4 == 0 (hidden=%d)", hidden);
+  PSG_REQUIRE(K > 0 && vocab > 0 && splits >= 0 && splits <= 64 && trie_base >= 0, PSG_ERR_INVALID,
+              "psg_trie_beam_step: K=%d vocab=%d splits=%d trie_base=%d", K, vocab, splits, trie_base);
+  PSG_REQUIRE(max_children >= 0 && (int64_t)B * max_children <= PSG_BEAM_MAX_CAND, PSG_ERR_UNSUPPORTED,
+              "psg_trie_beam_step: B=%d beams of up to %d children exceed %d candidates per pair", B, max_children,
+              PSG_BEAM_MAX_CAND);
+  if (splits > 0) dtype = PSG_F32;                                      // split-K partials are fp32 slices
+  hipStream_t st = (hipStream_t)stream;
+#define TBS(TE_, TX_)                                                                                                 \
+  PSG_DISPATCH_DTYPE(dtype, "psg_trie_beam_step",                                                                     \
+                     (trie_beam_step_kernel<T, TE_, TX_><<<K, 256, 0, st>>>(                                          \
+                         logits, splits, vocab, B, beams_in, eos, child_off, child_tok, edge_node, edge_class, node_tok, \
+                         node_depth, n_nodes, n_edges, max_children, trie_base, seq_len, node, logp, fin_class, fin_logp, \
+                         row_node, tok_pos, rope_pos, (const TE_*)embed, hidden, (TX_*)x_out)))
+  if (!x_out || (embed_dtype == PSG_F32 && x_dtype == PSG_F32)) TBS(float, float);
+  else if (embed_dtype == PSG_BF16 && x_dtype == PSG_BF16) TBS(bf16_t, bf16_t);
+  else if (embed_dtype == PSG_BF16 && x_dtype == PSG_F32) TBS(bf16_t, float);
+  else if (embed_dtype == PSG_F16 && x_dtype == PSG_F16) TBS(f16_t, f16_t);
+  else if (embed_dtype == PSG_F16 && x_dtype == PSG_F32) TBS(f16_t, float);
+  else {
+    psg_set_error("psg_trie_beam_step: embedding dtype %d -> residual dtype %d unsupported", embed_dtype, x_dtype);
+    return PSG_ERR_UNSUPPORTED;
+  }
+#undef TBS
+  PSG_CHECK_LAUNCH("psg_trie_beam_step");
   return PSG_OK;
 }

@@ -65,6 +65,9 @@ class _Pending:
             sel = self.rq["selected"]
             if out.get("tokens") is None and "_finish" not in out:         # 'multiclass' alone: no decode
                 out["tokens_host"] = out["selected_host"] = None
+            if out.get("beam_class") is not None:                          # llm_beam_width > 1: classes and scores, no tokens
+                out["beam_class_host"], out["beam_logp_host"] = out["beam_class"].cpu().numpy(), out["beam_logp"].cpu().numpy()
+                out["selected_host"] = sel.cpu().numpy()
             if "_finish" in out:                                           # natural EOS: the chunks behind the first
                 out.pop("_finish")()
                 # the deferred chunks were enqueued only now: `_decode_done` of this image (recorded at submit, behind the
@@ -83,7 +86,8 @@ class _Pending:
                 out["mc_host"] = self.rq["mc_topk"].cpu().numpy()
         self.rq.update(out)
         h.last = self.rq
-        rel_pred, rel_score = ([], []) if out["tokens_host"] is None else h._parse_out(out, self.N)
+        decoded = out["tokens_host"] is not None or out.get("beam_class_host") is not None
+        rel_pred, rel_score = h._parse_out(out, self.N) if decoded else ([], [])
         mc_pred, mc_score = h.parse_multiclass(out.get("mc_host"), self.N)
         self.rq = self.out = self.inputs = None
         self._result = dict(rel_pred=rel_pred + mc_pred, rel_score=rel_score + mc_score)
@@ -236,6 +240,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # each selected pair yields exactly one valid relation in max_depth + 1
                                                # steps, and with 'likelihood' its score comes out of the same launches
                                                # 
+                 llm_beam_width=1,             # 1..8, above 1 with 'constrained' + 'likelihood' only: a beam of that width over
+                                               # the relation-name trie instead of the greedy walk - every selected pair
+                                               # yields up to that many scored relations, in max_depth forwards of
+                                               # num_selected x width <= 160 rows on the decode-step kernels.
+                                               # An approximation of the pair's best classes; 1 = today's launches
                  llm_weight_quant=None,        # None | 'fp8': the LLM's q/k/v/o/gate/up/down matrices as OCP e4m3fn bytes with one
                                                # fp32 scale per output row (weights.quantize_fp8_rows): decode
                                                # steps of <= 32 rows stream 1 byte per weight.  The model IS the quantised one
@@ -359,6 +368,25 @@ class RelationTransformerHeadV4(nn.Module):
             raise PsgHipError("llm_decode='constrained' cannot run with suppress_eos=True: a constrained sequence is a relation "
                               "name followed by EOS by definition")
         self.llm_decode = llm_decode
+        if isinstance(llm_beam_width, bool) or not isinstance(llm_beam_width, (int, np.integer)) or not 1 <= llm_beam_width <= 8:
+            raise PsgHipError(f"llm_beam_width must be an int in 1..8, got {llm_beam_width!r}")
+        self.llm_beam_width = int(llm_beam_width)
+        if self.llm_beam_width > 1:
+            if llm_decode != "constrained":
+                raise PsgHipError(f"llm_beam_width={self.llm_beam_width} is a beam over the relation-name trie: it needs "
+                                  f"llm_decode='constrained', got {llm_decode!r}")
+            if llm_rel_scores != "likelihood":
+                raise PsgHipError(f"llm_beam_width={self.llm_beam_width} returns several SCORED relations per pair: it needs "
+                                  f"llm_rel_scores='likelihood', got {llm_rel_scores!r}")
+            if self.num_llm_ranked_triples > 0:
+                raise PsgHipError(f"llm_beam_width={self.llm_beam_width} with num_llm_ranked_triples="
+                                  f"{self.num_llm_ranked_triples}: the trie pass is the other way to several scored relations "
+                                  "per pair - set one of the two")
+            rows = max(int(num_selected), int(max_selected) if pair_selector == "threshold" else 0)
+            if rows * self.llm_beam_width > 160:
+                raise PsgHipError(f"llm_beam_width={self.llm_beam_width}: {rows} selected pairs x {self.llm_beam_width} "
+                                  f"hypotheses = {rows * self.llm_beam_width} rows exceed the 160 rows of the decode-step "
+                                  "kernels (num_selected, or max_selected under pair_selector='threshold')")
         # 'binary': existence head -> top-20 pairs -> LLM decode (V4:206-209, 235-237).  'multiclass' in the type: one
         # sigmoid score per (pair, relation class) from multiclass_rel_cls_pred, the diagonal zeroed, the top
         # `num_multiclass_triples` (pair, class) scores returned behind the LLM triples (V4:238-257, 355-356)
@@ -780,7 +808,8 @@ class RelationTransformerHeadV4(nn.Module):
         if self._front_done is not None:
             st.wait_event(self._front_done)
         rows = max(self.cfg.num_selected, self.max_selected if self.pair_selector == "threshold" else 0)
-        if self._decode_done is not None and (self.cfg.num_selected > 32 or (
+        rows *= self.llm_beam_width                             # a beam's levels are forwards of pairs x width rows
+        if self._decode_done is not None and (rows > 32 or self.cfg.num_selected > 32 or (
                 self.pair_selector == "threshold" and self.max_selected > 32) or not self.llm_engine.use_skinny
                 or self.llm_engine.decode_uses_library(rows)):
             st.wait_event(self._decode_done)
@@ -1102,6 +1131,9 @@ class RelationTransformerHeadV4(nn.Module):
         tools/inflight_stress.py batch.)"""
         if self.training:
             raise NotImplementedError("training branch (V4:114-133, 360-406) is out of scope of this build")
+        if self.llm_beam_width > 1:
+            raise PsgHipError(f"forward_batch decodes one relation per pair; llm_beam_width={self.llm_beam_width} runs through "
+                              "forward / submit")
         if self.llm_rel_scores != "constant":
             raise PsgHipError("forward_batch scores LLM triples with the constant 1 only; llm_rel_scores='likelihood' runs "
                               "through forward / submit")
@@ -1475,7 +1507,8 @@ class RelationTransformerHeadV4(nn.Module):
         sel = rq["selected"] if selected is None else selected
         K = sel.numel()
         sel_in = sel
-        if self.pair_selector == "threshold" and K % 4:
+        if self.pair_selector == "threshold" and K % 4 and (
+                self.llm_beam_width == 1 or (K + 4 - K % 4) * self.llm_beam_width <= 160):      # (a beam stays within 160 rows)
             # the pair count is data dependent here: round it up to a multiple of 4 with copies of the last pair
             # (decode is weight-streaming-bound, extra rows are almost free) so that the engine keeps a few
             # decode graphs instead of one per count
@@ -1490,6 +1523,14 @@ class RelationTransformerHeadV4(nn.Module):
         defer = bool(defer) and eng.use_skinny and sel_in.numel() <= 32 and not eng.decode_uses_library(sel_in.numel())
         con = self._constraint()
         scored = self.llm_rel_scores == "likelihood"
+        if self.llm_beam_width > 1:                             # the beam's classes and scores are the whole result
+            res = eng.generate(X, plen, slot=slot, constraint=con, beam=self.llm_beam_width)
+            out = dict(llm_inputs=X[:K], prompt_len=plen[:K], tokens=None,
+                       beam_class=res[0][:K], beam_logp=res[1][:K])   # padding copies of the threshold selector are cut here
+            if to_host:
+                out["beam_class_host"], out["beam_logp_host"] = out["beam_class"].cpu().numpy(), out["beam_logp"].cpu().numpy()
+                out["selected_host"] = sel.cpu().numpy()
+            return out
         # a constrained decode scores the triple it emits itself: the trie pass (and its cache slots) is needed only for
         # the ranked triples behind it
         trie = self.relation_trie() if scored and (con is None or self.num_llm_ranked_triples > 0) else None
@@ -1522,6 +1563,8 @@ class RelationTransformerHeadV4(nn.Module):
 
     def _parse_out(self, out, N):
         """rel_pred / rel_score of the LLM stage from a decode's host copies."""
+        if out.get("beam_class_host") is not None:
+            return self.parse_beam(out["beam_class_host"], out["beam_logp_host"], out["selected_host"], N)
         if out.get("path_logp_host") is not None:
             return self.parse_path_scored(out["tokens_host"], out["selected_host"], N, out["path_logp_host"],
                                           out.get("logscores_host"))
@@ -1592,6 +1635,22 @@ class RelationTransformerHeadV4(nn.Module):
             return [list(t) for _, t in pairs], own
         rel_pred, rel_score = assemble(pairs, log_scores, selected_host, object_num, self.num_llm_ranked_triples)
         return rel_pred, own + rel_score[len(own):]
+
+    def parse_beam(self, beam_class, beam_logp, selected_host, object_num):
+        """rel_pred / rel_score of a beam decode (llm_beam_width > 1).  beam_class int [K, B] (-1 padded) /
+        beam_logp [K, B]: each pair's hypotheses, best first.  First each pair's best hypothesis in selection order - the K
+        triples llm_decode='constrained' returns -, then the remaining hypotheses of all pairs by descending score, ties to
+        the lower selection rank, then the lower class.  rel_score = exp(logp)."""
+        cls, lp = np.asarray(beam_class), np.asarray(beam_logp, dtype=np.float64)
+        first, rest = [], []
+        for k, si in enumerate(np.asarray(selected_host).tolist()):
+            for b in range(cls.shape[1]):
+                r = int(cls[k, b])
+                if r >= 0:
+                    (first if b == 0 else rest).append((k, r, float(lp[k, b]), [si // object_num, si % object_num, r]))
+        rest.sort(key=lambda e: (-e[2], e[0], e[1]))
+        order = first + rest
+        return [e[3] for e in order], [float(np.exp(e[2])) for e in order]
 
     def relation_trie(self):
         """The token trie of the relation classes' candidate sequences under the current LLM tokenizer (rel_scores.py),

@@ -1093,7 +1093,9 @@ class LlamaDecodeEngine:
         pair).  The last layer then writes K/V for every row (the cache needs them) and runs everything behind the
         attention - output projection, norms, MLP - on those k rows only; returns [k, D].
         tree (the relation-likelihood pass, `_rank_pass`): dict(row_node, prefix_len, anc, base, rope_bound) - the rows are
-        token-trie nodes whose attention is psg_tree_attn over their pair's prompt slots and their trie ancestors."""
+        token-trie nodes whose attention is psg_tree_attn over their pair's prompt slots and their trie ancestors.  With
+        decode=True (the levels of a beam, `_steps`) the projections take the decode-step routes of `linear`, and a row whose
+        tok_pos / row_node is -1 (a dead hypothesis) writes no cache slot and attends to nothing."""
         m = self.cfg.llm
         rows, D = resid.shape
         if (self.prefill_split and self.fuse_split and not self.row_invariant and not decode and prefill_shape is not None
@@ -1104,14 +1106,15 @@ class LlamaDecodeEngine:
         n = torch.empty((rows, D), device=self.device, dtype=self.dtype)
         ops.rmsnorm(resid, None, self.layers[0]["ln1"], m.rms_eps, n)
         q = torch.empty_like(n)
-        att = torch.empty_like(n)
+        # (a dead beam row's attention output is written by nobody: zeros, so that the row stays finite and reproducible)
+        att = torch.zeros_like(n) if decode and tree is not None else torch.empty_like(n)
         act = torch.empty((rows, m.inter), device=self.device, dtype=self.dtype)
         mfma_prefill = (prefill_shape is not None and m.head_dim == 128 and prefill_shape[1] <= 64
                         and not self.prefill_attn_scalar)
         fused_rope = mfma_prefill and self.dtype in (torch.bfloat16, torch.float16)       # rotary + cache write in the launch
         for l, L in enumerate(self.layers):
             qkv = self.linear(n, L["wqkv"], L.get("wqkv_s"), decode=decode)
-            if decode:
+            if decode and tree is None:
                 ops.decode_attn(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, kc[l], vc[l], att,
                                 kv_heads=self.kv)
             elif fused_rope and isinstance(qkv, torch.Tensor) and rope_pos is None:
@@ -1474,7 +1477,7 @@ class LlamaDecodeEngine:
 
     @torch.no_grad()
     def generate(self, X, prompt_len, max_new_tokens=None, suppress_eos=False, return_first_logits=False, slot=0,
-                 gate=None, defer=False, trie=None, constraint=None, path_logp=False):
+                 gate=None, defer=False, trie=None, constraint=None, path_logp=False, beam=None):
         """Batched greedy decode.  X [K, 32+Tp, D]; prompt_len int32 [K] (# of prompt tokens).
         Returns tokens int32 [K, max_new] (device; -1 after a pair's EOS) and optionally the
         first-step logits [K, vocab].
@@ -1500,8 +1503,25 @@ class LlamaDecodeEngine:
         children of the pair's trie node (`ops.trie_greedy_step`), so every pair emits exactly one candidate (a class name
         + EOS) in constraint.max_depth + 1 greedy steps: ONE graph, no early-exit chunks and no read-back.  path_logp: the
         log-probability of each pair's emitted sequence, fp32 [K], is appended to the result (behind the scores of
-        `trie`, if any)."""
+        `trie`, if any).
+        beam (2..8, with constraint=): a beam of that width over the constraint's trie instead of the greedy
+        walk - level 0 on the prompt's last rows, then constraint.max_depth levels of ONE forward over K x beam rows each
+        (`_forward(decode=True, tree=...)`: the decode-step projections, psg_tree_attn over the trie slots behind the
+        decode region) and one `ops.trie_beam_step`; ONE graph, no read-back.  Returns (beam_class int32 [K, beam] (-1
+        padded), beam_logp fp32 [K, beam] (-inf padded)), best first, and nothing else."""
         max_new = self.cfg.max_new_tokens if max_new_tokens is None else max_new_tokens
+        beam = None if beam is None or int(beam) == 1 else int(beam)
+        if beam is not None:
+            if constraint is None:
+                raise PsgHipError(f"beam={beam} is a beam over a relation trie: it needs constraint=")
+            if not 2 <= beam <= ops.BEAM_MAX_WIDTH:
+                raise PsgHipError(f"beam={beam}: the beam width must be in 1..{ops.BEAM_MAX_WIDTH}")
+            if trie is not None or path_logp or return_first_logits:
+                raise PsgHipError(f"beam={beam} returns the beam's classes and scores only: trie=, path_logp and "
+                                  "return_first_logits belong to the greedy decodes")
+            if X.shape[0] * beam > 160:
+                raise PsgHipError(f"beam decode: {X.shape[0]} pairs x beam {beam} = {X.shape[0] * beam} rows exceed the 160 rows "
+                                  "of the decode-step kernels")
         n_steps = max_new
         if constraint is not None:
             n_steps = constraint.max_depth + 1
@@ -1513,18 +1533,20 @@ class LlamaDecodeEngine:
         elif path_logp:
             raise PsgHipError("path_logp is the log-probability of a constrained decode's path: it needs constraint=")
         if not self.use_graph:
-            outs = self._finish(self._generate_eager(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot,
-                                                     trie=trie, constraint=constraint, path_logp=path_logp),
-                                return_first_logits)
+            outs = self._generate_eager(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
+                                        constraint=constraint, path_logp=path_logp, beam=beam)
+            outs = outs if beam is not None else self._finish(outs, return_first_logits)
             return (lambda: outs) if defer else outs
         chunk = 0 if suppress_eos or constraint is not None else int(self.early_exit_chunk)
-        split = gate is not None and n_steps > 1
+        split = gate is not None and n_steps > 1 and beam is None       # a beam is ONE graph: the gate is not called
         key = (tuple(X.shape), max_new, bool(suppress_eos), bool(return_first_logits), chunk, int(slot), split,
                bool(self.row_invariant))
         if trie is not None:
             key = key + (trie.key,)
         if constraint is not None:
             key = key + ("constraint", constraint.key, bool(path_logp))
+        if beam is not None:
+            key = key + (("beam", beam),)
         if self.bf16_value_stream:
             key = key + ("bf16_value_stream",)
         ent = self._graphs.get(key)
@@ -1543,7 +1565,7 @@ class LlamaDecodeEngine:
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):                      # warm-up: lazy library init must not be captured
                 self._generate_eager(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
-                                     constraint=constraint, path_logp=path_logp)
+                                     constraint=constraint, path_logp=path_logp, beam=beam)
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
             if self.persistent_layer:
@@ -1558,7 +1580,7 @@ class LlamaDecodeEngine:
                 with torch.cuda.graph(g, pool=graphs[0][0].pool() if graphs else None):
                     if st is None:
                         st = self._prefill(Xs, ps, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
-                                           constraint=constraint, path_logp=path_logp)
+                                           constraint=constraint, path_logp=path_logp, beam=beam)
                         self._steps(st, 1, hi)
                     else:
                         self._steps(st, lo, hi)
@@ -1592,6 +1614,8 @@ class LlamaDecodeEngine:
             advance(None)
             self._check_persistent(st)
             # the graph's static buffers are overwritten by the next replay: hand out copies
+            if st.get("beam"):
+                return st["fin_class"].clone(), st["fin_logp"].clone()
             fl = st["first_logits"]
             outs = (st["tokens"].clone(), None if fl is None else fl.clone())
             if st.get("rank") is not None:
@@ -1621,10 +1645,17 @@ class LlamaDecodeEngine:
                                   "generation are invalid - disable option decode_persistent")
 
     def _generate_eager(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None,
-                        constraint=None, path_logp=False):
+                        constraint=None, path_logp=False, beam=None):
         st = self._prefill(X, prompt_len, max_new, suppress_eos, return_first_logits, slot=slot, trie=trie,
-                           constraint=constraint, path_logp=path_logp)
+                           constraint=constraint, path_logp=path_logp, beam=beam)
         self._steps(st, 1, max_new if constraint is None else constraint.max_depth + 1)
+        if beam is not None:
+            # below the deepest internal nodes there are only EOS leaves: the live pool is empty after the last level.
+            # Checked once, never inside a capture
+            if not torch.cuda.is_current_stream_capturing() and bool((st["node"] >= 0).any().item()):
+                raise PsgHipError("beam decode: a hypothesis is still alive after max_depth + 1 levels (trie tables and beam "
+                                  "state disagree)")
+            return st["fin_class"], st["fin_logp"]
         if not torch.cuda.is_current_stream_capturing():
             self._check_persistent(st)
             # every path of the trie ends in an EOS leaf within max_depth + 1 edges: checked once, never inside a capture
@@ -1639,14 +1670,16 @@ class LlamaDecodeEngine:
         return outs
 
     def _prefill(self, X, prompt_len, max_new, suppress_eos, return_first_logits, slot=0, trie=None, constraint=None,
-                 path_logp=False):
+                 path_logp=False, beam=None):
         """Prompt pass + first greedy token (+ the relation-likelihood pass over `trie`, whose rows own the cache slots
         behind the decode region).  Returns the decode state (KV caches, token / flag buffers)."""
         m = self.cfg.llm
         self._slot = int(slot)
         K, maxlen, D = X.shape
         nv = self.cfg.qformer.num_query
-        ctx_len = maxlen + max_new + (trie.n_int if trie is not None else 0)
+        # (a beam's rows own the trie slots behind the decode region, as the rows of the relation-likelihood pass do)
+        slots = trie if trie is not None else (constraint if beam is not None else None)
+        ctx_len = maxlen + max_new + (slots.n_int if slots is not None else 0)
         dev = self.device
         seq_len = (prompt_len.to(torch.int32) + nv)                                   # valid tokens per pair
         t = torch.arange(maxlen, device=dev, dtype=torch.int32)[None, :].expand(K, -1)
@@ -1665,6 +1698,8 @@ class LlamaDecodeEngine:
         rank = None
         if trie is not None:
             rank = self._rank_pass(logits, seq_len, kc, vc, ctx_len, maxlen, maxlen + max_new, trie)
+        if beam is not None:
+            return self._beam_root(logits, seq_len, kc, vc, ctx_len, maxlen, maxlen + max_new, constraint, beam, slot)
         tokens = torch.full((K, max_new), -1, device=dev, dtype=torch.int32)
         done = torch.zeros(K, device=dev, dtype=torch.int32)
         next_ids = torch.zeros(K, device=dev, dtype=torch.int32)
@@ -1689,6 +1724,37 @@ class LlamaDecodeEngine:
                     # a captured graph reads the trie's device tables by address: the decode state (which the graph entry
                     # holds) keeps the trie and its tables alive as long as the graph, whatever becomes of the head's trie
                     rank_trie=trie, rank_tables=None if trie is None else trie.device(dev))
+
+    def _beam_root(self, root_logits, seq_len, kc, vc, ctx_len, maxlen, base, trie, B, slot):
+        """Level 0 of a beam of width B over `trie` on the prompt's last rows, and the state of its levels: row
+        k * B + b is hypothesis b of pair k; a live row sits at an internal trie node, whose cache slot is base + node and
+        whose rotary position is seq_len + depth - 1 (the slots and positions of `_rank_pass`)."""
+        m = self.cfg.llm
+        dev = self.device
+        K = seq_len.numel()
+        T = trie.device(dev)
+        if base + trie.n_int > ctx_len:
+            raise PsgHipError(f"beam decode: trie slots [{base}, {base + trie.n_int}) exceed the {ctx_len}-slot cache")
+        i32 = dict(device=dev, dtype=torch.int32)
+        node = torch.full((K, B), -1, **i32)
+        node[:, 0] = 0                                            # one live hypothesis per pair: the root, score 0
+        st = dict(beam=int(B), beam_tables=T, beam_trie=trie,     # kept alive with the graph (DESIGN 11's lifetime rule)
+                  node=node.view(-1), logp=torch.zeros(K * B, device=dev, dtype=torch.float32),
+                  fin_class=torch.full((K, B), -1, **i32),
+                  fin_logp=torch.full((K, B), float("-inf"), device=dev, dtype=torch.float32),
+                  row_node=torch.empty(K * B, **i32), tok_pos=torch.empty(K * B, **i32), rope_pos=torch.empty(K * B, **i32),
+                  row_pair=torch.arange(K, **i32).repeat_interleave(B).contiguous(),
+                  x=torch.empty((K * B, m.hidden), device=dev, dtype=self.resid_dtype), seq_len=seq_len.contiguous(),
+                  kc=kc, vc=vc, ctx_len=ctx_len, base=int(base), slot=int(slot))
+        st["tree"] = dict(row_node=st["row_node"], prefix_len=st["seq_len"], anc=T["anc"], base=int(base),
+                          rope_bound=int(maxlen + trie.max_depth))
+        self._beam_step(st, root_logits, 1)
+        return st
+
+    def _beam_step(self, st, logits, beams_in):
+        ops.trie_beam_step(logits, st["beam"], beams_in, self.cfg.llm.eos, st["beam_tables"], st["base"], st["seq_len"],
+                           st["node"], st["logp"], st["fin_class"], st["fin_logp"], st["row_node"], st["tok_pos"],
+                           st["rope_pos"], embed=self.embed, x_out=st["x"])
 
     def _rank_pass(self, root_logits, seq_len, kc, vc, ctx_len, maxlen, base, trie):
         """The relation-likelihood pass: log s(p, r) for every selected pair p and every class r of `trie`.
@@ -1732,6 +1798,12 @@ class LlamaDecodeEngine:
         """Decode steps lo .. hi-1 (step s writes tokens[:, s])."""
         m = self.cfg.llm
         self._slot = int(st.get("slot", 0))
+        if st.get("beam"):                                     # level `step` of a beam: K x B rows at their trie nodes
+            for step in range(lo, hi):
+                h = self._forward(st["x"], st["row_pair"], st["tok_pos"], st["kc"], st["vc"], st["ctx_len"], decode=True,
+                                  rope_pos=st["rope_pos"], tree=st["tree"])
+                self._beam_step(st, self.logits(h), st["beam"])
+            return
         route = self._decode_route(st["x"].shape[0], st.get("slot", 0), hi > lo)
         if route == "persist":                                 # one counter block per layer launch, zeroed once per call
             per_step = ops.decode_layer_counters(self.device) * len(self.layers)

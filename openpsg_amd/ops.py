@@ -713,6 +713,50 @@ def trie_greedy_step(logits, step, max_new, eos, tables, node, tokens, done, nex
                                    _p(tok_pos, torch.int32), ep, ed, hid, xp, xd, dt, st), "psg_trie_greedy_step")
 
 
+BEAM_MAX_WIDTH = 8                 # include/psg_hip.h: PSG_BEAM_MAX_WIDTH
+
+
+def trie_beam_step(logits, B, beams_in, eos, tables, trie_base, seq_len, node, logp, fin_class, fin_logp, row_node, tok_pos,
+                   rope_pos, embed=None, x_out=None):
+    """One level of a width-B beam over a relation trie (psg_trie_beam_step).  logits [K * beams_in, vocab]
+    (fp32 / 16-bit) or `Partials`; beams_in = 1 (the pairs' root rows) or B.  tables: the device dict of a
+    `rel_scores.RelationTrie` (child_off, child_tok, edge_node, edge_class, node_tok, node_depth, max_children).  State, read
+    and written: node int32 [K * B] (CSR node, -1 = dead), logp fp32 [K * B], fin_class int32 [K, B], fin_logp fp32 [K, B].
+    Written for the next level's rows: row_node / tok_pos / rope_pos int32 [K * B], x_out [K * B, hidden] = embed[token]."""
+    lib, ctx, st = _env(node)
+    rows, vocab = logits.shape
+    B, beams_in = int(B), int(beams_in)
+    if not 1 <= B <= BEAM_MAX_WIDTH:
+        raise PsgHipError(f"trie_beam_step: beam width B={B} must be in 1..{BEAM_MAX_WIDTH}")
+    if beams_in not in (1, B):
+        raise PsgHipError(f"trie_beam_step: beams_in={beams_in} must be 1 or B={B}")
+    if rows % beams_in:
+        raise PsgHipError(f"trie_beam_step: {rows} logit rows are no multiple of beams_in={beams_in}")
+    K = rows // beams_in
+    if isinstance(logits, Partials):
+        lp, ls, dt = _p(logits.t), logits.splits, PSG_F32
+    else:
+        lp, ls, dt = _p(logits), 0, _dt(logits)
+    if x_out is not None:
+        assert embed is not None and x_out.shape == (K * B, embed.shape[1])
+        ep, ed, hid, xp, xd = _p(embed), _dt(embed), embed.shape[1], _p(x_out), _dt(x_out)
+    else:
+        ep, ed, hid, xp, xd = None, 0, 0, None, 0
+    co, ct, en = tables["child_off"], tables["child_tok"], tables["edge_node"]
+    ec, nt, ndp = tables.get("edge_class"), tables.get("node_tok"), tables.get("node_depth")
+    assert en.numel() == ct.numel() and (ec is None or ec.numel() == ct.numel())
+    assert nt is None or ndp is None or nt.numel() == ndp.numel() == co.numel() - 2
+    assert seq_len.numel() == K and fin_class.numel() == K * B == fin_logp.numel()
+    assert all(t.numel() == K * B for t in (node, logp, row_node, tok_pos, rope_pos))
+    i32 = torch.int32
+    check(lib.psg_trie_beam_step(ctx, lp, ls, K, B, beams_in, vocab, int(eos), _p(co, i32), _p(ct, i32), _p(en, i32),
+                                 _p(ec, i32), _p(nt, i32), _p(ndp, i32), co.numel() - 1, ct.numel(), int(tables["max_children"]), int(trie_base),
+                                 _p(seq_len, torch.int32), _p(node, torch.int32), _p(logp, torch.float32),
+                                 _p(fin_class, torch.int32), _p(fin_logp, torch.float32), _p(row_node, torch.int32),
+                                 _p(tok_pos, torch.int32), _p(rope_pos, torch.int32), ep, ed, hid, xp, xd, dt, st),
+          "psg_trie_beam_step")
+
+
 def skinny_gemm_plan(M, N, K, dtype, device) -> int:
     """Split count psg_skinny_gemm would use for x [M, K] of `dtype` against w [N, K]; raises PsgHipError where the kernel
     does not take the shape (psg_skinny_gemm_plan: row count, divisibility, the fp32 kernel's LDS bound)."""

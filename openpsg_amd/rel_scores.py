@@ -44,6 +44,7 @@ class RelationTrie:
       anc [n_int, max_depth]  the node's ancestors root-side first, the node itself last, -1 padded
       child_off [n_int + 2] / child_tok [n_edges]: children of node 0 = root and node 1 + i = internal i (CSR)
       edge_node [n_edges]   internal node an edge leads to, -1 for a leaf (EOS edge)
+      edge_class [n_edges]  class a leaf edge completes (the lowest, where classes share a candidate), -1 for any other edge
       path [R, max_len]     edge indices on class r's path, padded with n_edges (a zero column)
     """
 
@@ -95,6 +96,11 @@ class RelationTrie:
         self.child_tok = np.asarray(ctok, dtype=np.int32)
         self.edge_node = np.asarray(enode, dtype=np.int32)
         self.n_edges = len(ctok)
+        self.edge_class = np.full(len(ctok), -1, dtype=np.int32)
+        for (src, t), rs in leaf_of.items():
+            if enode[edge_of[(src, t)]] < 0:
+                self.edge_class[edge_of[(src, t)]] = min(rs)
+        self.max_children = int(np.diff(self.child_off).max()) if len(ctok) else 0
         self.max_len = max(len(c) for c in self.candidates) if self.candidates else 0
         self.path = np.full((len(self.candidates), max(self.max_len, 1)), self.n_edges, dtype=np.int64)
         for r, c in enumerate(self.candidates):
@@ -121,7 +127,8 @@ class RelationTrie:
             t = lambda a, dt=torch.int32: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)  # noqa: E731
             ent = self._dev[dev] = dict(node_tok=t(self.node_tok), node_depth=t(self.node_depth), anc=t(self.anc),
                                         child_off=t(self.child_off), child_tok=t(self.child_tok),
-                                        edge_node=t(self.edge_node),
+                                        edge_node=t(self.edge_node), edge_class=t(self.edge_class),
+                                        max_children=self.max_children,
                                         path=t(self.path, torch.int64))
         return ent
 

@@ -69,7 +69,17 @@ def parser():
     ap.add_argument("--llm-decode", choices=["greedy", "constrained"], default="greedy",
                     help="constrained: every decode step's arg-max runs over the relation-name trie only - one valid relation "
                     "per selected pair in max_depth + 1 steps instead of 16")
+    ap.add_argument("--llm-beam-width", type=int, default=1,
+                    help="above 1 (--llm-decode constrained; up to 8, pairs x width <= 160): a beam of that width over the "
+                    "relation-name trie - up to that many relations per selected pair, each scored by its decoder likelihood "
+                    "(llm_rel_scores='likelihood' is set with it)")
     return ap
+
+
+def _beam_options(a):
+    """--llm-beam-width above 1: the head's beam, whose scores are the decoder likelihoods."""
+    width = int(getattr(a, "llm_beam_width", 1))
+    return dict(llm_beam_width=width, llm_rel_scores="likelihood") if width > 1 else {}
 
 
 def build_head(a, dev):
@@ -89,7 +99,7 @@ def build_head(a, dev):
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
                                          llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
-                                         llm_decode=getattr(a, "llm_decode", "greedy"))
+                                         llm_decode=getattr(a, "llm_decode", "greedy"), **_beam_options(a))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
     else:
@@ -102,7 +112,7 @@ def build_head(a, dev):
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
                                          llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
-                                         llm_decode=getattr(a, "llm_decode", "greedy"))
+                                         llm_decode=getattr(a, "llm_decode", "greedy"), **_beam_options(a))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
         sd = torch.load(a.checkpoint, map_location="cpu")
