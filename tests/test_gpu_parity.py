@@ -568,7 +568,8 @@ def test_self_attn_shared_query_rows_equals_full_kernel(B, T):
 def test_embed_split_and_periodic_residual_equal_the_full_kernels():
     """Layer-0 redundancy removal: qformer_embed_split writes the query block once + the text rows;
     add_layernorm_periodic reads the residual from that one block.  Both must be bit-identical to the full kernels
-    fed with the per-pair copies."""
+    fed with the per-pair copies.
+    psg_qformer_embed itself is anchored to float64 in tests/test_gpu_image_kernels_ref.py."""
     from openpsg_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(17)
@@ -832,6 +833,8 @@ def test_skinny_gemm_vs_fp32_reference(M, N, K):
 
 @pytest.mark.parametrize("hw,C", [((256, 256), 256), ((128, 128), 256), ((192, 256), 256), ((256, 336), 256), ((64, 48), 32)])
 def test_patch_embed_vs_conv2d(hw, C):
+    """A max-norm check at the workload's shapes; the kernel's anchor - float64, per element, both input families, every
+    tile / split edge - is tests/test_gpu_image_kernels_ref.py."""
     from openpsg_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(hw[0] + hw[1])
@@ -882,7 +885,8 @@ def test_self_attn_mfma_vs_fp32_reference(B, T, q_only):
 
 @pytest.mark.parametrize("geo", [((1024, 1024), None, None, 50), ((768, 1024), (720, 960), (750, 1000), 12)])
 def test_masked_mean_pool_vs_reference_formula(geo):
-    """SURVEY 8f rank 4 (openseed_relation.py:453-468): (feat*m).sum/(m.sum+1e-8) per object."""
+    """SURVEY 8f rank 4 (openseed_relation.py:453-468): (feat*m).sum/(m.sum+1e-8) per object.
+    A max-norm check at the workload's shapes; the kernel's anchor is tests/test_gpu_image_kernels_ref.py."""
     import torch.nn.functional as F
     from openpsg_amd import ops
     from openpsg_amd.synthetic import make_scene
@@ -909,7 +913,8 @@ def test_masked_mean_pool_vs_reference_formula(geo):
 def test_masked_split_mean_pool_vs_reference_formula(output_size):
     """`_mask_pooling(feature, mask, output_size)` (openseed_relation.py:175-200), restated per object in fp64: pixels in
     row-major order, torch.split into output_size chunks (the first n mod k one longer), chunk means; an object with fewer
-    pixels than chunks repeats its pixels; an object without pixels gives zeros."""
+    pixels than chunks repeats its pixels; an object without pixels gives zeros.
+    A max-norm check at the workload's shapes; the kernel's anchor is tests/test_gpu_image_kernels_ref.py."""
     import numpy as np
     import torch.nn.functional as F
     from openpsg_amd import ops
@@ -1006,7 +1011,8 @@ def test_context_options_and_caller_provided_trace_buffer():
 @pytest.mark.parametrize("B,N,R,C", [(1, 50, 56, 768), (2, 7, 3, 40), (1, 100, 56, 256), (1, 33, 5, 33)])
 def test_bilinear_scores_vs_einsum(B, N, R, C):
     """The closed-set heads' scorer (relation_transformer_head_v2.py:204-209) against the reference's own
-    reshape + permute + einsum in fp64."""
+    reshape + permute + einsum in fp64.
+    A max-norm check at the workload's shapes; the kernel's anchor is tests/test_gpu_image_kernels_ref.py."""
     from openpsg_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(B * 1000 + N)
