@@ -27,9 +27,10 @@ import sys
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from ._lib import PsgHipError
 from .config import PSGConfig
+from .llm_matrix import INT4_STREAM_OFF, W4_STREAM_AS_FP8, complete, dense_matrix, load_matrix  # noqa: F401  (the tables: also llm.<name>)
 
 
 # How the library runs one split-fp16 product [rows, K'] x [N, K']^T -> fp32: whole, or cut into column / row parts written
@@ -169,19 +170,6 @@ class _LtRoute:
             why.append("solution not among the library's candidates, its first choice ran: "
                        + ", ".join(f"(N={n}, K'={k}) #{i}" for n, k, i in self.fell_back))
         return sum(len(v) for v in self.lines.values()), "; ".join(why)
-
-
-# MXFP4 shapes (N, K) that stream as their exact FP8 image instead of as nibbles (acceptance rule): a shape goes
-# here when tools/w4_bench.py measured psg_gemm_w4.hip's range of times NOT wholly below psg_gemm_w8.hip's on the same W'.
-# "pair": fp32s engines (psg_split_gemm_w*), "single": 16-bit engines (psg_skinny_gemm_w*).  The image costs a byte per
-# weight and is kept for these shapes only
-W4_STREAM_AS_FP8 = {"pair": frozenset(), "single": frozenset()}
-
-# Group-wise INT4 shapes (N, K) that do NOT stream as codes (acceptance rule): a shape goes here when
-# tools/int4_bench.py measured psg_gemm_int4.hip's range of times not wholly below the range of what the engine runs for
-# the shape on W' without the stream (pair: the fp32 decode kernel, single: the 16-bit skinny kernel).  The engine then
-# runs it on W'; no image is kept for it
-INT4_STREAM_OFF = {"pair": frozenset(), "single": frozenset()}
 
 
 def _plan_split_mm(rows, w3, out_dtype=torch.float32, k3=False, pool=None):
@@ -391,36 +379,11 @@ def _batch_split_route(form, N, K, rows, table=None):
 WB16_STREAM_OFF: frozenset = frozenset()
 
 _LAYER_MATRICES = ("wqkv", "wo", "wgu", "wdown")                  # a decoder layer's projections, by their key in `layers`
-# The streams a matrix can have in a decode step of <= 32 rows (`LlamaDecodeEngine._stream`), each also the name of the step
+# The streams a matrix can have in a decode step of <= 32 rows (`LlmMatrix.stream`), each also the name of the step
 # route on which every decoder matrix has it (`_decode_route`) and the suffix of its pair-form entry ops.split_gemm_<kind>:
 # kind -> the planes of the fp32 rows that entry reads (two fp16 planes + a row scale, or three bf16 planes)
 _STREAM_PLANES = {"w16": 2, "w8": 2, "w4": 2, "int4": 2, "wb16": 3}
 _QUANT_STREAMS = {"w8": "fp8", "w4": "mxfp4", "int4": "int4"}      # ... of a quantised matrix -> the format it streams
-
-
-class QuantMatrix:
-    """A quantised matrix that is resident as bytes ONLY (resident='quantised'): what the layer tables and
-    `lm_head` hold in place of W'.  Carries the shape and dtype W' would have and the quantised parts - (q, s) for FP8,
-    (q, the raw block exponents e, the decode kernel's exponent image, s) for MXFP4.  `data_ptr()` is q's address: the key of
-    the engine's byte-stream tables, alive exactly as long as the bytes are.  A dense operand exists only for the length of
-    one product, in the engine's scratch (`LlamaDecodeEngine._dense`)."""
-    __slots__ = ("name", "fmt", "shape", "dtype", "device", "q", "e", "e_img", "s")
-
-    def __init__(self, name, fmt, shape, dtype, q, s, e=None, e_img=None):
-        self.name, self.fmt, self.shape, self.dtype, self.device = name, fmt, torch.Size(shape), dtype, q.device
-        self.q, self.s, self.e, self.e_img = q, s, e, e_img
-
-    def data_ptr(self):
-        return self.q.data_ptr()
-
-    def numel(self):
-        return self.shape[0] * self.shape[1]
-
-    def parts(self):
-        return [t for t in (self.q, self.e, self.e_img, self.s) if t is not None]
-
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self.parts())
 
 
 class LlamaDecodeEngine:
@@ -466,147 +429,31 @@ class LlamaDecodeEngine:
         self.qkv_width = m.hidden + 2 * m.kv_dim
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         self.n_layers = m.layers if n_layers is None else n_layers        # llm_truncate_num (V4:101-103)
+        self.prefill_split = bool(prefill_split) and dtype == torch.float32
+        dev_i = self.device.index or 0
         f32 = lambda k: weights[k].to(device=self.device, dtype=torch.float32).contiguous()   # noqa: E731
-        act = lambda t: t.to(device=self.device, dtype=dtype).contiguous()                     # noqa: E731
-        # FP8-quantised matrices: `name` holds e4m3fn bytes q, `name + '_scale'` the fp32 per-row scales s, the
-        # model's weight is W' = float32(q) * s.  W' goes under the existing key in the engine's dtype - every path not
-        # built for the byte stream computes the same model on the kernels it has - and `_w8` keeps (q, s) for the decode
-        # steps of <= 32 rows, `_w8h` an exact fp16 copy of q for the fp32s prompt pass (its two-plane operand x fp16 matrix)
-        # MXFP4-quantised matrices: `name` holds two fp4 codes per byte, `name + '_bexp'` the block exponents e,
-        # `name + '_scale'` s; W' = fp4(q) 2^(e - 127) s goes under the existing key likewise, `_w4` keeps (q, the kernel's
-        # exponent image, s) for the decode steps of <= 32 rows, `_w4h` the exact fp16 image of W' / s for the fp32s prompt
-        # pass.  A shape of W4_STREAM_AS_FP8 (measured slower as nibbles than as bytes) gets its exact FP8 image in `_w8`
-        # as well and streams through the FP8 kernels: the same W' bit for bit
-        # Group-wise INT4 matrices (GPTQ / AWQ): `name` holds two 4-bit codes per byte, `name + '_gscale'` the fp16
-        # group scales gs, `name + '_gzero'` the zero points gz; W' = gs (q - gz) goes under the existing key likewise and
-        # `_wi4` keeps (the kernel's code image, its group image) for the decode steps of <= 32 rows - for groups of 128, K %
-        # 256 == 0 and shapes not in INT4_STREAM_OFF.  W' is no fp16 value (gs is an arbitrary fp16 number): the fp32s prompt
-        # pass runs on it as generic fp32 weights, the three-product split route - there is no two-plane image
-        from .weights import (BEXP_SUFFIX, GSCALE_SUFFIX, GZERO_SUFFIX, SCALE_SUFFIX, dequantize_fp8_rows, dequantize_int4_groups,
-                              dequantize_mxfp4_rows, is_quantized, mxfp4_as_fp8_rows, quant_format, _mxfp4_unscaled)
-        self._w8, self._w8h = {}, {}
-        self._w4, self._w4h = {}, {}
-        self._wi4, self._int4 = {}, set()                        # the INT4 streams / every INT4 matrix (data_ptr of W')
+        from .weights import BEXP_SUFFIX, GSCALE_SUFFIX, SCALE_SUFFIX, llm_quant_keys
         if any(str(k).endswith(GSCALE_SUFFIX) for k in weights.keys()) and (lean or batch_quant_stream):
             opt = "resident='quantised'" if lean else "batch_quant_stream"
             raise PsgHipError(f"{opt} is not built for the INT4 format: there is no expand kernel and no 33..160-row kernel "
                               "for it")
         if lean:
-            from .weights import llm_quant_keys
-            dense = [k for k in llm_quant_keys(m.layers if n_layers is None else n_layers) if k + SCALE_SUFFIX not in weights]
+            dense = [k for k in llm_quant_keys(self.n_layers) if k + SCALE_SUFFIX not in weights]
             if dense:
                 raise PsgHipError(f"resident='quantised' needs every decoder-layer matrix quantised; {len(dense)} are not (e.g. "
                                   f"{dense[0]}): set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint, or use "
                                   "resident='all'")
-
-        def quant_parts(keys):
-            """(q, s, e) of the FP8 / MXFP4 matrix of `keys`, row-concatenated and validated: the bytes, the fp32 row scales
-            and the block exponents (None for FP8).  A key's parts are read together, one key after the other (the loader
-            quantises a matrix when it is asked for and keeps none, head.load_llm_weights)."""
-            qs, scs, es = [], [], []
-            for k in keys:
-                qs.append(weights[k].to(self.device).view(torch.uint8))
-                scs.append(weights[k + SCALE_SUFFIX].to(device=self.device, dtype=torch.float32).reshape(-1))
-                es.append(weights[k + BEXP_SUFFIX].to(self.device) if k + BEXP_SUFFIX in weights else None)
-            if any(e is None for e in es) and not all(e is None for e in es):
-                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
-            # (resident='quantised' keeps a single part as it came: no second copy of the largest matrix during the load)
-            cat = lambda ts: (torch.cat(ts, 0) if len(ts) > 1 or not lean else ts[0]).contiguous()   # noqa: E731
-            q, sc = cat(qs), cat(scs)
-            del qs, scs
-            if sc.numel() != q.shape[0]:
-                raise PsgHipError(f"{keys}: {sc.numel()} scales for {q.shape[0]} rows (per-row scales only)")
-            if es[0] is None:
-                return q, sc, None
-            e = cat(es)
-            N, K = q.shape[0], 2 * q.shape[1]
-            if e.dtype != torch.uint8 or tuple(e.shape) != (N, K // 32) or K % 32 or int(e.min()) < 114 or int(e.max()) > 127:
-                raise PsgHipError(f"{keys}: block exponents must be uint8 [{N}, {K // 32}] in 114..127 "
-                                  "(weights.quantize_mxfp4_rows), got " f"{e.dtype} {tuple(e.shape)}")
-            return q, sc, e
-
-        def lean_matrix(keys):
-            """resident='quantised': the matrix of `keys` as a `QuantMatrix`."""
-            name = keys[0].rsplit(".", 2)[0] + "." + "|".join(k.split(".")[-2] for k in keys)
-            q, sc, e = quant_parts(keys)
-            if e is None:
-                N, K = q.shape
-                if N % 16 or K % 128:
-                    raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the FP8 byte-stream kernels of the "
-                                      "decode steps (N % 16 == 0, K % 128 == 0), and there is no W' to fall back on: "
-                                      "resident='all' runs it on W'")
-                w = QuantMatrix(name, "fp8", (N, K), dtype, q, sc)
-                self._w8[w.data_ptr()] = (q, sc)
-                return w
-            N, K = q.shape[0], 2 * q.shape[1]
-            if N % 16 or K % 256:
-                raise PsgHipError(f"resident='quantised': {name} [{N}, {K}] does not fit the MXFP4 nibble-stream kernels of the "
-                                  "decode steps (N % 16 == 0, K % 256 == 0), and there is no W' to fall back on: "
-                                  "resident='all' runs it on W'")
-            # (a W4_STREAM_AS_FP8 shape streams as nibbles here: its FP8 image would be a second resident copy)
-            w = QuantMatrix(name, "mxfp4", (N, K), dtype, q, sc, e, ops.mxfp4_exp_image(e))
-            self._w4[w.data_ptr()] = (q, w.e_img, sc)
-            return w
-
-        def matrix(*keys):
-            """The (row-concatenated) matrix of `keys` in the engine's dtype; registers its byte stream when every part
-            is quantised (per-row scales commute with the concatenation)."""
-            quant = [is_quantized(weights, k) for k in keys]
-            if any(quant) and not all(quant):
-                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some are not")
-            if lean and quant[0]:
-                return lean_matrix(keys)
-            if not quant[0]:
-                return act(torch.cat([weights[k] for k in keys], 0) if len(keys) > 1 else weights[keys[0]])
-            fmts = {quant_format(weights, k) for k in keys}
-            if len(fmts) > 1 and "int4" in fmts:
-                raise PsgHipError(f"{keys}: some parts are INT4-quantised and some FP8- / MXFP4-quantised")
-            if len(fmts) > 1:
-                raise PsgHipError(f"{keys}: some parts are FP8-quantised and some MXFP4-quantised")
-            if fmts == {"int4"}:
-                q = torch.cat([weights[k].to(self.device).view(torch.uint8) for k in keys], 0).contiguous()
-                gss = [weights[k + GSCALE_SUFFIX].to(self.device) for k in keys]
-                gzs = [weights[k + GZERO_SUFFIX].to(self.device) for k in keys]
-                N, K = q.shape[0], 2 * q.shape[1]
-                B = gss[0].shape[-1]
-                if (any(t.dtype != torch.float16 or t.dim() != 2 or t.shape[1] != B for t in gss) or B <= 0 or K % B
-                        or K // B not in (32, 64, 128)
-                        or any(z.dtype != torch.uint8 or z.shape != t.shape for z, t in zip(gzs, gss))
-                        or sum(t.shape[0] for t in gss) != N):
-                    raise PsgHipError(f"{keys}: group scales must be fp16 and zero points uint8 [{N} rows in all, K / G] with G "
-                                      f"in (32, 64, 128) and K = {K} (weights.quantize_int4_groups), got "
-                                      f"{[(t.dtype, tuple(t.shape)) for t in gss + gzs]}")
-                gs, gz = torch.cat(gss, 0).contiguous(), torch.cat(gzs, 0).contiguous()
-                absf = gs.float().abs()
-                if not bool(torch.isfinite(absf).all()) or bool((absf < 2.0 ** -14).any()) or int(gz.max()) > 15:
-                    raise PsgHipError(f"{keys}: group scales must be finite, normal fp16 numbers and zero points 0..15")
-                w = dequantize_int4_groups(q, gs, gz, dtype).contiguous()
-                self._int4.add(w.data_ptr())
-                if (K // B == 128 and K % 256 == 0 and N % 16 == 0
-                        and (N, K) not in INT4_STREAM_OFF["pair" if dtype == torch.float32 else "single"]):
-                    self._wi4[w.data_ptr()] = (ops.int4_q_image(q), ops.int4_group_image(gs, gz))
-                return w
-            q, sc, e = quant_parts(keys)
-            if e is not None:
-                N, K = q.shape[0], 2 * q.shape[1]
-                w = dequantize_mxfp4_rows(q, e, sc, dtype).contiguous()
-                self._w4[w.data_ptr()] = (q, ops.mxfp4_exp_image(e) if K % 256 == 0 else None, sc)
-                if prefill_split and dtype == torch.float32:
-                    self._w4h[w.data_ptr()] = _mxfp4_unscaled(q, e).to(torch.float16)
-                if (N, K) in W4_STREAM_AS_FP8["pair" if dtype == torch.float32 else "single"]:
-                    self._w8[w.data_ptr()] = mxfp4_as_fp8_rows(q, e, sc)
-                return w
-            w = dequantize_fp8_rows(q, sc, dtype).contiguous()
-            self._w8[w.data_ptr()] = (q, sc)
-            if prefill_split and dtype == torch.float32:
-                self._w8h[w.data_ptr()] = q.view(torch.float8_e4m3fn).to(torch.float16)
-            return w
-        self.embed = act(weights["language_model.model.embed_tokens.weight"])
-        self.lm_head = matrix("language_model.lm_head.weight")
+        # one `LlmMatrix` record per (row-concatenated) projection matrix (llm_matrix.py): `mats[l][key]`,
+        # `lm_head_mat`, `proj_mat`.  `layers[l][key]` and `lm_head` are what the records hold as the dense operand W' - or the
+        # record itself where a matrix is resident as bytes only - for readers outside the engine (and the layer norms)
+        load = lambda *keys: load_matrix(weights, keys, self.device, dtype, lean, self.prefill_split)   # noqa: E731
+        held = lambda rec: rec if rec.w is None else rec.w                                             # noqa: E731
+        self.embed = weights["language_model.model.embed_tokens.weight"].to(device=self.device, dtype=dtype).contiguous()
+        self.lm_head_mat = load("language_model.lm_head.weight")
+        self.lm_head = held(self.lm_head_mat)
         self.final_norm = f32("language_model.model.norm.weight")
-        self.proj_w = act(weights["language_projection.weight"])
-        self.proj_b = act(weights["language_projection.bias"])
-        self.layers = []
+        self.set_projection(weights["language_projection.weight"], weights["language_projection.bias"])
+        self.mats, self.layers = [], []
         for l in range(self.n_layers):
             p = f"language_model.model.layers.{l}."
             for n, rows_ in (("q", m.hidden), ("k", m.kv_dim), ("v", m.kv_dim)):
@@ -617,91 +464,49 @@ class LlamaDecodeEngine:
                 if shp != (rows_, m.hidden):
                     raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
                                       f"({m.heads} query / {m.n_kv_heads} key-value heads of 128)")
-            self.layers.append(dict(
-                wqkv=matrix(*[p + f"self_attn.{n}_proj.weight" for n in "qkv"]),
-                wo=matrix(p + "self_attn.o_proj.weight"),
-                wgu=matrix(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
-                wdown=matrix(p + "mlp.down_proj.weight"),
-                ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
-        layer_w = self._layer_matrices()
-        n_q4 = sum(t.data_ptr() in self._w4 for t in layer_w)
-        n_qi = sum(t.data_ptr() in self._int4 for t in layer_w)
-        if n_qi and (n_qi < len(layer_w) or self._w8 or self._w4):
-            raise PsgHipError(f"{n_qi} of the {len(layer_w)} decoder-layer matrices are INT4-quantised: all or none, and one format")
-        self._wi4_layers = n_qi > 0 and all(t.data_ptr() in self._wi4 for t in layer_w)   # every layer matrix streams as codes
-        n_q = sum(t.data_ptr() in self._w8 and t.data_ptr() not in self._w4 for t in layer_w)
+            self.mats.append(dict(
+                wqkv=load(*[p + f"self_attn.{n}_proj.weight" for n in "qkv"]),
+                wo=load(p + "self_attn.o_proj.weight"),
+                wgu=load(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
+                wdown=load(p + "mlp.down_proj.weight")))
+            self.layers.append(dict({k: held(rec) for k, rec in self.mats[-1].items()},
+                                    ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
+        layer_m = self._layer_mats()
+        n_q, n_q4, n_qi = (sum(rec.fmt == f for rec in layer_m) for f in ("fp8", "mxfp4", "int4"))
+        bytes_fmt = any(rec.fmt in ("fp8", "mxfp4") for rec in self.matrices())
+        if n_qi and (n_qi < len(layer_m) or bytes_fmt):
+            raise PsgHipError(f"{n_qi} of the {len(layer_m)} decoder-layer matrices are INT4-quantised: all or none, and one format")
         if n_q and n_q4:
             raise PsgHipError(f"{n_q} decoder-layer matrices are FP8-quantised and {n_q4} MXFP4-quantised: one format")
-        if 0 < n_q < len(layer_w):
-            raise PsgHipError(f"{n_q} of the {len(layer_w)} decoder-layer matrices are FP8-quantised: all or none")
-        if 0 < n_q4 < len(layer_w):
-            raise PsgHipError(f"{n_q4} of the {len(layer_w)} decoder-layer matrices are MXFP4-quantised: all or none")
-        self._w8_layers = n_q > 0                                # every decoder-layer matrix streams as bytes
-        self._w4_layers = n_q4 > 0                               # ... as nibbles (or, per shape, as their exact FP8 image)
+        if 0 < n_q < len(layer_m):
+            raise PsgHipError(f"{n_q} of the {len(layer_m)} decoder-layer matrices are FP8-quantised: all or none")
+        if 0 < n_q4 < len(layer_m):
+            raise PsgHipError(f"{n_q4} of the {len(layer_m)} decoder-layer matrices are MXFP4-quantised: all or none")
+        self._any_quant = n_q + n_q4 + n_qi > 0 or self.lm_head_mat.fmt is not None
         self.use_skinny = True
-        self.prefill_split = bool(prefill_split) and dtype == torch.float32
         self.batch_quant_stream = bool(batch_quant_stream)
-        if self.batch_quant_stream and not (self._w8 or self._w4):
+        if self.batch_quant_stream and not bytes_fmt:
             raise PsgHipError("batch_quant_stream streams a quantised LLM's bytes in the batched decode, and no matrix of this "
                               "model is quantised: set llm_weight_quant='fp8' / 'mxfp4' or load an FP8 / MXFP4 checkpoint")
         self.batch_split_gemm = bool(batch_split_gemm)
         if self.batch_split_gemm and not self.prefill_split:
             raise PsgHipError("batch_split_gemm runs the batched decode of an fp32s engine (dtype float32 with prefill_split) on "
                               "split-fp16 products: the 16-bit engines run psg_batch_gemm there, the exact fp32 engine its SGEMM")
-        self.lm_head_s = None            # batch_split_gemm: the packed [wh | wl] image of a generic lm_head (below)
-        # fp32 engines: are the projection weights fp16 VALUES?  The reference's LLM is the frozen Llama-2-7b-hf checkpoint
-        # (fp16 on disk, configs/psg/baseline_v4_ov.py:61-65) upcast by from_pretrained (V4:99-100): if every element of
-        # every projection round-trips through fp16, the decode steps stream an fp16 copy - half the HBM bytes - instead
-        # of the fp32 tensor: exact mode 'fp32' on the same f32 matrix instructions (psg_skinny_gemm_w16, bit-identical),
-        # mode 'fp32s' as two fp16 products of the split activations (psg_split_gemm_w16, 2^-22).  Anything trained in
-        # fp32 fails the check and keeps the fp32 stream.
-        self._w16 = {}
-        self._skinny_ok = {}
-        self._w16_all = False
-        self._ones_cache = {}
-        from . import _lib
-        dev_i = self.device.index or 0
-        if dtype == torch.float32 and _lib.get_option(dev_i, "llm_w16"):
-            tensors = self._layer_matrices() + [self.lm_head]
-            for t in tensors:                                   # per tensor: a fine-tuned lm_head keeps its fp32 stream alone
-                if self._quantised(t):                          # (has its byte stream: never counted, `_w16_all` stays false)
-                    continue
-                h = t.half()
-                if torch.equal(h.float(), t):
-                    self._w16[t.data_ptr()] = h
-            self._w16_all = len(self._w16) == len(tensors)      # the fused decode step / two-plane prompt pass need all of them
-        # bf16_value_stream: the same question for bf16 - Mistral-7B, Llama-3 and most current Llama-family checkpoints are
-        # bf16 on disk, and a bf16 value below fp16's subnormal grid (0.02 % of an N(0, 0.02) matrix) fails the round trip
-        # above.  Per tensor again: a matrix that is neither quantised nor in `_w16` and round-trips through bf16 keeps a
-        # bf16 copy (2 bytes per weight beside the fp32 tensor and its split image, which the prompt pass still reads)
         if not isinstance(bf16_value_stream, bool):
             raise PsgHipError(f"bf16_value_stream must be a bool, got {bf16_value_stream!r}")
         self.bf16_value_stream = bf16_value_stream
-        self._wb16 = {}
-        if bf16_value_stream and dtype == torch.float32:
-            for t in self._layer_matrices() + [self.lm_head]:
-                if not isinstance(t, torch.Tensor) or t.data_ptr() in self._w16 or self._quantised(t):
-                    continue
-                b = t.bfloat16()
-                if torch.equal(b.float(), t):
-                    self._wb16[t.data_ptr()] = b
-        if self.prefill_split:
-            # [wh | wl | wh] fp16 + the per-row power of two that undoes the row scaling, per projection (3 x 2 bytes per
-            # weight next to the fp32 copy the decode steps stream: 40 GB + 27 GB for Llama-2-7B, of 288 GB)
-            for L in self.layers:
-                for k in _LAYER_MATRICES:
-                    if L[k].data_ptr() not in self._w8 and L[k].data_ptr() not in self._w4:   # (quantised: the two-plane prompt pass on `_w8h` / `_w4h`, no split copy)
-                        L[k + "_s"] = ops.split_f16x3(L[k], weights=True)
-        # batch_split_gemm: a generic fp32 lm_head has no split image (the prompt pass reads one row per pair of it, the decode
-        # steps of <= 32 rows stream the fp32 tensor), and its SGEMM is the longest launch of a 33..160-row step (288-291 us at
-        # 80 / 160 rows against 146 / 187 on the planes): keep the packed [wh | wl] image - 4 bytes per weight, 0.52 GB at
-        # 32000 x 4096, counted under `other` in resident_bytes()
-        lm = self.lm_head
-        if (self.batch_split_gemm and isinstance(lm, torch.Tensor) and lm.dtype == torch.float32 and lm.data_ptr() not in self._w16
-                and not self._quantised(lm) and lm.shape[0] % 16 == 0 and lm.shape[1] % 64 == 0):
-            img, inv = ops.split_f16x3(lm, weights=True)
-            self.lm_head_s = (img[:, :2 * lm.shape[1]].contiguous(), inv)
-            del img
+        complete(layer_m, self.lm_head_mat, dtype, prefill_split=self.prefill_split, llm_w16=bool(_lib.get_option(dev_i, "llm_w16")),
+                 bf16_value_stream=bf16_value_stream, batch_split_gemm=self.batch_split_gemm)
+        # What every decoder-layer matrix is, as the step route it opens (a key of `_STREAM_PLANES`), or None: FP8 / MXFP4
+        # bytes ('w8' / 'w4': all or none, above; an MXFP4 shape may stream its FP8 image), INT4 with every code stream
+        # ('int4'), fp16 values - the lm_head too - ('w16': the fused decode step / two-plane prompt pass need all of them),
+        # bf16 copies ('wb16')
+        every = lambda f: bool(layer_m) and all(f(rec) for rec in layer_m)                             # noqa: E731
+        self.layer_kind = ("w8" if n_q else "w4" if n_q4 else "int4" if every(lambda r: r.int4_img is not None)
+                           else "w16" if all(r.w16 is not None for r in self.matrices())
+                           else "wb16" if every(lambda r: r.wb16 is not None) else None)
+        self._skinny_ok = {}
+        self._ones_cache = {}
         # row_invariant (fp32s engines): the prompt pass's projections and the language projection on psg_dense_gemm - one
         # k-ordered accumulation per output element whatever the row count of the call - instead of the library GEMM, whose
         # kernel choice follows the row count: a pair decoded in a batch of 3 (decodes DEALT over the ranks of a pair-sharded
@@ -709,8 +514,6 @@ class LlamaDecodeEngine:
         # pipeline switches it on, a single GPU does not need it
         self._row_invariant = False
         self.split_i2 = bool(_lib.get_option(dev_i, "split_i2"))
-        self._i2_w = {}
-        self.proj_s = ops.split_f16x3(self.proj_w, weights=True) if self.prefill_split else None
         # greedy argmax over the fp32 split-K sums of the lm_head, NOT over their 16-bit rounding: HF computes the logits of
         # a model cast to 16 bits in 16 bits, but the reference runs the LLM in fp32 (V4:99-100), and a 16-bit logit has
         # an ulp of 0.008-0.016 (fp16) / 0.06 (bf16) at |x| ~ 8-16 - wider than many top-2 margins of a 32000-way
@@ -737,15 +540,15 @@ class LlamaDecodeEngine:
         # decode steps of 33..160 rows: psg_batch_gemm where it beats the library (option decode_batch_gemm)
         self.batch_gemm = bool(_lib.get_option(dev_i, "decode_batch_gemm"))
         self._w_pools = {}
-        for w in self._layer_matrices() + [self.lm_head]:
-            if not isinstance(w, QuantMatrix):                 # (pools time dense tensors in rotation, PSG_PLAN=measure)
-                self._w_pools.setdefault(tuple(w.shape), []).append(w)
+        for rec in self.matrices():
+            if rec.w is not None:                              # (pools time dense tensors in rotation, PSG_PLAN=measure)
+                self._w_pools.setdefault(tuple(rec.shape), []).append(rec.w)
         # resident='quantised': one scratch buffer per slot (`head.submit` runs two streams), as large as the largest
         # quantised matrix in the engine's dtype - the widest form `_dense` makes (the unscaled fp16 operand of the fp32s
         # prompt pass uses its head).  Allocated once, outside any graph: captured graphs replay against its address
         self._slot = 0
         self._scratch = {}
-        self._scratch_elems = max([w.numel() for w in self._quant_matrices()], default=0)
+        self._scratch_elems = max([rec.numel() for rec in self.matrices() if rec.w is None], default=0)
         if lean:
             self._scratch_for(0)
         self._dl_ws = {}
@@ -773,40 +576,23 @@ class LlamaDecodeEngine:
                               "interleaved images of every weight - build the engine with resident='all'")
         self._row_invariant = bool(on)
 
-    def _quant_matrices(self):
-        """The `QuantMatrix` handles of an engine with resident='quantised' (none otherwise)."""
-        return [w for w in self._layer_matrices() + [self.lm_head] if isinstance(w, QuantMatrix)]
+    def _layer_mats(self):
+        """The record of every decoder-layer projection matrix, layer after layer."""
+        return [M[k] for M in self.mats for k in _LAYER_MATRICES]
 
-    def _layer_matrices(self):
-        """Every decoder-layer projection matrix, layer after layer."""
-        return [L[k] for L in self.layers for k in _LAYER_MATRICES]
+    def matrices(self):
+        """... and the lm_head's."""
+        return self._layer_mats() + [self.lm_head_mat]
 
-    def _quantised(self, w):
-        """Has `w` a byte stream of its own (FP8, MXFP4) or is it an INT4 matrix?"""
-        p = w.data_ptr()
-        return p in self._w8 or p in self._w4 or p in self._int4
+    @property
+    def _w16(self):
+        """For the benchmark only: address of a dense tensor of `layers` / `lm_head` -> its fp16 copy."""
+        return {rec.w.data_ptr(): rec.w16 for rec in self.matrices() if rec.w16 is not None}
 
-    def _stream(self, w):
-        """The stream the matrix `w` has in a decode step of <= 32 rows, as (kind, the arguments of ops.split_gemm_<kind> /
-        ops.skinny_gemm_<kind> behind the rows), or None where it has none and runs on its dense tensor.  THE place that says
-        when a table entry is usable.  An FP8 image comes before the nibbles (that is what makes a W4_STREAM_AS_FP8 shape
-        stream as bytes); a quantised matrix has neither 16-bit copy, an fp16-valued one no bf16 copy."""
-        p, (N, K) = w.data_ptr(), w.shape
-        w8 = self._w8.get(p)
-        if w8 is not None and N % 16 == 0 and K % 128 == 0:
-            return "w8", w8
-        w4 = self._w4.get(p)
-        if w4 is not None and w4[1] is not None and N % 16 == 0:      # (K % 256 == 0 or there is no exponent image)
-            return "w4", w4
-        # (an INT4 image exists only for G = 128, K % 256 == 0, N % 16 == 0 and shapes outside INT4_STREAM_OFF)
-        wi4 = self._wi4.get(p)
-        if wi4 is not None:
-            return "int4", wi4
-        if p in self._w16:
-            return "w16", (self._w16[p],)
-        if p in self._wb16:
-            return "wb16", (self._wb16[p],)
-        return None
+    @property
+    def _w16_all(self):
+        """... and: is every decoder-layer matrix and the lm_head an fp16 value?"""
+        return self.layer_kind == "w16"
 
     def _scratch_for(self, slot):
         buf = self._scratch.get(slot)
@@ -817,13 +603,13 @@ class LlamaDecodeEngine:
         return buf
 
     def _dense(self, w, unscaled=False):
-        """THE accessor for the dense operand of a product.  A tensor is its own operand.  A `QuantMatrix` is expanded on
-        the current stream into the current slot's scratch (psg_expand_w8 / _w4) and a view of that is returned: W' in the
-        engine's dtype - weights.dequantize_*_rows bit for bit - or, `unscaled`, the exact fp16 image of W' / s (the fp32s
-        two-plane prompt pass applies s as the column scale).  The view is valid until the slot's next expansion: expand
-        per matrix, immediately before its product."""
-        if not isinstance(w, QuantMatrix):
-            return w
+        """THE accessor for the dense operand of a product over the record `w`: W' in the engine's dtype or, `unscaled`, the
+        fp16 operand of the fp32s two-plane prompt pass - the exact image of W' / s (s is applied as the column scale) or the
+        copy of an fp16-valued W'.  A matrix resident as bytes only is expanded on the current stream into the current slot's
+        scratch (psg_expand_w8 / _w4: weights.dequantize_*_rows bit for bit) and a view of that is returned, valid until
+        the slot's next expansion: expand per matrix, immediately before its product."""
+        if w.w is not None:
+            return w.two_plane() if unscaled else w.w
         buf = self._scratch_for(self._slot)
         if unscaled:
             buf = buf.view(torch.float16)
@@ -833,80 +619,53 @@ class LlamaDecodeEngine:
         return ops.expand_w4(w.q, w.e, s, out=buf)
 
     def resident_bytes(self):
-        """What the engine holds in HBM, in bytes (numel * element_size): `quantised` - the byte streams, block exponents
-        and row scales of its quantised matrices; `scratch` - every slot's expansion scratch; `other` - every other tensor
-        (embedding, norms, projections, rotary tables, and with resident='all' the dense copies W' and their fp16 / split
-        images); `total`.  KV caches and graph pools belong to a generation, not to the engine, and are not counted."""
-        seen, quant = set(), 0
-        for t in [p for w in self._quant_matrices() for p in w.parts()] + \
-                 [p for ent in list(self._w8.values()) + list(self._w4.values()) + list(self._wi4.values()) for p in ent
-                  if p is not None]:
-            if t.data_ptr() not in seen:
-                seen.add(t.data_ptr())
-                quant += t.numel() * t.element_size()
-        scratch = 0
-        for t in self._scratch.values():
-            seen.add(t.data_ptr())
-            scratch += t.numel() * t.element_size()
-        other = 0
+        """What the engine holds in HBM, in bytes (numel * element_size): `quantised` - the byte streams, block exponents,
+        row scales and stream images of its quantised matrices; `scratch` - every slot's expansion scratch; `other` - every
+        other tensor (embedding, norms, rotary tables, and what the records own beside: the dense W', their 16-bit copies and
+        split images); `total`.  KV caches and graph pools belong to a generation, not to the engine, and are not counted."""
+        mats = self.matrices() + [self.proj_mat]
+        norms = [L[k] for L in self.layers for k in ("ln1", "ln2")]
+        seen = set()
 
-        def walk(o):
-            nonlocal other
-            if isinstance(o, torch.Tensor):
-                if o.is_cuda and o.data_ptr() not in seen:
-                    seen.add(o.data_ptr())
-                    other += o.numel() * o.element_size()
-            elif isinstance(o, dict):
-                for v in o.values():
-                    walk(v)
-            elif isinstance(o, (list, tuple)):
-                for v in o:
-                    walk(v)
-        for name in ("embed", "lm_head", "lm_head_s", "final_norm", "proj_w", "proj_b", "proj_s", "layers", "rope", "_w8h", "_w4h",
-                     "_w16", "_wb16", "_i2_w", "_ones_cache"):
-            walk(getattr(self, name, None))
+        def count(tensors):                                    # (a tensor two records share is counted once)
+            fresh = [t for t in tensors if t.data_ptr() not in seen and not seen.add(t.data_ptr())]
+            return sum(t.numel() * t.element_size() for t in fresh)
+        quant = count(t for rec in mats for t in rec.quant_tensors())
+        scratch = count(self._scratch.values())
+        other = count([self.embed, self.final_norm, self.proj_b, *self.rope, *norms, *self._ones_cache.values()]
+                      + [t for rec in mats for t in rec.tensors()])
         return dict(quantised=quant, scratch=scratch, other=other, total=quant + scratch + other)
 
-    def _dense_split(self, ws):
-        """Does `linear_split` run this split weight on psg_dense_gemm (the row-invariant path)?"""
-        return self.row_invariant and ws is not None and ws[0].shape[0] % 256 == 0 and ws[0].shape[1] % 64 == 0
+    def _dense_split(self, w):
+        """Does `linear_split` run the split image of the record `w` on psg_dense_gemm (the row-invariant path)?"""
+        return self.row_invariant and w.split is not None and w.shape[0] % 256 == 0 and (3 * w.shape[1]) % 64 == 0
 
-    def linear_split(self, x, ws, w=None, bias=None):
+    def linear_split(self, x, w, bias=None):
         """x [rows, K] fp32 @ w.T (+ bias) as ONE fp16 matrix-core GEMM over 3K: [xh | xh | xl] . [wh | wl | wh]^T with fp32
         accumulation, rows and columns rescaled by their powers of two afterwards (exact).  Products of fp16 values
         are exact in fp32, so what is lost against an fp32 GEMM is the xl.wl term and the split residuals: ~7e-7
         relative per product (fp32 rounds each product to 6e-8), at 3/16 of the fp32 matrix time."""
-        if self._dense_split(ws):
-            if self.split_i2 and w is not None and w.shape[1] % 32 == 0:
+        w3, inv_c = w.split
+        if self._dense_split(w):
+            if self.split_i2 and w.shape[1] % 32 == 0:
                 # round 6: interleaved hi / lo images, the three products from one staging (psg_dense_gemm_split)
-                w2 = self._i2_weight(w)
+                w2, inv_c = w.interleaved()
                 a2, inv_r = ops.split_f16i2(x)
-                return ops.dense_gemm_split(a2, w2[0], bias, inv_r, w2[1], tile="256x256")
+                return ops.dense_gemm_split(a2, w2, bias, inv_r, inv_c, tile="256x256")
             a3, inv_r = ops.split_f16x3(x)
-            return ops.dense_gemm(a3, ws[0], bias, out_dtype=torch.float32, row_scale=inv_r, col_scale=ws[1])
+            return ops.dense_gemm(a3, w3, bias, out_dtype=torch.float32, row_scale=inv_r, col_scale=inv_c)
         a3, inv_r = ops.split_f16x3(x)
-        y = _split_mm(a3, ws[0], _plan_split_mm(a3.shape[0], ws[0]) if self.plan_split else None)
-        y = ops.scale_rows_cols(y, inv_r, ws[1])
+        y = _split_mm(a3, w3, _plan_split_mm(a3.shape[0], w3) if self.plan_split else None)
+        y = ops.scale_rows_cols(y, inv_r, inv_c)
         return y if bias is None else y + bias
 
     def set_projection(self, weight, bias):
         """Replaces the packed copy of `language_projection` (a checkpoint loaded after the engine was built, an optimizer
-        step in training mode) TOGETHER with everything derived from it: the fp32s split image and the interleaved image
-        of the row-invariant path, whose cache is keyed by the tensor's address - which the allocator hands to the new
-        tensor as soon as the old one is released."""
-        self._i2_w.pop(self.proj_w.data_ptr(), None)
-        self.proj_w = weight.to(device=self.device, dtype=self.dtype).contiguous()
+        step in training mode): a new record, so everything derived from the old tensor - the fp32s split image, the
+        interleaved image of the row-invariant path - goes with it."""
+        self.proj_mat = dense_matrix("language_projection", weight.to(device=self.device, dtype=self.dtype).contiguous(),
+                                     split=self.prefill_split)
         self.proj_b = bias.to(device=self.device, dtype=self.dtype).contiguous()
-        self._i2_w.pop(self.proj_w.data_ptr(), None)
-        self.proj_s = ops.split_f16x3(self.proj_w, weights=True) if self.prefill_split else None
-
-    def _i2_weight(self, w):
-        """The interleaved hi / lo image of a projection weight (+ its rows' inverse scales), made at first use: only the
-        row-invariant path (the dealt decodes of a pair-sharded job) reads it - 4 bytes per weight next to the fp32 tensor."""
-        ent = self._i2_w.get(w.data_ptr())
-        if ent is None:
-            ent = self._i2_w[w.data_ptr()] = ops.split_f16i2(w)
-        return ent
 
     def _streams(self, rows, w, dtype):
         """Can the weight-streaming kernel run `rows` rows of `dtype` against w?  It keeps the rows' K slice in LDS beside its
@@ -933,32 +692,30 @@ class LlamaDecodeEngine:
             t = self._ones_cache[n] = torch.ones(n, device=self.device, dtype=torch.float32)
         return t
 
-    def linear(self, x, w, ws=None, decode=False, batch_stream=True):
-        """Bias-free projection.  Decode-step shapes (<= 32 rows) use the hand-written weight-streaming kernel - in
+    def linear(self, x, rec, decode=False, batch_stream=True):
+        """Bias-free projection of x over the matrix of the record `rec`.  Decode-step shapes (<= 32 rows) use the hand-written weight-streaming kernel - in
         the 16-bit modes and in the fp32 mode (the reference's own precision, V4:99-100) alike; the prompt pass goes
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
         psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm) - or, with
         batch_quant_stream, over a quantised matrix's bytes (`_batch_quant`; batch_stream=False: the caller keeps W')."""
-        stream = self._stream(w)
-        kind = stream[0] if stream is not None else None
-        if (kind in _QUANT_STREAMS and self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype
+        kind, args = rec.stream or (None, None)
+        if (kind in _QUANT_STREAMS and self.use_skinny and x.shape[0] <= 32 and x.dtype == rec.dtype
                 and (self.prefill_split or x.dtype != torch.float32)):
             # quantised matrix, <= 32 rows: one byte (FP8, psg_gemm_w8.hip) or 4.25 bits (MXFP4, psg_gemm_w4.hip; group-wise INT4,
-            # psg_gemm_int4.hip) per weight.  The exact fp32 mode, shapes `_stream` does not accept and more rows run the paths
+            # psg_gemm_int4.hip) per weight.  The exact fp32 mode, shapes without a stream and more rows run the paths
             # below on W'
             if x.dtype == torch.float32:
                 x2, inv = ops.split_f16x2(x)
-                return getattr(ops, "split_gemm_" + kind)(x2, inv, *stream[1])
-            return getattr(ops, "skinny_gemm_" + kind)(x, *stream[1])
-        if (self.batch_quant_stream and batch_stream and decode and self.use_skinny and 32 < x.shape[0] <= 160 and x.dtype == w.dtype
+                return getattr(ops, "split_gemm_" + kind)(x2, inv, *args)
+            return getattr(ops, "skinny_gemm_" + kind)(x, *args)
+        if (self.batch_quant_stream and batch_stream and decode and self.use_skinny and 32 < x.shape[0] <= 160 and x.dtype == rec.dtype
                 and kind in ("w8", "w4") and (self.prefill_split or x.dtype != torch.float32)):   # (no such kernel for INT4)
-            out = self._batch_quant(x, w)
+            out = self._batch_quant(x, rec)
             if out is not None:
                 return out
-        unquantised = isinstance(w, torch.Tensor) and not self._quantised(w)
-        w = self._dense(w)                                    # (resident='quantised': W' expanded into the slot's scratch)
+        w = self._dense(rec)                                  # (resident='quantised': W' expanded into the slot's scratch)
         if self.use_skinny and x.shape[0] <= 32 and x.dtype == w.dtype and self._streams(x.shape[0], w, x.dtype):
-            wh = self._w16.get(w.data_ptr()) if x.dtype == torch.float32 else None
+            wh = rec.w16 if x.dtype == torch.float32 else None
             if wh is not None and self.prefill_split:         # fp32s: two fp16 products of the split rows, 2 bytes per weight
                 x2, inv = ops.split_f16x2(x)
                 return ops.split_gemm_w16(x2, inv, wh)
@@ -975,9 +732,9 @@ class LlamaDecodeEngine:
             # the 16-bit prompt pass of several images (forward_batch: 2 / 4 / 8 x 960 rows): the library's pick for the
             # whole product against its column / row parts (_plan_split_mm; 7-14 % per layer at 1920-7680 rows, nothing at 960)
             return _split_mm(x, w, _plan_split_mm(x.shape[0], w, None, pool=self._w_pools.get(tuple(w.shape))), None)
-        if (self.batch_split_gemm and batch_stream and decode and self.use_skinny and self.prefill_split and unquantised
+        if (self.batch_split_gemm and batch_stream and decode and self.use_skinny and self.prefill_split and rec.fmt is None
                 and 32 < x.shape[0] <= 160 and x.dtype == torch.float32):
-            out = self._batch_split(x, w, ws)
+            out = self._batch_split(x, rec)
             if out is not None:
                 return out
         if decode and x.dtype == torch.float32 and x.shape[0] > 32:
@@ -987,24 +744,24 @@ class LlamaDecodeEngine:
             # fp32 result (2 bytes per weight, 2^-22 per product - the arithmetic of psg_split_gemm_w16); generic fp32
             # weights: the library SGEMM, exact (4 bytes per weight) - NOT the three-segment split product of the prompt
             # pass, which would stream 6 bytes per weight for flops a 160-row step does not need to save
-            wh = self._w16.get(w.data_ptr()) if self.prefill_split else None
+            wh = rec.w16 if self.prefill_split else None
             if wh is not None and w.shape[1] % 8 == 0:
                 a2, inv = ops.split_f16x2(x)
                 y2 = torch.mm(a2.view(2 * x.shape[0], x.shape[1]), wh.t(), out_dtype=torch.float32)
                 return ops.Scaled(y2.view(2, x.shape[0], w.shape[0]), inv, self._ones(w.shape[0])).dense()
             return F.linear(x, w)
-        if ws is not None and x.dtype == torch.float32:
-            return self.linear_split(x, ws, w)
+        if rec.split is not None and x.dtype == torch.float32:
+            return self.linear_split(x, rec)
         return F.linear(x, w)
 
-    def _batch_quant(self, x, w):
+    def _batch_quant(self, x, rec):
         """Decode projection of 33..160 rows over a quantised matrix on its byte / nibble stream (psg_batch_gemm_q.hip,
         DESIGN 16): fp32 slices for the consumers of `ops.batch_gemm`, or None where the shape does not fit the kernels or
         the routing table sends it to the dense path.  fp32s rows go through `split_f16x2` and the pair form, 16-bit rows
-        take the single form.  The stream is the one the matrix has below 33 rows (`_stream`: a matrix with an FP8 image -
+        take the single form.  The stream is the one the matrix has below 33 rows (`rec.stream`: a matrix with an FP8 image -
         FP8 itself, or a W4_STREAM_AS_FP8 shape - streams that)."""
-        rows, (N, K) = int(x.shape[0]), w.shape
-        kind, args = self._stream(w)
+        rows, (N, K) = int(x.shape[0]), rec.shape
+        kind, args = rec.stream
         pair = x.dtype == torch.float32
         if (self.resident != "quantised"
                 and _batch_quant_route(_QUANT_STREAMS[kind], "pair" if pair else "single", N, K, rows) == "dense"):
@@ -1014,29 +771,21 @@ class LlamaDecodeEngine:
             return getattr(ops, "batch_split_gemm_" + kind)(x2, inv, *args)
         return getattr(ops, "batch_gemm_" + kind)(x, *args)
 
-    def _batch_split(self, x, w, ws):
+    def _batch_split(self, x, rec):
         """Decode projection of 33..160 fp32s rows over an unquantised matrix on psg_batch_gemm_s.hip: fp32
         slices for the consumers of `ops.batch_gemm`, or None where the shape does not fit the kernel, the matrix has no
         16-bit operand or the routing table sends it to the library.  An fp16-valued matrix streams its fp16 copy (2 bytes
         per weight, two products); a generic one the [wh | wl] planes of the prompt pass's split image in place - the
-        lm_head: of its packed image `lm_head_s` - (4 bytes per weight, three products)."""
-        rows, (N, K) = int(x.shape[0]), w.shape
+        lm_head: of its packed image - (4 bytes per weight, three products)."""
+        rows, (N, K) = int(x.shape[0]), rec.shape
         if N % 16 or K % 64:
             return None
-        wh = self._w16.get(w.data_ptr())
-        if wh is not None:
-            form = "w16"
-        elif ws is not None and tuple(ws[0].shape) == (N, 3 * K):
-            form = "w32"
-        elif self.lm_head_s is not None and w.data_ptr() == self.lm_head.data_ptr():
-            form, ws = "w32", self.lm_head_s
-        else:
-            return None
-        if _batch_split_route(form, N, K, rows) == "library":
+        ws = rec.split or rec.packed
+        if rec.w16 is None and ws is None or _batch_split_route("w32" if rec.w16 is None else "w16", N, K, rows) == "library":
             return None
         x2, inv = ops.split_f16x2(x)
-        if form == "w16":
-            return ops.batch_split_gemm_w16(x2, inv, wh, self._ones(N))
+        if rec.w16 is not None:
+            return ops.batch_split_gemm_w16(x2, inv, rec.w16, self._ones(N))
         return ops.batch_split_gemm_w32(x2, inv, ws[0], ws[1], K)
 
     def decode_uses_library(self, rows) -> bool:
@@ -1049,12 +798,11 @@ class LlamaDecodeEngine:
         # (the persistent layer and the fused step run the chain's own weight-streaming kernels: answered as the chain)
         route = self._decode_route(rows, per_call=False)
         if route == "wb16":                                    # psg_split_gemm_wb16 for every decoder projection; the lm_head
-            head = self.lm_head                                # follows the stream its tensor has
-            return not (head.data_ptr() in self._wb16 or head.data_ptr() in self._w16 or self._streams(rows, head, self.dtype))
+            head = self.lm_head_mat                            # follows the stream its tensor has
+            return not (head.wb16 is not None or head.w16 is not None or self._streams(rows, head, self.dtype))
         if route is not None:                                  # psg_split_gemm_w16 / _w8 / _w4 / _int4 for every projection
             return False
-        L = self.layers[0] if self.layers else None
-        ws = ([L[k] for k in _LAYER_MATRICES] if L is not None else []) + [self.lm_head]
+        ws = (list(self.mats[0].values()) if self.mats else []) + [self.lm_head_mat]
         return not all(self._streams(rows, w, self.dtype) for w in ws)
 
     def logits(self, h, batch_stream=True):
@@ -1062,7 +810,7 @@ class LlamaDecodeEngine:
         more rows (several images' pairs decoded together): the library GEMM with an fp32 result, so that the greedy
         argmax sees unrounded logits on this path too (exact_argmax) - or, with batch_quant_stream and a quantised
         lm_head, the fp32 slices of its byte stream (batch_stream=False, the trie pass: never)."""
-        out = self.linear(h, self.lm_head, decode=True, batch_stream=batch_stream)
+        out = self.linear(h, self.lm_head_mat, decode=True, batch_stream=batch_stream)
         if isinstance(out, ops.Partials) or not self.exact_argmax or h.dtype == torch.float32:
             return out
         return self._lm_head_f32(h, out)
@@ -1072,14 +820,14 @@ class LlamaDecodeEngine:
         rounded: the 16-bit product, where the caller has it: without `out_dtype` it is widened instead of computed again."""
         if self._mm_out_dtype is None:
             try:
-                probe = self.embed if isinstance(self.lm_head, QuantMatrix) else self.lm_head
+                probe = self.embed if self.lm_head_mat.w is None else self.lm_head_mat.w
                 torch.mm(h[:1], probe[:16].t(), out_dtype=torch.float32)
                 self._mm_out_dtype = True
             except (TypeError, RuntimeError):
                 self._mm_out_dtype = False
         if self._mm_out_dtype:
-            return torch.mm(h, self._dense(self.lm_head).t(), out_dtype=torch.float32)
-        return (F.linear(h, self._dense(self.lm_head)) if rounded is None else rounded).float()
+            return torch.mm(h, self._dense(self.lm_head_mat).t(), out_dtype=torch.float32)
+        return (F.linear(h, self._dense(self.lm_head_mat)) if rounded is None else rounded).float()
 
     # ---- one pass over `rows` token rows -------------------------------------------------------
     def _forward(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, decode=False, prefill_shape=None, rope_pos=None,
@@ -1112,8 +860,8 @@ class LlamaDecodeEngine:
         mfma_prefill = (prefill_shape is not None and m.head_dim == 128 and prefill_shape[1] <= 64
                         and not self.prefill_attn_scalar)
         fused_rope = mfma_prefill and self.dtype in (torch.bfloat16, torch.float16)       # rotary + cache write in the launch
-        for l, L in enumerate(self.layers):
-            qkv = self.linear(n, L["wqkv"], L.get("wqkv_s"), decode=decode)
+        for l, (L, M) in enumerate(zip(self.layers, self.mats)):
+            qkv = self.linear(n, M["wqkv"], decode=decode)
             if decode and tree is None:
                 ops.decode_attn(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, kc[l], vc[l], att,
                                 kv_heads=self.kv)
@@ -1137,11 +885,11 @@ class LlamaDecodeEngine:
                 att, resid = self._gather_kept(att, resid, keep_rows)
                 n = torch.empty_like(att)
                 act = torch.empty((keep_rows.numel(), m.inter), device=self.device, dtype=self.dtype)
-            o = self.linear(att, L["wo"], L.get("wo_s"), decode=decode)
+            o = self.linear(att, M["wo"], decode=decode)
             ops.rmsnorm(resid, o, L["ln2"], m.rms_eps, n)                      # resid += o ; n = norm(resid)
-            gu = self.linear(n, L["wgu"], L.get("wgu_s"), decode=decode)
+            gu = self.linear(n, M["wgu"], decode=decode)
             ops.silu_mul(gu, act)
-            d = self.linear(act, L["wdown"], L.get("wdown_s"), decode=decode)
+            d = self.linear(act, M["wdown"], decode=decode)
             nxt = self.layers[l + 1]["ln1"] if l + 1 < len(self.layers) else self.final_norm
             ops.rmsnorm(resid, d, nxt, m.rms_eps, n)                           # resid += d ; n = norm(resid)
         return n
@@ -1161,13 +909,13 @@ class LlamaDecodeEngine:
         kernels: RMSNorm and SwiGLU write the split fp16 operand, every projection result stays raw (`ops.Scaled`) until
         its reader applies the scales while loading.  Same arithmetic as `_forward` + linear_split, bit for bit.
         Three planes (generic fp32 weights): [hi | hi | lo] K segments against the split weight [wh | wl | wh] and its
-        column scale.  Two planes (every matrix an fp16 value, `self._w16`): a weight has no low part, so a product is ONE
+        column scale.  Two planes (every matrix an fp16 value or FP8 / MXFP4 bytes): a weight has no low part, so a product is ONE
         library GEMM of the operand [xh; xl] (2 x rows rows) against the fp16 weight over K - two thirds of the flops, and
         no split copy of the weights at all; its [2, rows, N] result is summed by the reader (`slices`), the only scale
         left is the row's."""
         m = self.cfg.llm
         rows, D = resid.shape
-        planes = 2 if self._w16_all or self._w8_layers or self._w4_layers else 3
+        planes = 2 if self.layer_kind in ("w16", "w8", "w4") else 3
 
         def plan(r, w, k3=False):                              # a pinned library algorithm, else the shape's table form
             if not self.plan_split:
@@ -1175,18 +923,12 @@ class LlamaDecodeEngine:
             lt = None if _plan_measuring() else self._lt.plan(r, w.shape[0], w.shape[1], planes, k3)
             return lt or _plan_split_mm(r, w, k3=k3)
         if planes == 3:
-            weight = lambda L, k: L[k + "_s"]                                               # noqa: E731
+            weight = lambda rec: rec.split                                                  # noqa: E731
             mm = lambda a3, w3, k3: _split_mm(a3, w3, plan(a3.shape[0], w3, k3=k3))         # noqa: E731
             split = ops.split_f16x3
-        else:
-            if self.resident == "quantised":                    # the same operand, expanded right before its product
-                weight = lambda L, k: (self._dense(L[k], unscaled=True), L[k].s)                # noqa: E731
-            elif self._w8_layers:                               # W' = q s: the exact fp16 image of q, s as the column scale
-                weight = lambda L, k: (self._w8h[L[k].data_ptr()], self._w8[L[k].data_ptr()][1])   # noqa: E731
-            elif self._w4_layers:                               # W' = (fp4(q) 2^(e - 127)) s: likewise
-                weight = lambda L, k: (self._w4h[L[k].data_ptr()], self._w4[L[k].data_ptr()][2])   # noqa: E731
-            else:
-                weight = lambda L, k: (self._w16[L[k].data_ptr()], self._ones(L[k].shape[0]))   # noqa: E731
+        else:                                                  # W' = (the exact fp16 image) s, or an fp16 value: s = 1
+            # (resident='quantised': the same operand, expanded right before its product)
+            weight = lambda rec: (self._dense(rec, unscaled=True), rec.column_scale(self._ones))   # noqa: E731
             split = ops.split_f16x2
 
             def mm(a2, w16, k3):                               # a2 [2, r, K] -> raw product slices [S, r, N]
@@ -1194,16 +936,16 @@ class LlamaDecodeEngine:
                 y = _split_mm(a2.view(2 * r, a2.shape[2]), w16, plan(2 * r, w16, k3=k3))
                 return y.view(-1, r, w16.shape[0])
 
-        def proj(a, inv, L, k, k3=False):                      # k3: the reader (rmsnorm_split) can sum K slices
-            w, col = weight(L, k)
+        def proj(a, inv, rec, k3=False):                       # k3: the reader (rmsnorm_split) can sum K slices
+            w, col = weight(rec)
             return ops.Scaled(mm(a, w, k3), inv, col)
 
         a, inv_r = ops.rmsnorm_split(resid, None, self.layers[0]["ln1"], m.rms_eps, planes=planes)
         q = torch.empty((rows, D), device=self.device, dtype=torch.float32)
         att = torch.empty_like(q)
         n = None
-        for l, L in enumerate(self.layers):
-            qkv = proj(a, inv_r, L, "wqkv")
+        for l, (L, M) in enumerate(zip(self.layers, self.mats)):
+            qkv = proj(a, inv_r, M["wqkv"])
             ops.rope_kvwrite_scaled(qkv, tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
                                     kv_heads=self.kv)
             ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
@@ -1212,11 +954,11 @@ class LlamaDecodeEngine:
             if keep_rows is not None and last:
                 att, resid = self._gather_kept(att, resid, keep_rows)
             ao, inv_o = split(att)                              # a row's maximum spans all heads: stays a kernel of its own
-            o = proj(ao, inv_o, L, "wo", k3=True)
+            o = proj(ao, inv_o, M["wo"], k3=True)
             a, inv_r = ops.rmsnorm_split(resid, o, L["ln2"], m.rms_eps, planes=planes)
-            gu = proj(a, inv_r, L, "wgu")
+            gu = proj(a, inv_r, M["wgu"])
             aa, inv_a = ops.silu_mul_split(gu, m.inter, planes=planes)
-            d = proj(aa, inv_a, L, "wdown", k3=True)
+            d = proj(aa, inv_a, M["wdown"], k3=True)
             if last:                                            # the lm_head reads fp32 rows
                 n = torch.empty_like(resid)
                 ops.rmsnorm(resid, d.dense(), self.final_norm, m.rms_eps, n)
@@ -1232,9 +974,8 @@ class LlamaDecodeEngine:
 
     def _can_persist(self, rows, slot):
         m = self.cfg.llm
-        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32 and not self._w8 and not self._w4
-                and not self._int4
-                and self.kv is None                            # the persistent decoder layer is multi-head only
+        return (self.persistent_layer and self.use_skinny and slot == 0 and self.dtype == torch.float32
+                and not self._any_quant and self.kv is None                           # the persistent decoder layer is multi-head only
                 and ops.decode_layer_supported(rows, m.hidden, m.inter, m.heads, self.dtype, self.device))
 
     def _decode_step_persistent(self, st, counters):
@@ -1264,35 +1005,35 @@ class LlamaDecodeEngine:
         ops.rmsnorm(x, delta, self.final_norm, m.rms_eps, n)
         return self.logits(n)
 
-    def _can_pair(self, rows, every_layer, k_multiple):
-        """fp32s decode steps of <= 32 rows with every projection on the two-plane entry of ONE stream (`every_layer`: every
-        decoder matrix has it), the row kernels writing that operand directly (`_decode_step_split`).  k_multiple: the K step
-        of the stream's kernel."""
+    def _can_pair(self, rows, kind, k_multiple):
+        """fp32s decode steps of <= 32 rows with every projection on the two-plane entry of ONE stream (the decoder layers
+        are of `kind`, `layer_kind`), the row kernels writing that operand directly (`_decode_step_split`).  k_multiple: the
+        K step of the stream's kernel."""
         m = self.cfg.llm
-        return (every_layer and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
+        return (self.layer_kind == kind and self.prefill_split and self.use_skinny and self.fuse_split and rows <= 32
                 and self.dtype == torch.float32 and m.hidden % k_multiple == 0 and m.inter % k_multiple == 0 and m.inter <= 16384
                 and m.hidden <= 8192 and m.vocab % 16 == 0)
 
     def _can_w16(self, rows):
-        """`_can_pair` over fp16-valued weights (`self._w16`): psg_split_gemm_w16, 2 bytes per weight from HBM, two fp16 products per
+        """`_can_pair` over fp16-valued weights: psg_split_gemm_w16, 2 bytes per weight from HBM, two fp16 products per
         projection (high and low part of the fp32 rows) on the 16-bit matrix cores."""
-        return self._can_pair(rows, self._w16_all, 64)
+        return self._can_pair(rows, "w16", 64)
 
     def _can_w8(self, rows):
         """`_can_pair` over FP8-quantised decoder layers: psg_split_gemm_w8, 1 byte per weight, the same two fp16 products on the exactly
         widened bytes, the per-row weight scale applied in fp32 where a slice is stored."""
-        return self._can_pair(rows, self._w8_layers, 128)
+        return self._can_pair(rows, "w8", 128)
 
     def _can_w4(self, rows):
         """`_can_pair` over MXFP4-quantised decoder layers: psg_split_gemm_w4 - or, for a shape of W4_STREAM_AS_FP8, psg_split_gemm_w8 on
         its exact FP8 image - 4.25 bits per weight, nibbles and block scale widened exactly to fp16 in registers."""
-        return self._can_pair(rows, self._w4_layers, 256)
+        return self._can_pair(rows, "w4", 256)
 
     def _can_int4(self, rows):
         """`_can_pair` over group-wise INT4 decoder layers, every one of which has its code stream (groups of 128, K % 256 == 0, none in
         INT4_STREAM_OFF): psg_split_gemm_int4, 4.25 bits per weight, the codes widened to the exact integers q - z in fp16,
         each group's sum scaled in fp32."""
-        return self._can_pair(rows, self._wi4_layers, 256)
+        return self._can_pair(rows, "int4", 256)
 
     @property
     def bf16_stream_active(self):
@@ -1303,13 +1044,10 @@ class LlamaDecodeEngine:
         """fp32s decode steps over bf16-valued decoder layers (option bf16_value_stream): every projection as
         psg_split_gemm_wb16 - 2 bytes per weight, three bf16 products (the exact three-plane form of the fp32 rows) - the row
         kernels writing its three-plane operand directly (`_decode_step_split`)."""
-        if not self._wb16:
-            return False
         m = self.cfg.llm
-        ws = self._layer_matrices()
-        return (all(w.data_ptr() in self._wb16 for w in ws) and self.prefill_split and self.use_skinny and rows <= 32
+        return (self.layer_kind == "wb16" and self.prefill_split and self.use_skinny and rows <= 32
                 and self.dtype == torch.float32 and m.hidden % 64 == 0 and m.inter % 64 == 0 and m.hidden <= 8192
-                and self.qkv_width % 16 == 0 and not any(tuple(w.shape) in WB16_STREAM_OFF for w in ws))
+                and self.qkv_width % 16 == 0 and not any(tuple(w.shape) in WB16_STREAM_OFF for w in self._layer_mats()))
 
     def _decode_route(self, rows, slot=0, per_call=True):
         """THE route of a decode step of `rows` rows: a key of `_STREAM_PLANES` (`_decode_step_split`), 'persist'
@@ -1349,10 +1087,9 @@ class LlamaDecodeEngine:
     def _split_gemm(self, planes, operand, w):
         """The projection of a split operand of `planes` planes over `w` on the stream it has: ops.split_gemm_<kind>, looked
         up when it is called."""
-        stream = self._stream(w)
-        if stream is None or _STREAM_PLANES[stream[0]] != planes:
+        if w.stream is None or _STREAM_PLANES[w.stream[0]] != planes:
             raise PsgHipError(f"decode step: the matrix {tuple(w.shape)} has no stream that reads a {planes}-plane operand")
-        return getattr(ops, "split_gemm_" + stream[0])(*operand, *stream[1])
+        return getattr(ops, "split_gemm_" + w.stream[0])(*operand, *w.stream[1])
 
     def _decode_step_split(self, st, kind):
         """One fp32s decode step of <= 32 rows on the route `kind` (a key of `_STREAM_PLANES`): every decoder projection as
@@ -1364,13 +1101,13 @@ class LlamaDecodeEngine:
         norm, split, swiglu = self._operand_form(planes, rows)
         att = torch.empty((rows, D), device=self.device, dtype=torch.float32)
         a = norm(x, None, self.layers[0]["ln1"])
-        for l, L in enumerate(self.layers):
-            qkv = self._split_gemm(planes, a, L["wqkv"])
+        for l, (L, M) in enumerate(zip(self.layers, self.mats)):
+            qkv = self._split_gemm(planes, a, M["wqkv"])
             ops.decode_attn(qkv, st["dec_pair"], st["dec_pos"], self.rope, m.heads, m.head_dim, st["ctx_len"], st["kc"][l],
                             st["vc"][l], att, kv_heads=self.kv)
-            o = self._split_gemm(planes, split(att), L["wo"])
-            gu = self._split_gemm(planes, norm(x, o, L["ln2"]), L["wgu"])
-            d = self._split_gemm(planes, swiglu(gu), L["wdown"])
+            o = self._split_gemm(planes, split(att), M["wo"])
+            gu = self._split_gemm(planes, norm(x, o, L["ln2"]), M["wgu"])
+            d = self._split_gemm(planes, swiglu(gu), M["wdown"])
             if l + 1 < len(self.layers):
                 a = norm(x, d, self.layers[l + 1]["ln1"])
         return self._lm_head_tail(x, d, planes)
@@ -1382,11 +1119,11 @@ class LlamaDecodeEngine:
         stream on its fp32 tensor, a quantised lm_head under bf16-valued layers on its own stream behind a split launch, and
         the bf16 copy of an lm_head under quantised layers is not streamed."""
         m = self.cfg.llm
-        stream = self._stream(self.lm_head)
+        stream = self.lm_head_mat.stream
         if stream is not None and m.vocab % 16 == 0 and (_STREAM_PLANES[stream[0]] == planes or stream[0] == "w16"):
             planes = _STREAM_PLANES[stream[0]]
             norm = self._operand_form(planes, x.shape[0])[0]
-            return self._split_gemm(planes, norm(x, delta, self.final_norm), self.lm_head)
+            return self._split_gemm(planes, norm(x, delta, self.final_norm), self.lm_head_mat)
         n = torch.empty_like(x)
         ops.rmsnorm(x, delta, self.final_norm, m.rms_eps, n)
         return self.logits(n)
@@ -1394,7 +1131,7 @@ class LlamaDecodeEngine:
     def _can_fuse(self, rows):
         m = self.cfg.llm
         D = m.hidden
-        return (bool(self.fuse_rowops) and not self._w8 and not self._w4 and not self._int4 and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
+        return (bool(self.fuse_rowops) and not self._any_quant and self.use_skinny and self.dtype in (torch.bfloat16, torch.float16)
                 and self.resid_dtype == self.dtype and rows <= 32 and D in (1024, 4096) and m.inter >= 1024 and m.inter % 64 == 0
                 and m.vocab >= 1024 and m.vocab % 16 == 0)
 
@@ -1442,10 +1179,10 @@ class LlamaDecodeEngine:
         K, Tp = prompt_ids.shape
         nv = self.cfg.qformer.num_query
         X = torch.empty((K, nv + Tp, m.hidden), device=self.device, dtype=self.dtype)
-        if self._dense_split(self.proj_s):
-            vis = self.linear_split(pair_feature_rows.contiguous(), self.proj_s, self.proj_w, bias=self.proj_b)
+        if self._dense_split(self.proj_mat):
+            vis = self.linear_split(pair_feature_rows.contiguous(), self.proj_mat, bias=self.proj_b)
         else:                                                  # the exact library product: `linear_split`'s fallback is not
-            vis = F.linear(pair_feature_rows, self.proj_w, self.proj_b)
+            vis = F.linear(pair_feature_rows, self.proj_mat.w, self.proj_b)
         X[:, :nv] = vis.view(K, nv, m.hidden)
         tok = torch.empty((K * Tp, m.hidden), device=self.device, dtype=self.dtype)
         ops.gather_rows(self.embed, prompt_ids.reshape(-1).contiguous(), tok)

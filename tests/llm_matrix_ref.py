@@ -20,6 +20,16 @@ def load(case):
     return H.load_case(case)
 
 
+def formats(eng):
+    """The format (None, 'fp8', 'mxfp4', 'int4') of every matrix record of the engine: the decoder layers', then the lm_head's."""
+    return [rec.fmt for rec in eng.matrices()]
+
+
+def streams(eng):
+    """... and the kind of the stream each has in a decode step of <= 32 rows (None: it runs on W')."""
+    return [rec.stream[0] if rec.stream is not None else None for rec in eng.matrices()]
+
+
 def dequantised(w, n_layers, fmt, lm_head=False):
     """The model a head with llm_weight_quant=fmt computes: W' in fp32 for every quantised matrix (fmt None: w itself)."""
     if fmt is None:

@@ -485,7 +485,7 @@ def test_engine_takes_the_library_gemm_where_the_streaming_kernel_cannot_hold_th
     library GEMM (dense result) instead of raising - a model wider than Llama-2-13B still decodes."""
     from openpsg_amd import _lib, ops
     from openpsg_amd.config import PSGConfig, QFormerConfig, tiny_llm
-    from openpsg_amd.llm import LlamaDecodeEngine
+    from openpsg_amd.llm import LlamaDecodeEngine, dense_matrix
     from openpsg_amd.weights import make_weights_numpy
     dev = _dev()
     assert ops.skinny_gemm_plan(32, 4096, 11008, torch.float32, dev) == 16 and ops.skinny_gemm_plan(20, 4096, 20480, torch.float32, dev) == 16
@@ -499,9 +499,10 @@ def test_engine_takes_the_library_gemm_where_the_streaming_kernel_cannot_hold_th
     g = torch.Generator().manual_seed(2)
     wide = (torch.randn(256, 12288, generator=g) / 110.0).to(dev)
     x = torch.randn(32, 12288, generator=g).to(dev)
-    y32 = eng.linear(x, wide, decode=True)
+    rec = dense_matrix("wide", wide)
+    y32 = eng.linear(x, rec, decode=True)
     assert torch.is_tensor(y32) and torch.equal(y32, torch.nn.functional.linear(x, wide))     # the library's own result
-    y20 = eng.linear(x[:20].contiguous(), wide, decode=True)
+    y20 = eng.linear(x[:20].contiguous(), rec, decode=True)
     assert isinstance(y20, ops.Partials)                                                     # 20 rows still stream
     ref = x[:20].double() @ wide.double().t()
     assert ((y20.reduce(torch.float32).double() - ref).abs() <= 4e-7 * (x[:20].double().abs() @ wide.double().abs().t())).all()

@@ -229,7 +229,7 @@ def test_a_matrix_the_kernels_refuse_keeps_the_dense_path(monkeypatch):
     cfg, w = _tiny(inter=160)
     head = _head(cfg, w, "mixed", suppress_eos=True, llm_weight_quant="fp8", llm_batch_weight_stream="quantised")
     eng = head.llm_engine
-    L = eng.layers[0]
+    L = eng.mats[0]
     calls = _spy(monkeypatch)
     xd = torch.randn(40, 160, device=DEV).to(eng.dtype)
     y_on = eng.linear(xd, L["wdown"], decode=True)
@@ -242,7 +242,7 @@ def test_a_matrix_the_kernels_refuse_keeps_the_dense_path(monkeypatch):
     eng.batch_quant_stream = True
     raw = lambda y: y.t if isinstance(y, ops.Partials) else y                # noqa: E731
     assert type(y_on) is type(y_off) and torch.equal(raw(y_on), raw(y_off))
-    q, s = eng._w8[L["wqkv"].data_ptr()]
+    q, s = L["wqkv"].q, L["wqkv"].s
     wd = q.view(torch.float8_e4m3fn).double() * s.double()[:, None]
     assert ((q_on.t.sum(0).double() - xq.double() @ wd.t()).abs() <= 2.0 ** -20 * (xq.double().abs() @ wd.abs().t())).all()
     scene = make_scene((512, 512), 6, seed=3, device=DEV)

@@ -67,7 +67,8 @@ def _spy(monkeypatch):
 
 def _watch_head(calls, head):
     eng = head.llm_engine
-    copies = [eng._w16.get(eng.lm_head.data_ptr()), eng.lm_head_s[0] if eng.lm_head_s is not None else None]
+    rec = eng.lm_head_mat
+    copies = [rec.w16, rec.packed[0] if rec.packed is not None else None]
     calls["head_ptrs"] = {eng.lm_head.data_ptr()} | {c.data_ptr() for c in copies if c is not None}
     for n in list(calls):
         if n != "head_ptrs":
@@ -163,9 +164,9 @@ def test_two_images_run_the_kernel_and_agree_with_the_single_image_decode_and_th
     # [wh | wl] image the option makes the engine keep (4 bytes per weight, under `other`)
     head_own = _batch_split_route(form, cfg.llm.vocab, cfg.llm.hidden, 2 * K) == "own"
     assert bool(calls[entry + "_head"]) == head_own and bool(calls["library_head"]) == (not head_own)
-    assert (on.llm_engine.lm_head_s is None) == valued
+    assert (on.llm_engine.lm_head_mat.packed is None) == valued
     if not valued:
-        assert tuple(on.llm_engine.lm_head_s[0].shape) == (cfg.llm.vocab, 2 * cfg.llm.hidden)
+        assert tuple(on.llm_engine.lm_head_mat.packed[0].shape) == (cfg.llm.vocab, 2 * cfg.llm.hidden)
     err_on = _oracle_distance(f_on, ref, K, 2)
     print(f"{case} valued={valued}: first-step logits of a batch of 2 against the CPU oracle: option off {err_off:.3e}, "
           f"on {err_on:.3e} (bar {FP32S_ORACLE_BAR:.0e})")
@@ -204,6 +205,6 @@ def test_a_quantised_matrix_follows_llm_batch_weight_stream_alone(monkeypatch):
     head = _head(cfg, wq, "fp32s", llm_batch_split_gemm="own", **kw)
     _watch_head(calls, head)
     r1, t1, f1 = _batch(head, inputs)
-    assert not any(calls[n] or calls[n + "_head"] for n in ENTRIES) and head.llm_engine.lm_head_s is None
+    assert not any(calls[n] or calls[n + "_head"] for n in ENTRIES) and head.llm_engine.lm_head_mat.packed is None
     assert r1 == r0 and all(np.array_equal(a, b) for a, b in zip(t0, t1))
     assert torch.equal(f1.view(torch.int32), f0.view(torch.int32))

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests import llm_matrix_ref as M
 from tests.test_gpu_llm_batch_quant import _free, _load
 from tests.test_gpu_llm_resident import _inputs
 
@@ -145,7 +146,7 @@ def test_the_option_routes_the_decode_steps_and_keeps_the_tokens(case, spy):
     rb_plain = plain.llm_engine.resident_bytes()
     _free(plain, d_plain)
     off = _head(cfg, wb, suppress_eos=sup, llm_bf16_value_stream=False)
-    assert not off.llm_engine.bf16_stream_active and not off.llm_engine._wb16
+    assert not off.llm_engine.bf16_stream_active and "wb16" not in M.streams(off.llm_engine)
     d_off = _decode(off, scene, sel)
     t_off = np.asarray(d_off["tokens_host"]).copy()
     assert np.array_equal(t_off, t_plain) and torch.equal(d_off["first_logits"], f_plain)
@@ -157,8 +158,8 @@ def test_the_option_routes_the_decode_steps_and_keeps_the_tokens(case, spy):
 
     on = _head(cfg, wb, suppress_eos=sup, llm_bf16_value_stream=True)
     eng = on.llm_engine
-    assert eng.bf16_stream_active and len(eng._wb16) == 4 * len(eng.layers) + 1 and not eng.decode_uses_library(20)
-    copies = sum(t.numel() for t in eng._wb16.values())
+    assert eng.bf16_stream_active and M.streams(eng).count("wb16") == 4 * len(eng.layers) + 1 and not eng.decode_uses_library(20)
+    copies = sum(rec.wb16.numel() for rec in eng.matrices())
     rb_on = eng.resident_bytes()
     assert rb_on["other"] - rb_plain["other"] == 2 * copies and rb_on["quantised"] == 0      # 2 bytes per weight
     d_on = _decode(on, scene, sel)
@@ -231,7 +232,7 @@ def test_mixed_generic_and_fp16_valued_weights(spy):
     _free(off)
     on = _head(cfg, wm, suppress_eos=sup, llm_bf16_value_stream=True)
     eng = on.llm_engine
-    assert eng.bf16_stream_active and len(eng._wb16) == 4 * len(eng.layers) and eng.lm_head.data_ptr() not in eng._wb16
+    assert eng.bf16_stream_active and M.streams(eng).count("wb16") == 4 * len(eng.layers) and eng.lm_head_mat.wb16 is None
     t_on = np.asarray(_decode(on, scene, sel)["tokens_host"]).copy()
     log = spy.take()
     head_ptr = eng.lm_head.data_ptr()                             # (this model's lm_head has the output projection's shape)
@@ -243,7 +244,7 @@ def test_mixed_generic_and_fp16_valued_weights(spy):
     logs = {}
     for flag in (False, True):
         h = _head(cfg, w, suppress_eos=sup, llm_bf16_value_stream=flag)
-        assert not h.llm_engine.bf16_stream_active and not h.llm_engine._wb16
+        assert not h.llm_engine.bf16_stream_active and "wb16" not in M.streams(h.llm_engine)
         logs[flag] = (np.asarray(_decode(h, scene, sel)["tokens_host"]).copy(), spy.take())
         _free(h)
     strip = lambda log: [e if isinstance(e, str) else e[:2] for e in log]    # noqa: E731  (addresses differ between heads)
@@ -251,7 +252,7 @@ def test_mixed_generic_and_fp16_valued_weights(spy):
     assert not set(_names(logs[True][1])) & set(NEW_OPS)
     # fp16-valued weights still take the fp16 stream
     h = _head(cfg, _valued(w, torch.float16), suppress_eos=sup, llm_bf16_value_stream=True)
-    assert h.llm_engine._w16_all and not h.llm_engine._wb16 and not h.llm_engine.bf16_stream_active
+    assert h.llm_engine._w16_all and "wb16" not in M.streams(h.llm_engine) and not h.llm_engine.bf16_stream_active
     _decode(h, scene, sel)
     names = set(_names(spy.take()))
     assert "split_gemm_w16" in names and not names & set(NEW_OPS)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests import llm_matrix_ref as M
 from tests.test_gpu_llm_w8 import _assert_tokens_agree, _decode, _head, _step_margins
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def _fp32s_pair(case, loader, monkeypatch, lm_head=False):
     g, cfg, w, scene = loader(case)
     sup = bool(g["suppress_eos"])
     ref = _head(cfg, _dequantised(w, cfg.llm.layers, lm_head), "fp32s", suppress_eos=sup)
-    assert not ref.llm_engine._wi4 and not ref.llm_engine._int4 and not ref.llm_engine._w4 and not ref.llm_engine._w8
+    assert set(M.formats(ref.llm_engine)) == {None} and set(M.streams(ref.llm_engine)) <= {None, "w16"}
     rq0, dec0 = _decode(ref, g, scene)
     margins = _step_margins(ref, dec0, sup)
     t0, f0 = np.asarray(dec0["tokens_host"]).copy(), dec0["first_logits"].float().cpu()
@@ -50,10 +51,10 @@ def _fp32s_pair(case, loader, monkeypatch, lm_head=False):
     calls = _spy(monkeypatch)
     head = _head(cfg, w, "fp32s", suppress_eos=sup, llm_weight_quant="int4g", llm_quantize_lm_head=lm_head)
     eng = head.llm_engine
-    assert eng._wi4_layers and not eng._w8_layers and not eng._w4_layers and not eng._w16
-    assert len(eng._wi4) == len(eng._int4) == 4 * len(eng.layers) + int(lm_head)
+    assert eng.layer_kind == "int4" and not eng._w16
+    assert M.streams(eng).count("int4") == M.formats(eng).count("int4") == 4 * len(eng.layers) + int(lm_head)
     # W' is no fp16 value: the prompt pass keeps the three-product split copies
-    assert all(k + "_s" in L for L in eng.layers for k in ("wqkv", "wo", "wgu", "wdown"))
+    assert all(rec.split is not None for rec in eng._layer_mats())
     assert eng._can_int4(20) and not eng._can_persist(20, 0) and not eng._can_fuse(20)
     rq, dec = _decode(head, g, scene)
     assert calls["split_gemm_int4"] > 0 and calls["skinny_gemm_int4"] == 0
@@ -180,7 +181,7 @@ def test_gptq_and_awq_checkpoint_directories_through_the_constructor(tmp_path):
             fed[k] = v.half()
     b = RelationTransformerHeadV4(llm_config=cfg.llm, **kw)
     b.load_weights(fed)
-    assert b.llm_engine._wi4_layers and b.llm_engine.lm_head.data_ptr() not in b.llm_engine._int4
+    assert b.llm_engine.layer_kind == "int4" and b.llm_engine.lm_head_mat.fmt is None
     scene = make_scene((512, 512), 6, seed=3, device=DEV)
     inputs = dict(mask_features=scene["mask_features"], img_metas=[scene["img_meta"]],
                   object_info=[dict(object_id_list=scene["object_id_list"], pan_results=scene["pan_results"])])
@@ -189,7 +190,7 @@ def test_gptq_and_awq_checkpoint_directories_through_the_constructor(tmp_path):
         d = str(tmp_path / tag)
         write_int4_checkpoint(d, cfg, w, model, **args)
         a = RelationTransformerHeadV4(llm_model_name=d, **kw)                 # no option: the checkpoint IS quantised
-        assert a.llm_engine._wi4_layers
+        assert a.llm_engine.layer_kind == "int4"
         a.load_state_dict(own, strict=False)
         ra = a(inputs)
         assert torch.equal(a.last["tokens"], b.last["tokens"]) and torch.equal(a.last["first_logits"], b.last["first_logits"])

@@ -199,7 +199,7 @@ def test_a_constrained_decode_on_the_quantised_stream(case, dtype, fmt, lm_head,
         wq = M.dequantised({k: v.clone() for k, v in w.items()}, cfg.llm.layers, fmt, lm_head)
         off = _head(cfg, wq, dtype, llm_decode="constrained", llm_rel_scores="likelihood")
         oe = off.llm_engine
-        assert not oe._w8 and not oe._w4 and not oe._int4
+        assert set(M.formats(oe)) == {None}
         _reset(calls, steps)
         off(inp)
         assert all(calls[n] == 0 for n in ALL_STREAMS)

@@ -58,12 +58,12 @@ def _quantised_bytes(m, fmt, lm_head):
 
 
 def _tensors(o, skip=()):
-    """Every tensor reachable from an engine attribute / layer table (QuantMatrix handles opened)."""
-    from openpsg_amd.llm import QuantMatrix
+    """Every tensor reachable from an engine attribute / layer table (matrix records opened)."""
+    from openpsg_amd.llm_matrix import LlmMatrix
     if isinstance(o, torch.Tensor):
         yield o
-    elif isinstance(o, QuantMatrix):
-        yield from o.parts()
+    elif isinstance(o, LlmMatrix):
+        yield from o.tensors()
     elif isinstance(o, dict):
         for v in o.values():
             yield from _tensors(v)
@@ -73,14 +73,14 @@ def _tensors(o, skip=()):
 
 
 def _assert_holds_bytes_only(eng, m, fmt, lm_head):
-    from openpsg_amd.llm import QuantMatrix
     assert eng.resident == "quantised"
-    assert all(isinstance(L[k], QuantMatrix) for L in eng.layers for k in MATS)
-    assert isinstance(eng.lm_head, QuantMatrix) == bool(lm_head)
-    assert not eng._w8h and not eng._w4h and not eng._i2_w
+    # the layer tables and `lm_head` hold the record itself in place of W': there is none
+    assert all(L[k] is M[k] and M[k].w is None for L, M in zip(eng.layers, eng.mats) for k in MATS)
+    assert (eng.lm_head is eng.lm_head_mat and eng.lm_head_mat.w is None) == bool(lm_head)
+    assert all(rec.h16 is None and rec.i2 is None for rec in eng.matrices() + [eng.proj_mat])
     # (`_w16`: fp16 images of fp16-VALUED matrices that are not quantised - at most the dense lm_head of an fp16 checkpoint)
     assert set(eng._w16) <= (set() if lm_head else {eng.lm_head.data_ptr()})
-    assert all(k + "_s" not in L for L in eng.layers for k in MATS)
+    assert all(rec.split is None for rec in eng.matrices())
     rb = eng.resident_bytes()
     assert rb["quantised"] == _quantised_bytes(m, fmt, lm_head)
     assert rb["scratch"] == sum(t.numel() * t.element_size() for t in eng._scratch.values()) > 0
@@ -89,7 +89,7 @@ def _assert_holds_bytes_only(eng, m, fmt, lm_head):
     # caches, activations).  Known by identity and allowed: the scratch and the matrices that are NOT quantised (embedding,
     # a dense lm_head, language_projection and its split image, rotary tables), whatever table refers to them
     counts = {N * K for N, K in _matrix_shapes(m, lm_head)}
-    allowed = {t.data_ptr() for n in ("_scratch", "embed", "proj_w", "proj_b", "proj_s", "rope") for t in _tensors(getattr(eng, n))}
+    allowed = {t.data_ptr() for n in ("_scratch", "embed", "proj_mat", "proj_b", "rope") for t in _tensors(getattr(eng, n))}
     if not lm_head:
         allowed.add(eng.lm_head.data_ptr())
         allowed |= {t.data_ptr() for t in eng._w16.values()}                 # (its fp16 image, asserted above to be the only entry)
@@ -305,7 +305,7 @@ def test_fp8_checkpoint_directory_read_lean(tmp_path):
     ra = a(inputs)
     b = RelationTransformerHeadV4(llm_weight_resident="quantised", **kw)
     b.load_state_dict(own, strict=False)
-    assert b.llm_engine.resident == "quantised" and b.llm_engine._w8_layers
+    assert b.llm_engine.resident == "quantised" and b.llm_engine.layer_kind == "w8"
     _assert_holds_bytes_only(b.llm_engine, cfg.llm, "fp8", False)
     rb = b(inputs)
     assert torch.equal(a.last["tokens"], b.last["tokens"]) and torch.equal(a.last["first_logits"], b.last["first_logits"])

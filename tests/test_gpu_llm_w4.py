@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests import llm_matrix_ref as M
 from tests.test_gpu_llm_w8 import _assert_tokens_agree, _decode, _head, _step_margins
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def _fp32s_pair(case, loader, monkeypatch, lm_head=False):
     g, cfg, w, scene = loader(case)
     sup = bool(g["suppress_eos"])
     ref = _head(cfg, _dequantised(w, cfg.llm.layers, lm_head), "fp32s", suppress_eos=sup)
-    assert not ref.llm_engine._w4 and not ref.llm_engine._w8
+    assert set(M.formats(ref.llm_engine)) == {None}
     rq0, dec0 = _decode(ref, g, scene)
     margins = _step_margins(ref, dec0, sup)
     t0, f0 = np.asarray(dec0["tokens_host"]).copy(), dec0["first_logits"].float().cpu()
@@ -48,8 +49,8 @@ def _fp32s_pair(case, loader, monkeypatch, lm_head=False):
     calls = _spy(monkeypatch)
     head = _head(cfg, w, "fp32s", suppress_eos=sup, llm_weight_quant="mxfp4", llm_quantize_lm_head=lm_head)
     eng = head.llm_engine
-    assert eng._w4_layers and not eng._w8_layers and len(eng._w4) == 4 * len(eng.layers) + int(lm_head) and not eng._w16
-    assert all(k + "_s" not in L for L in eng.layers for k in ("wqkv", "wo", "wgu", "wdown"))   # no 6-byte split copies
+    assert eng.layer_kind == "w4" and M.formats(eng).count("mxfp4") == 4 * len(eng.layers) + int(lm_head) and not eng._w16
+    assert all(rec.split is None for rec in eng.matrices())                                    # no 6-byte split copies
     assert not eng.decode_uses_library(20) and not eng._can_persist(20, 0) and not eng._can_fuse(20)
     rq, dec = _decode(head, g, scene)
     assert calls["split_gemm_w4"] > 0 and calls["skinny_gemm_w4"] == 0
@@ -171,7 +172,7 @@ def test_mxfp4_checkpoint_directory_through_the_constructor(tmp_path):
     kw = dict(dtype="fp32s", device=DEV, qformer_vocab_size=512, tokenizers="word", max_object_num=30, on_parse_error="skip",
               suppress_eos=True, llm_feature_size=256)
     a = RelationTransformerHeadV4(llm_model_name=d, **kw)                     # no option: the checkpoint IS quantised
-    assert a.llm_engine._w4_layers and a.llm_engine.lm_head.data_ptr() not in a.llm_engine._w4
+    assert a.llm_engine.layer_kind == "w4" and a.llm_engine.lm_head_mat.fmt is None
     own = {k: v for k, v in w.items() if not k.startswith("language_model.")}
     a.load_state_dict(own, strict=False)
     b = RelationTransformerHeadV4(llm_config=cfg.llm, **kw)

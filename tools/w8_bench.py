@@ -111,7 +111,7 @@ def bench_images(steps, layers):
             torch.cuda.synchronize()
             times.append((time.perf_counter() - t0) * 1e3)
         eng = h.llm_engine
-        r = dict(mode=mode, llm_weight_quant=quant, layers=layers, w16_stream=bool(eng._w16_all), w8_stream=bool(eng._w8_layers),
+        r = dict(mode=mode, llm_weight_quant=quant, layers=layers, w16_stream=bool(eng._w16_all), w8_stream=eng.layer_kind == "w8",
                  ms_per_image_median=round(sorted(times)[len(times) // 2], 2), ms_per_image_all=[round(t, 2) for t in times])
         res.append(r)
         print("image", r, flush=True)
