@@ -85,8 +85,10 @@ enum psg_xattn_variant { PSG_XATTN_MFMA = 0, PSG_XATTN_SIMPLE = 1, PSG_XATTN_MFM
  *        psg_silu_mul_split_b16x3, psg_split_gemm_wb16(_plan) added
  *   613  the prompt pass's library products with a pinned algorithm: psg_lt_gemm_init, psg_lt_gemm_candidates, psg_lt_gemm
  *        added
- *   614  beam decode over the relation-name trie: psg_trie_beam_step added */
-#define PSG_ABI_VERSION 614
+ *   614  beam decode over the relation-name trie: psg_trie_beam_step added
+ *   615  bf16-valued LLM weights resident as bf16 only, the batched decode on three bf16 planes:
+ *        psg_batch_split_gemm_wb16(_plan) added */
+#define PSG_ABI_VERSION 615
 int psg_version(void);
 const char* psg_last_error(void);
 int psg_create(int device, psg_ctx** out);
@@ -486,6 +488,16 @@ int psg_batch_split_gemm_w32_plan(psg_ctx*, int M, int N, int K, int mode, int* 
 int psg_batch_split_gemm_w32(psg_ctx*, const void* x2, const float* inv_scale, const void* w_img, int64_t row_stride,
                              int64_t lo_off, const float* col_scale, float* part, int M, int N, int K, int slots, int mode,
                              void* stream);
+/* psg_split_gemm_wb16 for 33 <= M <= 160 rows: x3 the bf16 planes [3][M][K] of psg_split_b16x3 (x = x0 + x1 + x2
+ * exactly), wb16 bf16 [N][K] contiguous (a weight that IS a bf16 value).  Every bf16 x bf16 product is exact in fp32 and all
+ * three planes' products of an output element go into one fp32 accumulator (per K step of 64: x2 . w, x1 . w, x0 . w):
+ *   part[slot][m][n] = (x2 . w + x1 . w + x0 . w)[m][n]; no row or column scale.
+ * 33 <= M <= 160, N % 16 == 0, K % 64 == 0, x3 / wb16 / part 16-byte aligned, else PSG_ERR_UNSUPPORTED without a launch.
+ * Slices (k-ordered, slots <= 16, no atomics, unused slots zero-filled), plan entry, modes and row independence (the plan
+ * is a function of N, K and mode only; rows :M of a 160-row call are bit-equal to the M-row call) as the entries above. */
+int psg_batch_split_gemm_wb16_plan(psg_ctx*, int M, int N, int K, int mode, int* slots);
+int psg_batch_split_gemm_wb16(psg_ctx*, const void* x3, const void* wb16, float* part, int M, int N, int K, int slots, int mode,
+                              void* stream);
 /* The dense operand of a quantised matrix, rebuilt from its bytes (an engine that keeps only the bytes resident
  * expands a matrix into a scratch buffer right before the one large-M product that reads it).  q: e4m3fn bytes [N][K]
  * (psg_expand_w8) or fp4 nibbles [N][K / 2], the low nibble the even k, with the RAW block exponents e uint8 [N][K / 32] in

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpsg_hip.so")
 
-PSG_ABI_VERSION = 614           # include/psg_hip.h; checked against psg_version() of the loaded library
+PSG_ABI_VERSION = 615           # include/psg_hip.h; checked against psg_version() of the loaded library
 PSG_F32, PSG_BF16, PSG_F16 = 0, 1, 2
 PSG_EMPTY_UNIFORM, PSG_EMPTY_UNMASKED = 0, 1
 PSG_XATTN_MFMA, PSG_XATTN_SIMPLE, PSG_XATTN_MFMA_V1 = 0, 1, 2
@@ -108,6 +108,8 @@ SIGNATURES = {
     "psg_batch_split_gemm_w16": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "psg_batch_split_gemm_w32_plan": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
     "psg_batch_split_gemm_w32": [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "psg_batch_split_gemm_wb16_plan": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
+    "psg_batch_split_gemm_wb16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "psg_batch_split_gemm_w8_plan": [_vp, _i, _i, _i, _i, C.POINTER(_i)],
     "psg_batch_split_gemm_w8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "psg_split_gemm_int4_plan": [_vp, _i, _i, _i, _i, _i, C.POINTER(_i)],

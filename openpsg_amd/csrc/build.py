@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, "libpsg_hip.so")
-SOURCES = ["psg_core.hip", "psg_rowops.hip", "psg_attn.hip", "psg_attn_f32.hip", "psg_xattn_mfma.hip", "psg_xattn_dma.hip", "psg_gemm.hip", "psg_gemm_f32.hip", "psg_batch_gemm.hip", "psg_gemm_w8.hip", "psg_gemm_w4.hip", "psg_gemm_int4.hip", "psg_batch_gemm_q.hip", "psg_batch_gemm_s.hip", "psg_expand.hip", "psg_decode_layer.hip", "psg_split.hip", "psg_dense_gemm.hip", "psg_patch_embed.hip", "psg_selfattn_mfma.hip", "psg_prefill_attn_mfma.hip", "psg_pool.hip", "psg_train.hip", "psg_train_bwd.hip", "psg_train_bf16.hip", "psg_tree.hip", "psg_lt_gemm.hip"]
+SOURCES = ["psg_core.hip", "psg_rowops.hip", "psg_attn.hip", "psg_attn_f32.hip", "psg_xattn_mfma.hip", "psg_xattn_dma.hip", "psg_gemm.hip", "psg_gemm_f32.hip", "psg_batch_gemm.hip", "psg_gemm_w8.hip", "psg_gemm_w4.hip", "psg_gemm_int4.hip", "psg_batch_gemm_q.hip", "psg_batch_gemm_s.hip", "psg_batch_gemm_b3.hip", "psg_expand.hip", "psg_decode_layer.hip", "psg_split.hip", "psg_dense_gemm.hip", "psg_patch_embed.hip", "psg_selfattn_mfma.hip", "psg_prefill_attn_mfma.hip", "psg_pool.hip", "psg_train.hip", "psg_train_bwd.hip", "psg_train_bf16.hip", "psg_tree.hip", "psg_lt_gemm.hip"]
 HEADERS = ["psg_common.h", "psg_wave.h", "psg_streamk.h", "psg_gemm_q32.h", "psg_decode_math.h", "psg_train_rows.h", "psg_xattn_tile.h", "psg_split_b16.h", os.path.join("..", "..", "include", "psg_hip.h")]
 
 

@@ -276,6 +276,11 @@ class RelationTransformerHeadV4(nn.Module):
                                                # copies in the decode steps of <= 32 rows (psg_split_gemm_wb16: 2 bytes per
                                                # weight, three exact bf16 products).  A model whose matrices are not
                                                # bf16 values runs exactly as with False (`llm_engine.bf16_stream_active`)
+                 llm_bf16_value_resident=False,  # True (with llm_bf16_value_stream=True): every decoder matrix MUST be a bf16
+                                               # value and is held as its bf16 copy ONLY, a bf16-valued lm_head too - 2 bytes
+                                               # per weight instead of 12, no fp32 tensor and no split image; every product
+                                               # runs on three bf16 planes of the fp32 rows against that copy, the decode
+                                               # steps of 33..160 rows on psg_batch_gemm_b3.hip.  Inference only
                  train_precision=None,         # None | 'bf16': the gradient path in the model torch.autocast(bfloat16) gives the
                                                # reference - bf16 activations and products on fp32 masters, with
                                                # any `dtype`; None: the fp32 path of an fp32 head, a 16-bit head does not train
@@ -328,6 +333,13 @@ class RelationTransformerHeadV4(nn.Module):
                               f"llm_weight_quant={llm_weight_quant!r} the decode steps stream the quantised bytes - set one of "
                               "the two")
         self.llm_bf16_value_stream = llm_bf16_value_stream
+        if not isinstance(llm_bf16_value_resident, bool):
+            raise PsgHipError(f"llm_bf16_value_resident must be True or False, got {llm_bf16_value_resident!r}")
+        if llm_bf16_value_resident and not llm_bf16_value_stream:
+            raise PsgHipError("llm_bf16_value_resident=True keeps the bf16 copies of llm_bf16_value_stream as the ONLY copy of the "
+                              "LLM's matrices: it needs llm_bf16_value_stream=True (an fp32s head with an LLM stage and no "
+                              "llm_weight_quant)")
+        self.llm_bf16_value_resident = llm_bf16_value_resident
         if llm_quantize_lm_head and llm_weight_quant is None:
             raise PsgHipError("llm_quantize_lm_head=True needs llm_weight_quant='fp8' or 'mxfp4' or 'int4g'")
         # group-wise INT4 has the decode kernels of <= 32 rows only: no expand kernel, no 33..160-row kernel
@@ -599,7 +611,8 @@ class RelationTransformerHeadV4(nn.Module):
                                              resident=self.llm_weight_resident,
                                              batch_quant_stream=self.llm_batch_weight_stream == "quantised",
                                              batch_split_gemm=self.llm_batch_split_gemm == "own",
-                                             bf16_value_stream=self.llm_bf16_value_stream)
+                                             bf16_value_stream=self.llm_bf16_value_stream,
+                                             bf16_value_resident=self.llm_bf16_value_resident)
         return self
 
     def quantize_llm_weights(self, weights: dict) -> dict:
@@ -883,6 +896,10 @@ class RelationTransformerHeadV4(nn.Module):
             raise PsgHipError("llm_weight_resident='quantised' is an inference mode: the training forward would keep views of "
                               "an expansion scratch that the next product overwrites - build the head with "
                               "llm_weight_resident='all' to train")
+        if self.llm_bf16_value_resident and self.has_binary:
+            raise PsgHipError("llm_bf16_value_resident=True is an inference mode: the training forward reads the fp32 tensors "
+                              "of the LLM, which this head does not hold - build the head with llm_bf16_value_resident=False "
+                              "to train")
         dev = self.device
         feat = inputs['mask_features']
         assert feat.shape[0] == 1, 'only support batch size 1 for now.'                     # V4:112

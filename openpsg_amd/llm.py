@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from ._lib import PsgHipError
 from .config import PSGConfig
-from .llm_matrix import INT4_STREAM_OFF, W4_STREAM_AS_FP8, complete, dense_matrix, load_matrix  # noqa: F401  (the tables: also llm.<name>)
+from .llm_matrix import INT4_STREAM_OFF, W4_STREAM_AS_FP8, complete, dense_matrix, load_bf16_matrix, load_matrix  # noqa: F401  (the tables: also llm.<name>)
 
 
 # How the library runs one split-fp16 product [rows, K'] x [N, K']^T -> fp32: whole, or cut into column / row parts written
@@ -378,6 +378,32 @@ def _batch_split_route(form, N, K, rows, table=None):
 # Llama-2-7B shape lies wholly below its yardstick, nothing is listed.
 WB16_STREAM_OFF: frozenset = frozenset()
 
+# Decode steps with 33..160 rows of an fp32s engine whose matrices are resident as their bf16 copies only, engine option
+# bf16_value_resident: psg_batch_gemm_b3.hip runs the three bf16-plane products.  A FIXED table like
+# _BATCH_SPLIT_LIBRARY: a listed row range sends a measured loser (tools/bf16_resident_bench.py, tools/batch_split_bench.py's
+# method: the kernel's range of times not wholly below the yardstick's) to the yardstick - what this mode runs otherwise on
+# the same bf16 copy: split_b16x3 + the stacked-plane library product (`_stacked_b3`); a shape that is not listed takes the
+# kernel.
+#   key: (N, K) -> [(rows from, rows below), ...]
+# Measured at the Llama-2-7B shapes and 40 / 80 / 160 rows = 2 / 3 / 5 x tiles (profiles/bf16_resident_bench.json; the row
+# ranges are those of the tile counts; us per launch, median (min-max), own against yardstick).  The kernel wins the shapes
+# whose slabs are cut into many slices - o 15.9 / 22.6 / 30.5 against 23.2 / 29.9 / 38.1, down 31.9 / 45.9 / 65.6 against
+# 48.6 / 62.7 / 86.6 - and loses the wide ones, where a workgroup walks all of K for 128 weight rows and the matrix
+# instructions of three planes are not hidden behind 16 KB of weights per step:
+_BATCH_WB16_LIBRARY: dict = {
+    (12288, 4096): [(33, 161)],                                # q|k|v: 38.7 (36.2-43.5) against 38.8 (38.5-40.7): overlap; 55.0 / 76.8 against 47.8 / 64.9
+    (22016, 4096): [(33, 161)],                                # gate|up: 56.1 (54.6-62.9) against 55.2 (53.0-55.8); 84.5 / 120.0 against 71.2 / 93.5
+    (32000, 4096): [(33, 161)],                                # lm_head: 77.1 / 114.7 / 161.8 against 68.6 / 87.7 / 120.9
+}
+
+
+def _batch_wb16_route(N, K, rows, table=None):
+    """'own' or 'library' for a decode projection of `rows` fp32s rows over the bf16 copy of an [N, K] matrix."""
+    for lo, hi in (_BATCH_WB16_LIBRARY if table is None else table).get((int(N), int(K)), ()):
+        if lo <= rows < hi:
+            return "library"
+    return "own"
+
 _LAYER_MATRICES = ("wqkv", "wo", "wgu", "wdown")                  # a decoder layer's projections, by their key in `layers`
 # The streams a matrix can have in a decode step of <= 32 rows (`LlmMatrix.stream`), each also the name of the step
 # route on which every decoder matrix has it (`_decode_route`) and the suffix of its pair-form entry ops.split_gemm_<kind>:
@@ -389,7 +415,7 @@ _QUANT_STREAMS = {"w8": "fp8", "w4": "mxfp4", "int4": "int4"}      # ... of a qu
 class LlamaDecodeEngine:
     def __init__(self, weights: dict, cfg: PSGConfig, device, dtype=torch.bfloat16, n_layers=None, resid_dtype=None,
                  prefill_split=False, resident="all", batch_quant_stream=False, batch_split_gemm=False,
-                 bf16_value_stream=False):
+                 bf16_value_stream=False, bf16_value_resident=False):
         """prefill_split (fp32 engines): the prompt pass's projections as split-fp16 products on the 16-bit matrix cores,
         `linear_split` below; the decode steps stay exact fp32 (psg_gemm_f32.hip).
         resid_dtype: storage type of the residual stream; None = `dtype` (what HF keeps for a model cast to 16
@@ -401,7 +427,10 @@ class LlamaDecodeEngine:
         (`_batch_split`) instead of the library GEMM.
         bf16_value_stream (fp32s engines): decoder matrices and an lm_head that are bf16 VALUES (a bf16 checkpoint upcast on
         load; verified per tensor) keep a bf16 copy, and the decode steps of <= 32 rows stream it on psg_split_gemm_wb16
-        (`_decode_step_split` on the 'wb16' route) instead of the fp32 tensor."""
+        (`_decode_step_split` on the 'wb16' route) instead of the fp32 tensor.
+        bf16_value_resident (with bf16_value_stream): every decoder matrix must be a bf16 value and is held as its
+        bf16 copy ONLY (so is a bf16-valued lm_head) - no fp32 W', no split image; every product of the engine runs on the
+        three bf16 planes of its fp32 rows against that copy (`_linear_b3`, `_forward_split_b3`).  Inference only."""
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise PsgHipError(f"activation dtype must be float32, bfloat16 or float16, got {dtype}")
         if resident not in ("all", "quantised"):
@@ -410,6 +439,13 @@ class LlamaDecodeEngine:
         # product that reads a dense operand (more than 32 rows) has it expanded into a scratch buffer first (`_dense`)
         self.resident = resident
         lean = resident == "quantised"
+        if not isinstance(bf16_value_resident, bool):
+            raise PsgHipError(f"bf16_value_resident must be a bool, got {bf16_value_resident!r}")
+        if bf16_value_resident and not (bf16_value_stream is True and dtype == torch.float32 and prefill_split and not lean):
+            raise PsgHipError("bf16_value_resident keeps the bf16 copies that bf16_value_stream streams as the ONLY copy of an "
+                              "fp32s engine's matrices: it needs bf16_value_stream=True, dtype float32 with prefill_split and "
+                              "resident='all'")
+        self.bf16_value_resident = bf16_value_resident
         if lean and dtype == torch.float32 and not prefill_split:
             raise PsgHipError("resident='quantised': the exact fp32 mode (dtype='fp32') reads W' in every decode step, there is "
                               "nothing to drop - use dtype='fp32s' / 'mixed' / 'bf16' / 'fp16', or resident='all'")
@@ -432,7 +468,7 @@ class LlamaDecodeEngine:
         self.prefill_split = bool(prefill_split) and dtype == torch.float32
         dev_i = self.device.index or 0
         f32 = lambda k: weights[k].to(device=self.device, dtype=torch.float32).contiguous()   # noqa: E731
-        from .weights import BEXP_SUFFIX, GSCALE_SUFFIX, SCALE_SUFFIX, llm_quant_keys
+        from .weights import BEXP_SUFFIX, GSCALE_SUFFIX, SCALE_SUFFIX, is_quantized, llm_quant_keys
         if any(str(k).endswith(GSCALE_SUFFIX) for k in weights.keys()) and (lean or batch_quant_stream):
             opt = "resident='quantised'" if lean else "batch_quant_stream"
             raise PsgHipError(f"{opt} is not built for the INT4 format: there is no expand kernel and no 33..160-row kernel "
@@ -446,14 +482,27 @@ class LlamaDecodeEngine:
         # one `LlmMatrix` record per (row-concatenated) projection matrix (llm_matrix.py): `mats[l][key]`,
         # `lm_head_mat`, `proj_mat`.  `layers[l][key]` and `lm_head` are what the records hold as the dense operand W' - or the
         # record itself where a matrix is resident as bytes only - for readers outside the engine (and the layer norms)
-        load = lambda *keys: load_matrix(weights, keys, self.device, dtype, lean, self.prefill_split)   # noqa: E731
+        def load(*keys, may_be_fp32=False):
+            """The record of the matrix of `keys`.  bf16_value_resident: its bf16 copy only - or, for a matrix that is no bf16
+            value, the name of its first such part (may_be_fp32, the lm_head: the fp32 record it has without the option)."""
+            if not self.bf16_value_resident:
+                return load_matrix(weights, keys, self.device, dtype, lean, self.prefill_split)
+            if any(is_quantized(weights, k) for k in keys):
+                raise PsgHipError(f"bf16_value_resident: {keys[0]} is quantised - the option holds UNQUANTISED bf16 values "
+                                  "(llm_weight_resident='quantised' is the lean mode of a quantised model)")
+            rec = load_bf16_matrix(weights, keys, self.device, dtype)
+            if isinstance(rec, str) and may_be_fp32:
+                return load_matrix(weights, keys, self.device, dtype, False, self.prefill_split)
+            return rec
         held = lambda rec: rec if rec.w is None else rec.w                                             # noqa: E731
         self.embed = weights["language_model.model.embed_tokens.weight"].to(device=self.device, dtype=dtype).contiguous()
-        self.lm_head_mat = load("language_model.lm_head.weight")
+        # (an lm_head fine-tuned in fp32 keeps its fp32 tensor and today's routes, as DESIGN 20 keeps its stream)
+        self.lm_head_mat = load("language_model.lm_head.weight", may_be_fp32=True)
         self.lm_head = held(self.lm_head_mat)
         self.final_norm = f32("language_model.model.norm.weight")
         self.set_projection(weights["language_projection.weight"], weights["language_projection.bias"])
         self.mats, self.layers = [], []
+        not_bf16 = []                                          # bf16_value_resident: decoder matrices that are no bf16 values
         for l in range(self.n_layers):
             p = f"language_model.model.layers.{l}."
             for n, rows_ in (("q", m.hidden), ("k", m.kv_dim), ("v", m.kv_dim)):
@@ -464,13 +513,21 @@ class LlamaDecodeEngine:
                 if shp != (rows_, m.hidden):
                     raise PsgHipError(f"{p}self_attn.{n}_proj.weight has shape {shp}, expected {(rows_, m.hidden)} "
                                       f"({m.heads} query / {m.n_kv_heads} key-value heads of 128)")
-            self.mats.append(dict(
+            recs = dict(
                 wqkv=load(*[p + f"self_attn.{n}_proj.weight" for n in "qkv"]),
                 wo=load(p + "self_attn.o_proj.weight"),
                 wgu=load(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"),
-                wdown=load(p + "mlp.down_proj.weight")))
+                wdown=load(p + "mlp.down_proj.weight"))
+            not_bf16 += [rec for rec in recs.values() if isinstance(rec, str)]
+            if not_bf16:                                       # (looked at to the last layer: the refusal counts them)
+                continue
+            self.mats.append(recs)
             self.layers.append(dict({k: held(rec) for k, rec in self.mats[-1].items()},
                                     ln1=f32(p + "input_layernorm.weight"), ln2=f32(p + "post_attention_layernorm.weight")))
+        if not_bf16:
+            raise PsgHipError(f"bf16_value_resident=True (llm_bf16_value_resident) holds every decoder matrix as its bf16 copy "
+                              f"only, and {len(not_bf16)} decoder matrices are not bf16 values (the first: {not_bf16[0]}): "
+                              "llm_bf16_value_resident=False runs them on their fp32 tensors")
         layer_m = self._layer_mats()
         n_q, n_q4, n_qi = (sum(rec.fmt == f for rec in layer_m) for f in ("fp8", "mxfp4", "int4"))
         bytes_fmt = any(rec.fmt in ("fp8", "mxfp4") for rec in self.matrices())
@@ -483,7 +540,7 @@ class LlamaDecodeEngine:
         if 0 < n_q4 < len(layer_m):
             raise PsgHipError(f"{n_q4} of the {len(layer_m)} decoder-layer matrices are MXFP4-quantised: all or none")
         self._any_quant = n_q + n_q4 + n_qi > 0 or self.lm_head_mat.fmt is not None
-        self.use_skinny = True
+        self._use_skinny = True
         self.batch_quant_stream = bool(batch_quant_stream)
         if self.batch_quant_stream and not bytes_fmt:
             raise PsgHipError("batch_quant_stream streams a quantised LLM's bytes in the batched decode, and no matrix of this "
@@ -507,6 +564,8 @@ class LlamaDecodeEngine:
                            else "wb16" if every(lambda r: r.wb16 is not None) else None)
         self._skinny_ok = {}
         self._ones_cache = {}
+        if self.bf16_value_resident:
+            self._check_resident_routes()
         # row_invariant (fp32s engines): the prompt pass's projections and the language projection on psg_dense_gemm - one
         # k-ordered accumulation per output element whatever the row count of the call - instead of the library GEMM, whose
         # kernel choice follows the row count: a pair decoded in a batch of 3 (decodes DEALT over the ranks of a pair-sharded
@@ -565,12 +624,34 @@ class LlamaDecodeEngine:
         ang = torch.arange(4096, dtype=torch.float32)[:, None] * inv_freq[None, :]
         self.rope = (ang.cos().contiguous().to(self.device), ang.sin().contiguous().to(self.device))
 
+    def _check_resident_routes(self):
+        """bf16_value_resident has no dense fallback: the decode steps of <= 32 rows run on the 'wb16' route of
+        `_decode_step_split` or not at all.  Raises, naming the first condition of `_can_wb16` the model fails."""
+        why = self._wb16_blockers(1)
+        if why:
+            raise PsgHipError(f"bf16_value_resident: the decode steps cannot stream the bf16 copies ({why[0]}), and there is no "
+                              "fp32 tensor to fall back on - use llm_bf16_value_resident=False")
+
+    @property
+    def use_skinny(self):
+        return self._use_skinny
+
+    @use_skinny.setter
+    def use_skinny(self, on):
+        if not on and getattr(self, "bf16_value_resident", False):
+            raise PsgHipError("bf16_value_resident: use_skinny=False sends the decode steps to library products on dense fp32 "
+                              "tensors, which this engine does not hold - build it with llm_bf16_value_resident=False")
+        self._use_skinny = bool(on)
+
     @property
     def row_invariant(self):
         return self._row_invariant
 
     @row_invariant.setter
     def row_invariant(self, on):
+        if on and self.bf16_value_resident:
+            raise PsgHipError("bf16_value_resident: the row-invariant prompt pass (pair-sharded pipelines) reads dense "
+                              "interleaved images of every weight - build the engine with llm_bf16_value_resident=False")
         if on and self.resident == "quantised":
             raise PsgHipError("resident='quantised': the row-invariant prompt pass (pair-sharded pipelines) reads dense "
                               "interleaved images of every weight - build the engine with resident='all'")
@@ -610,6 +691,8 @@ class LlamaDecodeEngine:
         the slot's next expansion: expand per matrix, immediately before its product."""
         if w.w is not None:
             return w.two_plane() if unscaled else w.w
+        if w.fmt is None:                                      # bf16_value_resident: `_linear_b3` is THE route of such a record
+            raise PsgHipError(f"{w.name}: held as its bf16 copy only (bf16_value_resident), there is no dense operand")
         buf = self._scratch_for(self._slot)
         if unscaled:
             buf = buf.view(torch.float16)
@@ -698,6 +781,8 @@ class LlamaDecodeEngine:
         through hipBLASLt; decode steps of 33..160 rows (several images' pairs, 16-bit modes) through whichever of
         psg_batch_gemm's variants and the library was measured fastest for the shape (_plan_batch_mm) - or, with
         batch_quant_stream, over a quantised matrix's bytes (`_batch_quant`; batch_stream=False: the caller keeps W')."""
+        if rec.w is None and rec.fmt is None:                  # bf16_value_resident: the bf16 copy is the operand of every product
+            return self._linear_b3(x, rec, decode, batch_stream)
         kind, args = rec.stream or (None, None)
         if (kind in _QUANT_STREAMS and self.use_skinny and x.shape[0] <= 32 and x.dtype == rec.dtype
                 and (self.prefill_split or x.dtype != torch.float32)):
@@ -753,6 +838,33 @@ class LlamaDecodeEngine:
         if rec.split is not None and x.dtype == torch.float32:
             return self.linear_split(x, rec)
         return F.linear(x, w)
+
+    def _stacked_b3(self, x3, rec, plan=None):
+        """The stacked-plane library product of bf16_value_resident: x3 bf16 [3, rows, K], the planes
+        [x0; x1; x2] of `split_b16x3`, against the bf16 copy of `rec` in ONE library product of 3 x rows rows with an fp32
+        result.  The planes are stacked [x2; x1; x0], so the result's slices are [y2, y1, y0] and a reader that adds slices
+        in slot order - every consumer of `ops.Partials` - computes (y2 + y1) + y0: THE order of the three plane sums, small
+        planes first, as psg_split_gemm_wb16's flush.  Every product is exact; only fp32 accumulation is left."""
+        _, rows, K = x3.shape
+        y = _split_mm(x3.flip(0).view(3 * rows, K), rec.wb16, plan)
+        return ops.Partials(y.view(3, rows, rec.shape[0]))
+
+    def _linear_b3(self, x, rec, decode=False, batch_stream=True):
+        """`linear` over a record held as its bf16 copy only: fp32 rows, three bf16 planes (exact), fp32 slices.  <= 32 rows:
+        psg_split_gemm_wb16 (the decode step's kernel); decode steps of 33..160 rows (`forward_batch`, beam levels):
+        psg_batch_split_gemm_wb16 unless `_BATCH_WB16_LIBRARY` lists the shape; everything else - more rows, the trie pass
+        (batch_stream=False), shapes the kernels do not take - `split_b16x3` + the stacked-plane library product."""
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise PsgHipError(f"{rec.name}: held as its bf16 copy only (bf16_value_resident), it takes fp32 rows, got {x.dtype} "
+                              f"{tuple(x.shape)}")
+        rows, (N, K) = int(x.shape[0]), rec.shape
+        x3 = ops.split_b16x3(x if x.is_contiguous() else x.contiguous())
+        fits = N % 16 == 0 and K % 64 == 0
+        if fits and rows <= 32:
+            return ops.split_gemm_wb16(x3, rec.wb16)
+        if fits and decode and batch_stream and 32 < rows <= 160 and _batch_wb16_route(N, K, rows) == "own":
+            return ops.batch_split_gemm_wb16(x3, rec.wb16)
+        return self._stacked_b3(x3, rec)
 
     def _batch_quant(self, x, rec):
         """Decode projection of 33..160 rows over a quantised matrix on its byte / nibble stream (psg_batch_gemm_q.hip,
@@ -913,6 +1025,8 @@ class LlamaDecodeEngine:
         library GEMM of the operand [xh; xl] (2 x rows rows) against the fp16 weight over K - two thirds of the flops, and
         no split copy of the weights at all; its [2, rows, N] result is summed by the reader (`slices`), the only scale
         left is the row's."""
+        if self.bf16_value_resident:
+            return self._forward_split_b3(resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape, keep_rows)
         m = self.cfg.llm
         rows, D = resid.shape
         planes = 2 if self.layer_kind in ("w16", "w8", "w4") else 3
@@ -964,6 +1078,37 @@ class LlamaDecodeEngine:
                 ops.rmsnorm(resid, d.dense(), self.final_norm, m.rms_eps, n)
             else:
                 a, inv_r = ops.rmsnorm_split(resid, d, self.layers[l + 1]["ln1"], m.rms_eps, planes=planes)
+        return n
+
+    def _forward_split_b3(self, resid, tok_pair, tok_pos, kc, vc, ctx_len, prefill_shape, keep_rows):
+        """`_forward_split`'s third plane mode, bf16_value_resident: three bf16 planes of the fp32 rows against
+        the bf16 copies.  RMSNorm and SwiGLU write the planes [3][rows][K] directly (no row maximum, no scale), a
+        projection is ONE library product of the stacked planes (`_stacked_b3`: the flop count of the 3K product), and its
+        three fp32 slices go to the reader as `ops.Partials`, summed (y2 + y1) + y0 while loading."""
+        m = self.cfg.llm
+        rows, D = resid.shape
+
+        proj = self._stacked_b3                                # (whole: `_SPLIT_PLAN_TABLE` holds no measured bf16 shape)
+        a = ops.rmsnorm_split_b16x3(resid, None, self.layers[0]["ln1"], m.rms_eps)
+        q = torch.empty((rows, D), device=self.device, dtype=torch.float32)
+        att = torch.empty_like(q)
+        n = None
+        for l, (L, M) in enumerate(zip(self.layers, self.mats)):
+            ops.rope_kvwrite(proj(a, M["wqkv"]), tok_pair, tok_pos, self.rope, m.heads, m.head_dim, ctx_len, q, kc[l], vc[l],
+                             kv_heads=self.kv)
+            ops.prefill_attn(q, kc[l], vc[l], tok_pos, prefill_shape[0], prefill_shape[1], m.heads, m.head_dim, ctx_len, att,
+                             kv_heads=self.kv)
+            last = l == len(self.layers) - 1
+            if keep_rows is not None and last:
+                att, resid = self._gather_kept(att, resid, keep_rows)
+            o = proj(ops.split_b16x3(att), M["wo"])
+            gu = proj(ops.rmsnorm_split_b16x3(resid, o, L["ln2"], m.rms_eps), M["wgu"])
+            d = proj(ops.silu_mul_split_b16x3(gu), M["wdown"])
+            if last:                                            # the lm_head reads fp32 rows
+                n = torch.empty_like(resid)
+                ops.rmsnorm(resid, d, self.final_norm, m.rms_eps, n)
+            else:
+                a = ops.rmsnorm_split_b16x3(resid, d, self.layers[l + 1]["ln1"], m.rms_eps)
         return n
 
     @property
@@ -1044,10 +1189,23 @@ class LlamaDecodeEngine:
         """fp32s decode steps over bf16-valued decoder layers (option bf16_value_stream): every projection as
         psg_split_gemm_wb16 - 2 bytes per weight, three bf16 products (the exact three-plane form of the fp32 rows) - the row
         kernels writing its three-plane operand directly (`_decode_step_split`)."""
+        return not self._wb16_blockers(rows)
+
+    def _wb16_blockers(self, rows):
+        """THE conditions of the 'wb16' decode route, as the reasons that hold against it (none: the route is open)."""
         m = self.cfg.llm
-        return (self.layer_kind == "wb16" and self.prefill_split and self.use_skinny and rows <= 32
-                and self.dtype == torch.float32 and m.hidden % 64 == 0 and m.inter % 64 == 0 and m.hidden <= 8192
-                and self.qkv_width % 16 == 0 and not any(tuple(w.shape) in WB16_STREAM_OFF for w in self._layer_mats()))
+        off = [tuple(w.shape) for w in self._layer_mats() if tuple(w.shape) in WB16_STREAM_OFF]
+        conditions = (
+            (self.layer_kind == "wb16", f"the decoder layers are of kind {self.layer_kind!r}, not bf16 copies"),
+            (self.prefill_split and self.dtype == torch.float32, "the engine is not an fp32s engine"),
+            (self.use_skinny, "use_skinny is off"),
+            (rows <= 32, f"{rows} rows exceed the 32 of the decode-step kernel"),
+            (m.hidden % 64 == 0, f"hidden = {m.hidden} is no multiple of 64"),
+            (m.inter % 64 == 0, f"inter = {m.inter} is no multiple of 64"),
+            (m.hidden <= 8192, f"hidden = {m.hidden} exceeds 8192"),
+            (self.qkv_width % 16 == 0, f"the q|k|v width {self.qkv_width} is no multiple of 16"),
+            (not off, f"a decoder matrix of shape {off[:1]} is listed in WB16_STREAM_OFF"))
+        return [why for ok, why in conditions if not ok]
 
     def _decode_route(self, rows, slot=0, per_call=True):
         """THE route of a decode step of `rows` rows: a key of `_STREAM_PLANES` (`_decode_step_split`), 'persist'
@@ -1198,6 +1356,9 @@ class LlamaDecodeEngine:
         if self.resident == "quantised":
             raise PsgHipError("resident='quantised': the training forward would keep views of a scratch buffer that the next "
                               "product overwrites - train on an engine built with resident='all'")
+        if self.bf16_value_resident:
+            raise PsgHipError("bf16_value_resident: an inference mode - the training forward reads the fp32 tensors this engine "
+                              "does not hold; train on an engine built with llm_bf16_value_resident=False")
         m = self.cfg.llm
         K, S, D = X.shape
         dev = self.device
@@ -1286,6 +1447,8 @@ class LlamaDecodeEngine:
             key = key + (("beam", beam),)
         if self.bf16_value_stream:
             key = key + ("bf16_value_stream",)
+        if self.bf16_value_resident:
+            key = key + ("bf16_value_resident",)
         ent = self._graphs.get(key)
         if ent is not None:
             self._graphs.move_to_end(key)

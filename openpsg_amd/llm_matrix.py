@@ -45,7 +45,9 @@ class LlmMatrix:
       fp8_img  (bytes, row scales): the exact FP8 image of a W4_STREAM_AS_FP8 shape
       int4_img (code image, group image) of an INT4 matrix that streams as codes
       h16      the exact fp16 image of W' / s (of q) for the two-plane prompt pass of an fp32s engine
-      w16, wb16  the fp16 / bf16 copy of an unquantised fp32 matrix whose every element is such a value
+      w16, wb16  the fp16 / bf16 copy of an unquantised fp32 matrix whose every element is such a value (bf16_value_resident,
+               DESIGN 24: `wb16` is then the ONLY thing the record holds - no w, no split, no packed - and the operand of
+               every product over it)
       split    ([wh | wl | wh] fp16, the rows' inverse scales): the three-product prompt pass of an fp32s engine
       packed   ([wh | wl], inverse scales) of a generic lm_head under batch_split_gemm
       i2       the interleaved hi / lo image of the row-invariant path, made at first use (`interleaved`)
@@ -179,6 +181,39 @@ def _int4_matrix(weights, keys, device, dtype):
     return rec
 
 
+def bf16_valued(t, chunk_elems: int = 1 << 22) -> bool:
+    """Is every element of `t` a bf16 value (`t.bfloat16().float() == t`, the test `complete` makes)?  Checked where `t`
+    lives, in row chunks of at most `chunk_elems` elements: the temporaries are a chunk's, not the tensor's.  A tensor that
+    is already torch.bfloat16 passes without a look."""
+    if t.dtype == torch.bfloat16:
+        return True
+    t2 = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(1, -1)
+    rows = max(1, int(chunk_elems) // max(1, int(t2.shape[1])))
+    return all(torch.equal((c := t2[r0:r0 + rows]).bfloat16().float(), c.float()) for r0 in range(0, t2.shape[0], rows))
+
+
+def load_bf16_matrix(weights, keys, device, dtype, chunk_elems: int = 1 << 22):
+    """bf16_value_resident: the record of the (row-concatenated) matrix of `keys` as its bf16 copy ONLY - or the
+    first key whose tensor is not a bf16 value (a str: the caller decides what that means for the matrix).  The check and
+    the conversion run where a tensor lives, chunk by chunk, and every chunk is copied straight into its rows of the one
+    device tensor: the fp32 matrix never reaches `device`, and the load's peak above the record is one chunk."""
+    parts = [weights[k] for k in keys]
+    K = int(parts[0].shape[1])
+    if any(t.dim() != 2 or int(t.shape[1]) != K for t in parts):
+        raise PsgHipError(f"{keys}: parts must be 2-D with the same K, got {[tuple(p.shape) for p in parts]}")
+    out = torch.empty((sum(int(t.shape[0]) for t in parts), K), device=device, dtype=torch.bfloat16)
+    rows, r = max(1, int(chunk_elems) // max(1, K)), 0
+    for k, t in zip(keys, parts):
+        for r0 in range(0, t.shape[0], rows):
+            c = t[r0:r0 + rows]
+            b = c.bfloat16()                                   # (`bf16_valued`'s test, on the chunk that is copied anyway)
+            if c.dtype != torch.bfloat16 and not torch.equal(b.float(), c.float()):
+                return k
+            out[r + r0:r + r0 + c.shape[0]].copy_(b)
+        r += t.shape[0]
+    return LlmMatrix(keys[0], out.shape, dtype, device, wb16=out)
+
+
 def load_matrix(weights, keys, device, dtype, lean=False, prefill_split=False):
     """The record of the (row-concatenated) matrix of `keys`, W' in `dtype`, with its stream parts when every part is
     quantised (per-row scales commute with the concatenation).  lean: resident='quantised'; prefill_split: an fp32s engine
@@ -233,7 +268,8 @@ def complete(layer_mats, lm_head, dtype, prefill_split=False, llm_w16=False, bf1
     32000 x 4096."""
     mats = list(layer_mats) + [lm_head]
     for rec in mats:
-        if dtype != torch.float32 or rec.fmt is not None:      # (a quantised matrix has its own stream: never a copy)
+        # (a quantised matrix has its own stream: never a copy; one resident as its bf16 copy only has nothing to test)
+        if dtype != torch.float32 or rec.fmt is not None or rec.w is None:
             continue
         if llm_w16 and torch.equal((h := rec.w.half()).float(), rec.w):
             rec.w16 = h
@@ -241,10 +277,11 @@ def complete(layer_mats, lm_head, dtype, prefill_split=False, llm_w16=False, bf1
             rec.wb16 = b
     if prefill_split:
         for rec in layer_mats:
-            if rec.fmt not in ("fp8", "mxfp4"):
+            if rec.fmt not in ("fp8", "mxfp4") and rec.w is not None:
                 rec.split = ops.split_f16x3(rec.w, weights=True)
     lm = lm_head
-    if (batch_split_gemm and lm.fmt is None and lm.dtype == torch.float32 and lm.w16 is None and lm.shape[0] % 16 == 0
+    if (batch_split_gemm and lm.fmt is None and lm.w is not None and lm.dtype == torch.float32 and lm.w16 is None
+            and lm.shape[0] % 16 == 0
             and lm.shape[1] % 64 == 0):
         img, inv = ops.split_f16x3(lm.w, weights=True)
         lm.packed = (img[:, :2 * lm.shape[1]].contiguous(), inv)

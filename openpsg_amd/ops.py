@@ -1304,6 +1304,42 @@ def batch_split_gemm_w32(x2, inv_scale, w_img, col_scale, K, lo_off=None, mode=0
                      _p(col_scale)), M, N, K, mode)
 
 
+def _x3_args(name, x3, wb16):
+    if not (isinstance(x3, torch.Tensor) and x3.dim() == 3 and x3.shape[0] == 3 and x3.dtype == torch.bfloat16
+            and x3.is_contiguous()):
+        raise PsgHipError(f"{name}: x3 must be the contiguous bf16 planes [3, M, K] of split_b16x3, got "
+                          f"{getattr(x3, 'dtype', type(x3))} {tuple(getattr(x3, 'shape', ()))}")
+    K = x3.shape[2]
+    if not (isinstance(wb16, torch.Tensor) and wb16.dim() == 2 and wb16.dtype == torch.bfloat16 and wb16.shape[1] == K
+            and wb16.is_contiguous() and wb16.device == x3.device):
+        raise PsgHipError(f"{name}: w must be contiguous bf16 [N, {K}] on {x3.device}, got "
+                          f"{getattr(wb16, 'dtype', type(wb16))} {tuple(getattr(wb16, 'shape', ()))}")
+    if not wb16.is_cuda:
+        raise PsgHipError(f"{name}: w must live in HBM (got a {wb16.device} tensor); this path has no CPU fallback")
+    return x3.shape[1], wb16.shape[0], K
+
+
+def batch_split_gemm_wb16_plan(M, N, K, device, mode=0) -> int:
+    """Slices `batch_split_gemm_wb16` writes for x3 [3, M, K] against w [N, K]: a function of (N, K, mode) only; raises
+    where the kernel does not take the shape."""
+    import ctypes
+    lib = _lib.load()
+    dev = torch.device(device)
+    s = ctypes.c_int(0)
+    check(lib.psg_batch_split_gemm_wb16_plan(_lib.ctx(dev.index or 0), int(M), int(N), int(K), int(mode), ctypes.byref(s)),
+          "psg_batch_split_gemm_wb16_plan")
+    return s.value
+
+
+def batch_split_gemm_wb16(x3, w, mode=0) -> Partials:
+    """`split_gemm_wb16` for 33..160 fp32 rows given as the planes of `split_b16x3`, over a weight that is a bf16 value: fp32
+    slices [S, M, N] of x2 . w + x1 . w + x0 . w, every product exact, one fp32 accumulator per output element
+    (psg_batch_split_gemm_wb16).  No scales.  N % 16 == 0, K % 64 == 0, 16-byte aligned operands.  A row's slices
+    do not depend on M or on the other rows.  mode 1 / 2: slab-aligned / stream-K ranges, 0 = the library's estimate."""
+    M, N, K = _x3_args("batch_split_gemm_wb16", x3, w)
+    return _batch_q("batch_split_gemm_wb16", x3, True, (_p(x3), _p(w, name="w")), M, N, K, mode)
+
+
 def skinny_gemm_fused(kind, x_out, w, sync, *, inp=None, resid=None, norm_w=None, eps=0.0, attn=None, splits=None):
     """Decode projection with its producer row operation in the same launch (psg_skinny_gemm_fused):
     the prologue `kind` computes x_out [M, K] from `inp` (Partials / activation tensor / None), then

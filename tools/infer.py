@@ -66,6 +66,9 @@ def parser():
     ap.add_argument("--llm-bf16-value-stream", action="store_true",
                     help="(--dtype fp32s) stream LLM matrices that are bf16 values - a bf16 checkpoint such as Mistral-7B or "
                     "Llama-3 - as bf16 in the decode steps: 2 bytes per weight, three exact bf16 products")
+    ap.add_argument("--llm-bf16-value-resident", action="store_true",
+                    help="(with --llm-bf16-value-stream) keep a bf16-valued LLM resident as its bf16 copies only: 2 bytes per "
+                    "weight instead of 12, every product on three exact bf16 planes of the fp32 rows; inference only")
     ap.add_argument("--llm-decode", choices=["greedy", "constrained"], default="greedy",
                     help="constrained: every decode step's arg-max runs over the relation-name trie only - one valid relation "
                     "per selected pair in max_depth + 1 steps instead of 16")
@@ -99,6 +102,7 @@ def build_head(a, dev):
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
                                          llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
+                                         llm_bf16_value_resident=bool(getattr(a, "llm_bf16_value_resident", False)),
                                          llm_decode=getattr(a, "llm_decode", "greedy"), **_beam_options(a))
         cfg = PSGConfig(qformer=QFormerConfig(), llm=llm, max_object_num=a.objects)
         head.load_weights(make_weights_device(cfg, 0, dev, with_llm=False))
@@ -112,6 +116,7 @@ def build_head(a, dev):
                                          llm_batch_weight_stream=getattr(a, "llm_batch_weight_stream", "dense"),
                                          llm_batch_split_gemm=getattr(a, "llm_batch_split_gemm", "library"),
                                          llm_bf16_value_stream=bool(getattr(a, "llm_bf16_value_stream", False)),
+                                         llm_bf16_value_resident=bool(getattr(a, "llm_bf16_value_resident", False)),
                                          llm_decode=getattr(a, "llm_decode", "greedy"), **_beam_options(a))
         head.load_weights(make_weights_device(cfg, 0, dev))
     if a.checkpoint:
